@@ -20,8 +20,15 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   `--config configs3` = PWCDCNet use_dc=True batch 8; `--config configs4` = 960x1920
   batch 8 per GPU on 2 GPUs (BASELINE.json configs[4]; an explicit `--gpus 1` runs one
   rank's share of it); `--config configs2` = configs[1] per GPU on 8 GPUs.
+  `--dump-outputs DIR`: after the timed region, what its last step returned (flows_final and
+  the flows_pyramid levels) goes to DIR/<name>.npy in float32 (rank r > 0 of N > 1:
+  DIR/rank<r>_<name>.npy), at most 64 MB in all -- larger outputs as a fixed, seeded sample
+  of their elements.  Inputs and weights are seeded: the same arguments give the same inputs.
 
-Extra objects in the line:
+A plain run does set-up, warm-up, the K timed steps and the line.  Everything below needs
+`--full` (each leg still has its --no-* switch there):
+  value_one_stream  the same K steps one after the other on one stream (pipelined runs);
+  value_fp32_only   the same K steps with fp32 MFMA everywhere (PWCDCNet(f16x2=False));
   roofline       dominant kernel (by summed duration).  For the Winograd kernel `achieved`
                  is the rate of the multiplies the MFMA units EXECUTE (a fraction of a
                  hardware peak, always <= 1); the direct-convolution ("algorithmic") rate it
@@ -116,7 +123,17 @@ def parse(argv=None):
                          "0 / 1 = the plain one-stream loop.  The per-kernel legs always come from the one-stream loop.")
     ap.add_argument("--persistent-outputs", action="store_true",
                     help="PWCDCNet(persistent_outputs=True): replays write into the plan's own output tensors")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the one-stream loop, the per-kernel profile pass and roofline "
+                         "figures, the op-level correlation/warp leg, the fp32-only forward, the CPU baseline and the parity "
+                         "checks against the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.op_leg_only:
+        ap.error("--op-leg-only runs no timed steps: nothing to --dump-outputs")
     raw = sys.argv[1:] if argv is None else list(argv)
     args.gpus_given = any(a == "--gpus" or a.startswith("--gpus=") for a in raw)
     if args.config:
@@ -159,6 +176,47 @@ def spawn(args):
 # measured: 2160 pairs/s with 2 sampled steps of 20, 2189 with none)
 SAMPLE_EVERY = 20
 
+# --dump-outputs: bytes of array data per run (the .npy headers fit in what is left of 64 MiB)
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES, prefix=""):
+    """Writes {name: array} as path/<prefix><name>.npy in float32.  When the arrays together hold more than `budget` bytes,
+    each is replaced by a sample of its share of the budget: the flattened array at sorted indices drawn with seed 0, the same
+    indices on every run for the same shapes, so that two builds can be compared element for element.  Returns
+    {file name: shape written}."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        if total > budget:
+            keep = int(budget * (a.nbytes / total)) // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        fname = f"{prefix}{name}.npy"
+        np.save(os.path.join(path, fname), a)
+        written[fname] = a.shape
+    return written
+
+
+def synthetic_pairs(B, H, Wd, dev, rank):
+    """The inference bench's inputs on rank `rank`: two (B, H, Wd, 3) uniform[0,1) image batches, seeded on the device."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234 + rank)
+    im0 = torch.rand((B, H, Wd, 3), generator=g, device=dev, dtype=torch.float32)
+    im1 = torch.rand((B, H, Wd, 3), generator=g, device=dev, dtype=torch.float32)
+    return im0, im1
+
+
+def flows_arrays(out):
+    """(flows_final, flows_pyramid) of a forward -> {name: host array}."""
+    final, pyramid = out[0], out[1]
+    arrays = {"flows_final": final.detach().cpu().numpy()}
+    for l, p in enumerate(pyramid):
+        arrays[f"flows_pyramid_{l}"] = p.detach().cpu().numpy()
+    return arrays
+
 
 def train_mode(args, dist, dev, rank, world):
     """--mode train: K optimisation steps of the training path on this rank's batch (synthetic pairs and flows,
@@ -191,6 +249,9 @@ def train_mode(args, dist, dev, rank, world):
         loss = tn.step(im0, im1, gt)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": np.asarray([float(loss)], np.float32)},
+                     budget=DUMP_BYTES // world, prefix="" if rank == 0 else f"rank{rank}_")
     stats = gather_stats(dict(pairs=float(B * args.steps), seconds=elapsed), dist, dev)
     if rank == 0:
         value, ms_per_step, _, _ = aggregate_throughput(stats, args.steps)
@@ -289,11 +350,8 @@ def main():
             print(json.dumps({"roofline_hbm": corr_warp_op_leg(net, args.batch, args.height, args.width, dev)}))
         return
 
-    g = torch.Generator(device=dev)
-    g.manual_seed(1234 + rank)
     B, H, Wd = args.batch, args.height, args.width
-    im0 = torch.rand((B, H, Wd, 3), generator=g, device=dev, dtype=torch.float32)
-    im1 = torch.rand((B, H, Wd, 3), generator=g, device=dev, dtype=torch.float32)
+    im0, im1 = synthetic_pairs(B, H, Wd, dev, rank)
 
     for _ in range(args.warmup):
         net(im0, im1)
@@ -325,7 +383,7 @@ def main():
     full_summary = None
     dominant = None
     full_steps = min(args.steps, 5)
-    if not args.no_op_timing and full_steps > 0:
+    if args.full and not args.no_op_timing and full_steps > 0:
         keep_streams, net.streams = net.streams, 1      # per-kernel durations: single-stream form of the same forward
         for _ in range(2):
             net(im0, im1)
@@ -340,6 +398,12 @@ def main():
         for _ in range(2):
             net(im0, im1)
         torch.cuda.synchronize()
+    elif not args.no_op_timing and full_steps > 0:
+        # as many untimed forwards as the profile pass runs (without its events): the timed region starts from the same device
+        # state with or without --full
+        for _ in range(4 + full_steps):
+            net(im0, im1)
+        torch.cuda.synchronize()
 
     # events inside the timed region only when its kernels run one after the other on the caller's stream
     timer = None if (dominant is None or overlapped) else OpTimer(only=(dominant, "cost_volume", "warp_kernel"))
@@ -348,7 +412,7 @@ def main():
 
     def one_stream_loop():
         """K steps one after the other on this stream, HIP events around the dominant kernel's and the correlation's launches in
-        the sampled steps -> (seconds, host seconds to issue)"""
+        the sampled steps -> (seconds, host seconds to issue, what the last step returned)"""
         sync_all()
         t0 = time.perf_counter()
         if timer is not None:
@@ -361,7 +425,7 @@ def main():
                 out = net(im0, im1)
         issue = time.perf_counter() - t0              # host time to ISSUE the K forwards (the GPU runs behind)
         sync_all()
-        return time.perf_counter() - t0, issue
+        return time.perf_counter() - t0, issue, out
 
     one_stream = None
     if pipe is not None:
@@ -374,11 +438,17 @@ def main():
         issue_elapsed = time.perf_counter() - t0
         sync_all()
         elapsed = time.perf_counter() - t0
+        last_out = ticket.result()
         del ticket
         st_rep = pipe.status()
     else:
-        elapsed, issue_elapsed = one_stream_loop()
+        elapsed, issue_elapsed, last_out = one_stream_loop()
         st_rep = net.status()                         # the kernels' status words (fp16 range / stream-K): nothing may have fired
+    if args.dump_outputs:
+        # before any other forward: with --persistent-outputs the next replay would overwrite these tensors
+        dump_outputs(args.dump_outputs, flows_arrays(last_out), budget=DUMP_BYTES // world,
+                     prefix="" if rank == 0 else f"rank{rank}_")
+    del last_out
 
     stats = gather_stats(dict(pairs=float(B * args.steps), seconds=elapsed, issue_seconds=issue_elapsed), dist,
                          "cpu" if args.share_gpu else dev)
@@ -396,10 +466,10 @@ def main():
     if rank != 0:
         return
 
-    if pipe is not None:
+    if pipe is not None and args.full:
         # the plain loop beside it: K more steps one after the other on one stream (rank 0), with the HIP events the per-kernel
         # legs need -- in the pipelined region the kernels of two steps overlap and a launch has no duration of its own
-        e1, i1 = one_stream_loop()
+        e1, i1, _ = one_stream_loop()
         one_stream = {"value": B * args.steps / e1, "ms_per_step": 1e3 * e1 / args.steps,
                       "host_issue_ms_per_step": 1e3 * i1 / args.steps}
         net.status()
@@ -448,7 +518,7 @@ def main():
                                   "stream-K workspace and status words), each replica on a HIP stream with a hardware queue of "
                                   "its own; every step is a whole batch through the whole network and all K steps complete "
                                   "inside the timed bracket; results are bit-identical to the one-stream loop "
-                                  "(tests/test_gpu_model.py::test_pipeline_matches_single_stream); value_one_stream = the same "
+                                  "(tests/test_gpu_model.py::test_pipeline_matches_single_stream); value_one_stream (--full) = the same "
                                   "K steps one after the other on one stream",
                           "streams": pipe.stream_report.get("verdict") if pipe.stream_report else None}
                          if pipe is not None else None),
@@ -590,7 +660,7 @@ def main():
         line["kernels"] = kernels
         line["gpu_busy_ms_per_step_profile_pass"] = sum(d["ms"] for d in full_summary.values()) / full_steps
 
-    if not args.no_op_leg:
+    if args.full and not args.no_op_leg:
         line["roofline_hbm"] = corr_warp_op_leg(net, B, H, Wd, dev)
         if "roofline_hbm_in_step" in line:
             # the same launches inside the timed forward (HIP events around them in sampled steps; flows ~ 0 there): VERDICT r5 1c
@@ -614,7 +684,7 @@ def main():
                 hb["traffic_per_kernel"] = t.get("per_kernel")
                 hb["traffic_source"] = "profiles/pmc_traffic.json: " + t["source"]
 
-    if not args.no_fp32_leg and world == 1 and net.f16x2:
+    if args.full and not args.no_fp32_leg and world == 1 and net.f16x2:
         # the same forward with fp32 MFMA everywhere (PWCDCNet(f16x2=False)): what the split arithmetic buys, in the same line
         net32 = pwcnet_amd.PWCDCNet(use_dc=args.use_dc, persistent_outputs=args.persistent_outputs,
                                     streams=args.streams if args.streams > 0 else None, f16x2=False)
@@ -633,7 +703,7 @@ def main():
         line["max_abs_flow_diff_vs_fp32_only"] = float((o16[0] - o32[0]).abs().max())
         del net32, o32, o16
 
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line.update(cpu_baseline_and_parity(net, wts, args, dev))
 
     print(json.dumps(line))

@@ -4,11 +4,11 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/r6t
 rm -rf $O; mkdir -p $O
 cd $R
-C="python bench.py --pipeline 0 --steps 150 --warmup 10 --no-cpu-baseline --no-op-leg --no-fp32-leg --no-op-timing"
+C="python bench.py --full --pipeline 0 --steps 150 --warmup 10 --no-cpu-baseline --no-op-leg --no-fp32-leg --no-op-timing"
 echo "== one process, all CUs, one-stream loop" | tee -a $O/exp_cu_partition.txt
 timeout 300 $C 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), 'pairs/s', round(d['ms_per_step'],3), 'ms')" | tee -a $O/exp_cu_partition.txt
 echo "== one process, all CUs, pipeline depth 3" | tee -a $O/exp_cu_partition.txt
-timeout 300 python bench.py --steps 150 --warmup 10 --no-cpu-baseline --no-op-leg --no-fp32-leg --no-op-timing 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), 'pairs/s', round(d['ms_per_step'],3), 'ms')" | tee -a $O/exp_cu_partition.txt
+timeout 300 python bench.py --full --steps 150 --warmup 10 --no-cpu-baseline --no-op-leg --no-fp32-leg --no-op-timing 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), 'pairs/s', round(d['ms_per_step'],3), 'ms')" | tee -a $O/exp_cu_partition.txt
 for parts in 2 4; do
   echo "== $parts processes, 256 / $parts CUs each (HSA_CU_MASK), one-stream loops side by side" | tee -a $O/exp_cu_partition.txt
   per=$((256 / parts))

@@ -5,7 +5,7 @@ mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -x -q -k "block_cost_volume" 2>&1 | tail -25 > $O/new_tests.txt
 timeout 900 python -m pytest tests/test_gpu_model.py -m gpu -x -q 2>&1 | tail -15 > $O/model_tests.txt
-timeout 600 python bench.py --no-cpu-baseline 2>$O/bench_err.txt | tail -1 > $O/bench_default.json
+timeout 600 python bench.py --full --no-cpu-baseline 2>$O/bench_err.txt | tail -1 > $O/bench_default.json
 timeout 300 python scripts/exp_timeline.py 8 > $O/timeline_batch8.txt 2>/dev/null
 tail -5 $O/new_tests.txt; tail -3 $O/model_tests.txt; python - <<PY
 import json

@@ -1,6 +1,9 @@
-# rocprofv3 kernel trace + stats of the default bench command (run on the GPU box via gpurun)
+# rocprofv3 kernel trace + stats of the default bench command
+# usage (from the repository root): bash scripts/gpu_profile.sh OUTPUT_DIR
 set -x
-mkdir -p gpurun_out/prof
+O=$(realpath -m "${1:?usage: bash scripts/gpu_profile.sh OUTPUT_DIR}")
+R=$PWD
+mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-op-leg > $GRAFT_REPO_ROOT/gpurun_out/prof/bench_stdout.log 2>&1
-ls -R $GRAFT_REPO_ROOT/gpurun_out/prof | head -30
+rocprofv3 --kernel-trace --stats -d "$O" -o bench -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-op-leg > "$O/bench_stdout.log" 2>&1
+ls -R "$O" | head -30

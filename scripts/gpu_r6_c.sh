@@ -11,6 +11,6 @@ for b in 8 1; do timeout 300 python scripts/exp_ab_model.py w32_conv $b 2>&1 | g
 cat $O/exp_ab_w32.txt
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt8
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt8 -o kt -- python $R/bench.py --batch 8 --steps 4 --warmup 3 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg --no-fp32-leg > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/kt8 -o kt -- python $R/bench.py --full --batch 8 --steps 4 --warmup 3 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg --no-fp32-leg > /dev/null 2>&1
 python $R/scripts/kernel_trace_forward.py /tmp/kt8 > $O/forward_trace_b8.txt 2>&1
 cut -c1-110 $O/forward_trace_b8.txt | head -70

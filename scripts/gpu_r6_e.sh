@@ -16,5 +16,5 @@ for k,v in d["per_kernel"].items(): print("  ", k, round(v["avg_us"],2), round(v
 PY
 for b in 8 1; do timeout 300 python scripts/exp_ab_model.py three_operand $b 2>&1 | grep -v amdgpu.ids >> $O/exp_ab_three_operand.txt; done
 cat $O/exp_ab_three_operand.txt
-timeout 600 python bench.py --no-cpu-baseline 2>$O/bench_err.txt | tail -1 > $O/bench_default.json
+timeout 600 python bench.py --full --no-cpu-baseline 2>$O/bench_err.txt | tail -1 > $O/bench_default.json
 cut -c1-300 $O/bench_default.json

@@ -7,25 +7,25 @@ O=$R/gpurun_out/final3
 rm -rf $O; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/gpu_tests.txt
-timeout 600 python bench.py 2>/dev/null | tail -1 > $O/bench_default.json
-timeout 600 python bench.py --streams 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_streams1.json
-timeout 300 python bench.py --gpus 1 --spawn --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_default_spawn.json
-timeout 600 python bench.py --config configs3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_configs3.json
-timeout 600 python bench.py --config configs4 --gpus 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_configs4_per_gpu.json
-timeout 300 python bench.py --batch 32 --no-cpu-baseline --no-op-leg 2>/dev/null | tail -1 > $O/bench_b32.json
-timeout 300 python bench.py --batch 1 --steps 50 --no-cpu-baseline --no-op-leg 2>/dev/null | tail -1 > $O/bench_b1.json
+timeout 600 python bench.py --full 2>/dev/null | tail -1 > $O/bench_default.json
+timeout 600 python bench.py --full --streams 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_streams1.json
+timeout 300 python bench.py --full --gpus 1 --spawn --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_default_spawn.json
+timeout 600 python bench.py --full --config configs3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_configs3.json
+timeout 600 python bench.py --full --config configs4 --gpus 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_configs4_per_gpu.json
+timeout 300 python bench.py --full --batch 32 --no-cpu-baseline --no-op-leg 2>/dev/null | tail -1 > $O/bench_b32.json
+timeout 300 python bench.py --full --batch 1 --steps 50 --no-cpu-baseline --no-op-leg 2>/dev/null | tail -1 > $O/bench_b1.json
 timeout 300 python bench.py --mode train --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/bench_train.json
 timeout 300 python scripts/exp_timeline.py 8 > $O/timeline_batch8.txt 2>/dev/null
 timeout 200 ./scripts/exp_cv3.bin > $O/exp_cv3.txt 2>&1
 timeout 200 ./scripts/exp_wino4.bin > $O/exp_wino4.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-C="python $R/bench.py --steps 10 --warmup 3 --streams 1 --no-cpu-baseline --no-op-leg"
+C="python $R/bench.py --full --steps 10 --warmup 3 --streams 1 --no-cpu-baseline --no-op-leg"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- $C > $O/prof_stdout.log 2>&1
 python $R/scripts/kernel_stats_table.py $O/prof 44 > $O/kernel_stats.txt 2>&1
-CD="python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-op-leg"
+CD="python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-op-leg"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -o bench -- $CD > $O/prof2_stdout.log 2>&1
 python $R/scripts/kernel_stats_table.py $O/prof2 44 > $O/kernel_stats_default_streams2.txt 2>&1
-C2="python $R/bench.py --steps 3 --warmup 2 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg"
+C2="python $R/bench.py --full --steps 3 --warmup 2 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg"
 mkdir -p $O/pmc_traffic $O/pmc_mfma
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_traffic -o $c --output-format csv -- $C2 > /dev/null 2>&1

@@ -6,13 +6,13 @@ rm -rf $O; mkdir -p $O
 cd $R
 timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/gpu_tests.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
-timeout 600 python bench.py 2>/dev/null | tail -1 > $O/bench_default.json
+timeout 600 python bench.py --full 2>/dev/null | tail -1 > $O/bench_default.json
 cd /tmp && export TMPDIR=/tmp
-C="python $R/bench.py --steps 10 --warmup 3 --streams 1 --no-cpu-baseline --no-op-leg --no-fp32-leg"
+C="python $R/bench.py --full --steps 10 --warmup 3 --streams 1 --no-cpu-baseline --no-op-leg --no-fp32-leg"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- $C > $O/prof_stdout.log 2>&1
 python $R/scripts/kernel_stats_table.py $O/prof 44 > $O/kernel_stats.txt 2>&1
 rm -rf /tmp/kt8
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt8 -o kt -- python $R/bench.py --batch 8 --steps 4 --warmup 3 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg --no-fp32-leg > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/kt8 -o kt -- python $R/bench.py --full --batch 8 --steps 4 --warmup 3 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg --no-fp32-leg > /dev/null 2>&1
 python $R/scripts/kernel_trace_forward.py /tmp/kt8 > $O/forward_trace_b8.txt 2>&1
 rm -rf $O/prof
 cd $R

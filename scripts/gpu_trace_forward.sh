@@ -4,11 +4,11 @@ O=$R/gpurun_out/${1:-trace}
 mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -x -q -k "block_cost_volume or bench" 2>&1 | tail -5 > $O/new_tests.txt
-timeout 600 python bench.py --no-cpu-baseline 2>$O/bench_err.txt | tail -1 > $O/bench_default.json
+timeout 600 python bench.py --full --no-cpu-baseline 2>$O/bench_err.txt | tail -1 > $O/bench_default.json
 cd /tmp && export TMPDIR=/tmp
 for b in 8 1; do
   rm -rf /tmp/kt$b
-  timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt$b -o kt -- python $R/bench.py --batch $b --steps 4 --warmup 3 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg --no-fp32-leg > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/kt$b -o kt -- python $R/bench.py --full --batch $b --steps 4 --warmup 3 --streams 1 --no-cpu-baseline --no-op-timing --no-op-leg --no-fp32-leg > /dev/null 2>&1
   python $R/scripts/kernel_trace_forward.py /tmp/kt$b > $O/forward_trace_b$b.txt 2>&1
 done
 cd $R

@@ -197,7 +197,7 @@ def test_load_weights_strict(pa):
 
 # ------------------------------------------------------------------ bench.py launch
 def _run_bench(extra, timeout=900):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--batch", "2", "--height", "128", "--width", "192", "--cpu-seconds", "1"] + extra,
                          capture_output=True, text=True, timeout=timeout)
     return out

@@ -357,11 +357,11 @@ def test_winograd_and_direct_convs_agree_end_to_end(pa):
 
 
 def test_bench_json_contract(pa):
-    """bench.py prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline`
+    """bench.py --full prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline`
     (small configuration so that the test takes seconds)."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1",
                           "--batch", "2", "--height", "128", "--width", "192", "--cpu-seconds", "1"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -406,6 +406,37 @@ def test_bench_json_contract(pa):
     # counter traffic is printed only when its stamp matches the build and launch pattern of THIS run (the
     # committed passes are of the batch-8 448x1024 workload: this small configuration gets none and says nothing stale either)
     assert r["traffic"] is None and "traffic_stale" not in r
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_last_step(pa, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs none of the --full legs, and --dump-outputs writes what its last
+    timed step returned: float32 flows equal to a forward of the bench's own seeded inputs and weights."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from pwcnet_amd import weights as W
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--batch", "2", "--height", "128", "--width", "192", "--dump-outputs", str(tmp_path / "d")],
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["unit"] == "pairs/s" and d["higher_is_better"] is True and "fp16x2" in d["dtype"]
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    assert abs(d["timed_region_ms"] - 4 * d["ms_per_step"]) <= 1e-6 * d["timed_region_ms"]
+    for k in ("value_one_stream", "value_fp32_only", "roofline", "roofline_hbm", "kernels", "cpu_baseline", "parity"):
+        assert k not in d, k
+    net = pa.PWCDCNet()
+    net.load_weights(W.init_weights(W.conv_specs(use_dc=False), seed=0))
+    final, pyr = net(*bench.synthetic_pairs(2, 128, 192, torch.device("cuda", 0), 0))
+    expect = {"flows_final": final, **{f"flows_pyramid_{l}": p for l, p in enumerate(pyr)}}
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(f"{k}.npy" for k in expect)
+    for k, t in expect.items():
+        got = np.load(tmp_path / "d" / f"{k}.npy")
+        assert got.dtype == np.float32 and got.shape == tuple(t.shape), k
+        assert float(np.abs(got - t.cpu().numpy()).max()) <= 1e-5, k
 
 
 @pytest.mark.parametrize("gain,use_dc", [(1.35, False), (1.6, False), (1.25, True)])

@@ -446,6 +446,28 @@ def test_bench_config_presets_imply_their_gpu_count():
     assert bench.parse(["--config", "configs3"]).gpus == 1 and bench.parse(["--config", "configs3"]).use_dc
 
 
+def test_bench_dump_outputs_caps_its_bytes_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs: float32 .npy files, whole arrays under the budget; over it, every array becomes the same seeded
+    sample of its share on every call.  A plain run is the headline only (--full off by default)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None and bench.parse(["--full", "--dump-outputs", "x"]).full
+    big = np.arange(1000, dtype=np.float64).reshape(10, 100)
+    small = np.ones((3, 4), np.float32)
+    w = bench.dump_outputs(str(tmp_path / "whole"), {"big": big, "small": small})
+    assert w == {"big.npy": (10, 100), "small.npy": (3, 4)}
+    got = np.load(tmp_path / "whole" / "big.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, big)
+    budget = 1000                                   # bytes: 4000 + 48 in, 247 + 2 floats out
+    w = bench.dump_outputs(str(tmp_path / "s1"), {"big": big, "small": small}, budget=budget, prefix="rank1_")
+    bench.dump_outputs(str(tmp_path / "s2"), {"big": big, "small": small}, budget=budget, prefix="rank1_")
+    s1 = np.load(tmp_path / "s1" / "rank1_big.npy")
+    assert sum(4 * n for (n,) in w.values()) <= budget and len(s1) > 200
+    assert np.array_equal(s1, np.load(tmp_path / "s2" / "rank1_big.npy"))
+    assert np.all(np.diff(s1) > 0) and set(s1) <= set(big.ravel())         # sorted distinct elements of the array
+
+
 _EVAL_WORKER = r"""
 import os, sys
 sys.path.insert(0, sys.argv[1])
