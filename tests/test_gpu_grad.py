@@ -2,7 +2,7 @@
 against torch.autograd on the float64 CPU restatement of the forward (oracle/torch_ref.py).
 
 Tolerances are relative to the largest reference gradient (fp32 kernels vs a float64 reference)."""
-import os
+import time
 
 import numpy as np
 import pytest
@@ -323,6 +323,33 @@ def test_adam_step(go):
 
 
 # ------------------------------------------------------------------ assembled training step
+LOSS_WEIGHTS = (0.32, 0.08, 0.02, 0.01, 0.005)
+
+# (N, H, W) -> (kernel gain, image seed, gt seed, image shift) of the step tests' inputs
+_STEP_INPUTS = {
+    (2, 64, 128): (1.25, 61, 62, (3, -2)),
+    (4, 384, 448): (1.2, 91, 92, (4, -3)),
+    (1, 448, 1024): (1.2, 81, 82, (4, -3)),
+}
+
+# Bounds of the step tests: (gradient, pyramid, loss), each relative to the reference's largest magnitude -- the gradient
+# bound per variable.  Every bound is max(10 x the worst error measured on an MI355X, 1e-5), rounded up to two digits and
+# capped at 1e-4 (64x128) / 6.5e-4 (448x1024); the comments give the measured worst gradient error and its variable.
+# Key: (use_dc, loss, (N, H, W), f16x2).
+STEP_BOUNDS = {
+    (False, "multiscale", (2, 64, 128), True): (1e-5, 1e-5, 1e-5),       # 7.5e-7 fp_extractor/conv2d_9/kernel
+    (True, "multiscale", (2, 64, 128), True): (1e-5, 1.6e-5, 1e-5),      # 8.9e-7 fp_extractor/conv2d_3/kernel
+    (False, "robust", (2, 64, 128), True): (1.8e-5, 1e-5, 1e-5),         # 1.75e-6 fp_extractor/conv2d/bias
+    (True, "robust", (2, 64, 128), True): (1e-5, 1.6e-5, 1e-5),          # 8.8e-7 fp_extractor/conv2d_3/kernel
+    (False, "multiscale", (2, 64, 128), False): (1e-5, 1e-5, 1e-5),      # 7.5e-7 fp_extractor/conv2d_9/kernel
+    (False, "multiscale", (4, 384, 448), True): (3.7e-4, 1.4e-5, 1e-5),  # 3.7e-5 fp_extractor/conv2d/bias (sign-following)
+    (False, "multiscale", (4, 384, 448), False): (1.2e-4, 1.5e-5, 1e-5),  # 1.2e-5 context/conv2d/bias (sign-following)
+    (False, "multiscale", (1, 448, 1024), True): (6.5e-4, 1.7e-5, 1e-5),  # 7.3e-5 fp_extractor/conv2d/kernel (cap)
+}
+# the first Adam step's gradients (64x64, batch 2, constant gt): same rule (7.5e-7 fp_extractor/conv2d/kernel)
+ADAM_STEP_GRAD_BOUND = 1e-5
+
+
 def _ref_grads(w, im0, im1, gt, weights, use_dc=False, loss="multiscale"):
     wt = {k: t64(v) for k, v in w.items()}
     _, pyr = tr.TorchPWCDCNet(wt, use_dc=use_dc)(t64(im0, False), t64(im1, False))
@@ -334,81 +361,249 @@ def _ref_grads(w, im0, im1, gt, weights, use_dc=False, loss="multiscale"):
     return float(loss.detach()), {k: v.grad for k, v in wt.items()}, [p.detach() for p in pyr]
 
 
+@pytest.fixture(scope="module")
+def step_ref():
+    """The float64 autograd reference of one training step, computed once per module and shared by the tests below:
+    step_ref(use_dc, loss, (N, H, W)) -> dict of the inputs, the loss, the pyramid, every variable's gradient and the
+    CPU seconds the reference took."""
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU (torch.cuda.is_available() is False)")
+    cache = {}
+
+    def get(use_dc, loss, shape):
+        key = (use_dc, loss, shape)
+        if key not in cache:
+            gain, s_im, s_gt, shift = _STEP_INPUTS[shape]
+            N, H, W = shape
+            w = util.model_weights(use_dc, gain=gain)
+            im0, im1 = util.smooth_images(N, H, W, seed=s_im, shift=shift)
+            gt = util.flow_field(N, H, W, seed=s_gt, sigma=2.0, outliers=False).astype(np.float32)
+            t0 = time.perf_counter()
+            ref_loss, ref_g, ref_pyr = _ref_grads(w, im0, im1, gt, LOSS_WEIGHTS, use_dc, loss)
+            cache[key] = dict(w=w, im0=im0, im1=im1, gt=gt, loss=ref_loss, grads=ref_g, pyr=ref_pyr,
+                              cpu_s=time.perf_counter() - t0, threads=torch.get_num_threads())
+        return cache[key]
+    return get
+
+
+def _rel_err(got, ref):
+    got = got.detach().cpu().double().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
+    ref = ref.detach().cpu().double().numpy() if isinstance(ref, torch.Tensor) else np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float(np.abs(got - ref).max()) / max(float(np.abs(ref).max()), 1e-12)
+
+
+def _run_step(ref, use_dc=False, loss="multiscale", f16x2=True):
+    """One Trainer forward + backward on ref's inputs: (trainer, worst pyramid level error, loss error, gradients), the
+    errors relative to the reference's largest magnitude."""
+    from pwcnet_amd.train import Trainer
+    tn = Trainer(weights=LOSS_WEIGHTS, gamma=0.0, lr=1e-4, use_dc=use_dc, loss=loss, epsilon=0.02, q=0.4, f16x2=f16x2)
+    tn.load_weights(ref["w"])
+    pyr = tn.forward(gpu(ref["im0"]), gpu(ref["im1"]))
+    pyr_err = max(_rel_err(a, b) for a, b in zip(pyr, ref["pyr"]))
+    ggt = gpu(ref["gt"])
+    loss_err = abs(float(tn.loss_value(ggt)) - ref["loss"]) / abs(ref["loss"])
+    tn.backward(ggt)
+    torch.cuda.synchronize()
+    return tn, pyr_err, loss_err, tn.gradients()
+
+
+def _step_errors(ref, use_dc=False, loss="multiscale", f16x2=True):
+    """(worst pyramid level error, loss error, {variable: relative gradient error}) of one Trainer step."""
+    _, pyr_err, loss_err, got = _run_step(ref, use_dc, loss, f16x2)
+    return pyr_err, loss_err, {k: _rel_err(got[k], r) for k, r in ref["grads"].items()}
+
+
+class _SignFollowingNet(tr.TorchPWCDCNet):
+    """The float64 restatement, except that every extractor leaky-relu takes the branch the given fp32 activations took
+    (signs[k]: (2N, h, w, c) booleans of extractor conv k, both frames stacked as the Trainer stacks them).  Counts the
+    elements where that differs from the float64 pre-activation's own sign in self.flips[k]."""
+
+    def __init__(self, weights, signs, N):
+        super().__init__(weights)
+        self.signs, self.N, self.frame, self.flips = signs, N, 0, {}
+
+    def extractor(self, images):
+        sl = slice(self.frame * self.N, (self.frame + 1) * self.N)
+        self.frame += 1
+        pyr, x, k = [], images, 0
+        for l in range(self.num_levels):
+            for j in range(3):
+                n = f"{self.name}/fp_extractor/conv2d" + ("" if k == 0 else f"_{k}")
+                y = tr.conv3x3_same(x, self.w[n + "/kernel"], self.w[n + "/bias"], 2 if j == 0 else 1)
+                pos = self.signs[k][sl]
+                self.flips[k] = self.flips.get(k, 0) + int((pos != (y.detach() > 0)).sum())
+                x = torch.where(pos, y, 0.1 * y)
+                k += 1
+            pyr.append(x)
+        return pyr[::-1]
+
+
+def _sign_following_grads(ref, tn):
+    """Float64 autograd of the multiscale step with the extractor's leaky-relu branches of tn's forward: {k: gradient},
+    {extractor conv: elements whose branch differs from float64's}."""
+    N = ref["im0"].shape[0]
+    signs = [torch.from_numpy(c.y_t.cpu().numpy() > 0) for c in tn.ext]
+    wt = {k: t64(v) for k, v in ref["w"].items()}
+    net = _SignFollowingNet(wt, signs, N)
+    _, pyr = net(t64(ref["im0"], False), t64(ref["im1"], False))
+    tr.multiscale_loss(t64(ref["gt"], False), pyr, LOSS_WEIGHTS).backward()
+    return {k: v.grad for k, v in wt.items()}, {k: n for k, n in net.flips.items() if n}
+
+
+def _report(tag, pyr_err, loss_err, errs):
+    ranked = sorted(errs.items(), key=lambda kv: -kv[1])
+    print(f"\n[{tag}] pyramid {pyr_err:.2e}, loss {loss_err:.2e}; gradients of {len(ranked)} variables: "
+          f"worst {ranked[0][1]:.2e} ({ranked[0][0]}), median {float(np.median(list(errs.values()))):.2e}")
+    for k, e in ranked[:4]:
+        print(f"    {e:.2e}  {k}")
+
+
+def _check_step(key, pyr_err, loss_err, errs):
+    g_bound, p_bound, l_bound = STEP_BOUNDS[key]
+    _report(key, pyr_err, loss_err, errs)
+    assert pyr_err <= p_bound, f"pyramid: relative error {pyr_err:.3e} > {p_bound:.1e}"
+    assert loss_err <= l_bound, f"loss: relative error {loss_err:.3e} > {l_bound:.1e}"
+    bad = {k: f"{e:.3e}" for k, e in errs.items() if e > g_bound}
+    assert not bad, f"relative gradient error above {g_bound:.1e}: {bad}"
+
+
 @pytest.mark.parametrize("use_dc,loss", [(False, "multiscale"), (True, "multiscale"), (False, "robust"), (True, "robust")])
-def test_train_step_gradients_vs_autograd(use_dc, loss):
+def test_train_step_gradients_vs_autograd(step_ref, use_dc, loss):
     """Whole backward (loss gradient, context, 5 estimators -- plain and densely connected --, cost volumes, warps,
-    resizes, shared-weight extractor) against torch.autograd on the float64 restatement: every variable's gradient."""
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    from pwcnet_amd.train import Trainer
-    N, H, W = 2, 64, 128
-    w = util.model_weights(use_dc, gain=1.25)
-    im0, im1 = util.smooth_images(N, H, W, seed=61, shift=(3, -2))
-    gt = (util.flow_field(N, H, W, seed=62, sigma=2.0, outliers=False)).astype(np.float32)
-    weights = (0.32, 0.08, 0.02, 0.01, 0.005)
-    ref_loss, ref_g, ref_pyr = _ref_grads(w, im0, im1, gt, weights, use_dc, loss)
-    tn = Trainer(weights=weights, gamma=0.0, lr=1e-4, use_dc=use_dc, loss=loss, epsilon=0.02, q=0.4)
-    tn.load_weights(w)
-    pyr = tn.forward(gpu(im0), gpu(im1))
-    for a, b in zip(pyr, ref_pyr):
-        close(a, b, rel=2e-4)
-    ggt = gpu(gt)
-    loss = float(tn.loss_value(ggt))
-    assert abs(loss - ref_loss) <= 1e-4 * abs(ref_loss)
-    tn.backward(ggt)
-    torch.cuda.synchronize()
-    got = tn.gradients()
-    worst = 0.0
-    for k in sorted(ref_g):
-        r = ref_g[k].numpy()
-        err = float(np.abs(got[k] - r).max()) / max(float(np.abs(r).max()), 1e-12)
-        worst = max(worst, err)
-        assert err <= 2e-3, f"{k}: relative gradient error {err:.3e}"
-    print(f"worst relative gradient error over {len(ref_g)} variables: {worst:.3e}")
+    resizes, shared-weight extractor) against torch.autograd on the float64 restatement: every variable's gradient, at
+    the bounds of STEP_BOUNDS."""
+    shape = (2, 64, 128)
+    _check_step((use_dc, loss, shape, True), *_step_errors(step_ref(use_dc, loss, shape), use_dc, loss))
 
 
-def test_train_step_gradients_full_size_spot_check():
+def test_train_step_gradients_with_the_fp32_forward(step_ref):
+    """Trainer(f16x2=False): the training forward on the fp32 convolution kernels instead of the F16-pipe ones (non-DC,
+    multiscale, 64x128; the F16-pipe kernels take no layer at this size, so both forwards measure alike here -- the
+    384x448 test runs both as well)."""
+    shape = (2, 64, 128)
+    _check_step((False, "multiscale", shape, False), *_step_errors(step_ref(False, "multiscale", shape), f16x2=False))
+
+
+@pytest.mark.parametrize("f16x2", [True, False])
+def test_train_step_gradients_at_the_cli_crop(step_ref, f16x2):
+    """train.py's own geometry: 384x448 crops at its default batch of 4.  The estimator levels are 6x7, 12x14, 24x28,
+    48x56 and 96x112: widths 7, 14 and 28 leave ragged 8x8 tiles along W in the cost-volume gradient and ragged
+    weight-gradient tiles, which neither 64x128 (powers of two) nor 448x1024 (ragged heights only) reach.  Every variable
+    of a non-DC multiscale step against float64 autograd; the float64 reference takes about 4 s on 16 CPU threads (8 s
+    on 8), so batch 4 it is.
+
+    Against the plain reference the worst error is 3.8e-4 (fp_extractor/conv2d_7/kernel, then conv2d/kernel 3.5e-4): ONE
+    leaky-relu branch differs -- an element of fp_extractor/conv2d_7's output (extractor level 2, 48x56, first frame)
+    whose float64 pre-activation is 8.7e-9 against a layer maximum of 0.18, below what fp32 resolves, comes out on the
+    other side of zero in the fp32 forward, and its gradient is 10x off.  That is the forward's rounding, not the
+    backward's: the bound applies to float64 autograd of the same branches (the extractor's leaky-relus take the fp32
+    forward's signs; worst 3.7e-5, fp_extractor/conv2d/bias, with the F16-pipe forward; 1.2e-5, context/conv2d/bias,
+    with the fp32 one), and the plain reference's error is reported."""
+    shape = (4, 384, 448)
+    ref = step_ref(False, "multiscale", shape)
+    print(f"\n384x448 batch 4: float64 reference {ref['cpu_s']:.1f} s on {ref['threads']} CPU threads")
+    tn, pyr_err, loss_err, got = _run_step(ref, f16x2=f16x2)
+    plain = {k: _rel_err(got[k], r) for k, r in ref["grads"].items()}
+    _report("384x448 plain reference (not asserted)", pyr_err, loss_err, plain)
+    grads, flips = _sign_following_grads(ref, tn)
+    print(f"extractor leaky-relu branches that differ from float64 (conv index: elements): {flips}")
+    assert sum(flips.values()) <= 16, flips                   # (a wrong forward would differ in many)
+    _check_step((False, "multiscale", shape, f16x2), pyr_err, loss_err, {k: _rel_err(got[k], r) for k, r in grads.items()})
+
+
+def test_train_step_gradients_full_size_spot_check(step_ref):
     """One 448x1024 pair (the geometry `bench.py --mode train` times: LDS-staged weight-gradient tiling with its k-split
-    over pixel chunks, Winograd data gradients, full-size cost-volume / warp gradients): the gradients of the first
-    conv, a level-4 128 -> 128 conv, the dilated context convs, a stride-2 extractor conv -- in fact every variable --
-    against float64 autograd on the torch restatement (about a minute of CPU)."""
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    from pwcnet_amd.train import Trainer
-    N, H, W = 1, 448, 1024
-    w = util.model_weights(False, gain=1.2)
-    im0, im1 = util.smooth_images(N, H, W, seed=81, shift=(4, -3))
-    gt = util.flow_field(N, H, W, seed=82, sigma=2.0, outliers=False).astype(np.float32)
-    weights = (0.32, 0.08, 0.02, 0.01, 0.005)
-    torch.set_num_threads(max(1, (os.cpu_count() or 2) // 2))
-    ref_loss, ref_g, ref_pyr = _ref_grads(w, im0, im1, gt, weights, False, "multiscale")
-    tn = Trainer(weights=weights, gamma=0.0, lr=1e-4)
-    tn.load_weights(w)
-    pyr = tn.forward(gpu(im0), gpu(im1))
-    for a, b in zip(pyr, ref_pyr):
-        close(a, b, rel=2e-4)
-    ggt = gpu(gt)
-    loss = float(tn.loss_value(ggt))
-    assert abs(loss - ref_loss) <= 1e-4 * abs(ref_loss)
-    tn.backward(ggt)
-    torch.cuda.synchronize()
-    got = tn.gradients()
-    named = ["pwcdcnet/fp_extractor/conv2d/kernel", "pwcdcnet/optflow_4/conv2d_1/kernel", "pwcdcnet/context/conv2d_2/kernel",
-             "pwcdcnet/context/conv2d_4/kernel", "pwcdcnet/fp_extractor/conv2d_3/kernel", "pwcdcnet/optflow_4/conv2d_5/kernel"]
-    worst = 0.0
-    for k in sorted(ref_g):
-        r = ref_g[k].numpy()
-        err = float(np.abs(got[k] - r).max()) / max(float(np.abs(r).max()), 1e-12)
-        worst = max(worst, err)
-        if k in named:
-            print(f"  {k}: relative gradient error {err:.3e}")
-        assert err <= 2e-3, f"{k}: relative gradient error {err:.3e}"
-    print(f"full size: worst relative gradient error over {len(ref_g)} variables: {worst:.3e}")
+    over pixel chunks, Winograd data gradients, full-size cost-volume / warp gradients): every variable against float64
+    autograd on the torch restatement.  The worst, 7.3e-5 on fp_extractor/conv2d/kernel (no leaky-relu branch differs
+    in the extractor), is fp32 summation over the 229 376 output pixels of the first conv, whose kernel gradient is a
+    small difference of large sums; 10x that is above the 6.5e-4 cap, so the cap is the bound."""
+    shape = (1, 448, 1024)
+    ref = step_ref(False, "multiscale", shape)
+    print(f"\n448x1024 batch 1: float64 reference {ref['cpu_s']:.1f} s on {ref['threads']} CPU threads")
+    _check_step((False, "multiscale", shape, True), *_step_errors(ref))
+
+
+def _mutate(case):
+    """(name of the grad_ops function, replacement) that perturbs one term of the backward at one level (64x128 step:
+    levels 0..4 are 1x2, 2x4, 4x8, 8x16, 16x32)."""
+    from pwcnet_amd import grad_ops as G
+    from pwcnet_amd.weights import SCALES
+    keep = []
+    if case == "warp_dflow":
+        # (a) the warp's flow gradient at level 4 (flow_scale 5), x 0.9.  At x 0.99 no level moves any variable by more
+        # than 3e-6 (dropping that term altogether moves level 2 by 5e-5, levels 3 / 4 by 3e-4): enlarged to 10 %.
+        orig = G.warp_grad
+
+        def f(x, flow, flow_scale, dy, dx=None, dflow=None, dflow_accumulate=False, deterministic=True):
+            if flow_scale != SCALES[4] or dflow is None:
+                return orig(x, flow, flow_scale, dy, dx, dflow, dflow_accumulate, deterministic)
+            orig(x, flow, flow_scale, dy, dx, None, deterministic=deterministic)
+            t = torch.zeros((flow.N, flow.H, flow.W, 2), device="cuda")
+            keep.append(t)
+            orig(x, flow, flow_scale, dy, None, V(t))
+            G.add_(V(t), dflow, alpha=0.9, accumulate=dflow_accumulate)
+        return "warp_grad", f
+    if case == "cv_grad":
+        # (b) the cost volume's feature gradients at level 3 x 0.99.  (Replaces slope 0.11 in the cost volume's leaky-relu
+        # mask, which no step here can see: every in-image cost-volume entry of these inputs is positive at every level
+        # -- the entries <= 0 are exactly the zero padding -- so the slope multiplies nothing.  test_gpu_grad_ops.py's
+        # sweeps, with features of both signs, pin the slope.)
+        orig = G.cost_volume_grad
+
+        def f(f0, f1w, cv, dcv, df0=None, df1w=None, accumulate=False, search_range=4, slope=0.1):
+            if f0.H != 8:
+                return orig(f0, f1w, cv, dcv, df0, df1w, accumulate, search_range, slope)
+            for d, which in ((df0, 0), (df1w, 1)):
+                if d is not None:
+                    t = torch.zeros((d.N, d.H, d.W, d.C), device="cuda")
+                    keep.append(t)
+                    orig(f0, f1w, cv, dcv, V(t) if which == 0 else None, V(t) if which == 1 else None, False, search_range, slope)
+                    G.add_(V(t), d, alpha=0.99, accumulate=accumulate)
+        return "cost_volume_grad", f
+    if case == "feat_up_mul":                # (c) level 3's feat_up resize gradient x 0.99
+        orig = G.resize_grad
+
+        def f(dy, dx, mul=1.0, accumulate=False):
+            return orig(dy, dx, 0.99 * mul if (dy.H == 8 and dy.C > 2) else mul, accumulate)
+        return "resize_grad", f
+    if case == "flow_norm_scale":            # (d) the loss gradient of level 4 (weight 0.005) x 1.01
+        orig = G.flow_norm_grad
+
+        def f(pred, gt, dpred, gt_div=1.0, ord=2, scale=1.0, accumulate=False):
+            return orig(pred, gt, dpred, gt_div, ord, 1.01 * scale if pred.H == 16 else scale, accumulate)
+        return "flow_norm_grad", f
+    if case == "lrelu_slope":                # (e) leaky-relu slope 0.105 in the backward of optflow_3/conv2d_2 (8x16, 96 out)
+        orig = G.lrelu_grad_channel_sums_
+
+        def f(y, dy, out, device, slope=0.1, accumulate=False):
+            hit = y.N == 2 and y.H == 8 and y.C == 96
+            return orig(y, dy, out, device, 0.105 if hit else slope, accumulate)
+        return "lrelu_grad_channel_sums_", f
+    raise ValueError(case)
+
+
+@pytest.mark.parametrize("case", ["warp_dflow", "cv_grad", "feat_up_mul", "flow_norm_scale", "lrelu_slope"])
+def test_train_step_check_sees_a_one_percent_error(step_ref, monkeypatch, case):
+    """The bounds of test_train_step_gradients_vs_autograd are tight enough to see a subtle backward bug: each case
+    perturbs one term of one level by about 1 % (10 % for the warp's flow gradient, see _mutate; the Trainer calls the
+    grad_ops functions as G.<name> at run time), and the same check must then fail for at least one variable."""
+    from pwcnet_amd import grad_ops as G
+    key = (False, "multiscale", (2, 64, 128), True)
+    ref = step_ref(*key[:3])
+    name, fn = _mutate(case)
+    monkeypatch.setattr(G, name, fn)
+    pyr_err, loss_err, errs = _step_errors(ref)
+    _report(f"mutation {case}", pyr_err, loss_err, errs)
+    worst = max(errs.values())
+    assert worst > STEP_BOUNDS[key][0], f"{case}: worst relative gradient error {worst:.3e} is inside the bound"
 
 
 def test_train_step_reduces_the_loss_and_matches_adam():
-    """A few optimisation steps on one batch: the loss goes down; the first update equals tf.train.AdamOptimizer's
-    formula applied to the reference gradients plus gamma * var."""
+    """A few optimisation steps on one batch: the loss goes down; after the first step every variable equals
+    tf.train.AdamOptimizer's formula applied to that step's gradient plus gamma * var, that gradient matches float64
+    autograd, the padding floats of the flat buffer stay zero, and three variables also match Adam on the reference
+    gradients directly."""
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU")
     from pwcnet_amd.train import Trainer
@@ -417,14 +612,28 @@ def test_train_step_reduces_the_loss_and_matches_adam():
     im0, im1 = util.smooth_images(N, H, W, seed=63, shift=(2, 1))
     gt = np.zeros((N, H, W, 2), np.float32)
     gt[..., 0], gt[..., 1] = 2.0, 1.0                       # the true motion of smooth_images(shift=(2, 1))
-    weights = (0.32, 0.08, 0.02, 0.01, 0.005)
     gamma, lr = 4e-4, 1e-3
-    _, ref_g, _ = _ref_grads(w, im0, im1, gt, weights)
-    tn = Trainer(weights=weights, gamma=gamma, lr=lr)
+    _, ref_g, _ = _ref_grads(w, im0, im1, gt, LOSS_WEIGHTS)
+    tn = Trainer(weights=LOSS_WEIGHTS, gamma=gamma, lr=lr)
     tn.load_weights(w)
     g0, g1, ggt = gpu(im0), gpu(im1), gpu(gt)
     losses = [float(tn.step(g0, g1, ggt))]
     after = tn.state_dict()
+    got_g = tn.gradients()                                  # the step's gradients (the optimiser does not clear them)
+    errs = {k: _rel_err(got_g[k], ref_g[k]) for k in ref_g}
+    _report("64x64 first step", 0.0, 0.0, errs)
+    bad = {k: f"{e:.3e}" for k, e in errs.items() if e > ADAM_STEP_GRAD_BOUND}
+    assert not bad, f"relative gradient error above {ADAM_STEP_GRAD_BOUND:.1e}: {bad}"
+    assert sorted(after) == sorted(ref_g)
+    for k in sorted(ref_g):
+        p = t64(w[k], False)
+        g = t64(got_g[k], False) + gamma * p
+        exp, _, _ = tr.adam_step(p, g, torch.zeros_like(g), torch.zeros_like(g), 1, lr)
+        close(after[k], exp, rel=1e-5)
+    used = torch.zeros(tn.params.numel(), dtype=torch.bool)
+    for off, shape in tn.views.values():
+        used[off:off + int(np.prod(shape))] = True
+    assert int(torch.count_nonzero(tn.params.cpu()[~used])) == 0, "padding floats of the flat buffer moved"
     for k in ("pwcdcnet/context/conv2d_6/kernel", "pwcdcnet/optflow_2/conv2d/kernel", "pwcdcnet/fp_extractor/conv2d_4/bias"):
         g = ref_g[k] + gamma * t64(w[k], False)
         exp, _, _ = tr.adam_step(t64(w[k], False), g, torch.zeros_like(g), torch.zeros_like(g), 1, lr)

@@ -676,7 +676,6 @@ def float64_forward(w, use_dc, im0, im1):
     """flows_final of the float64 restatement (oracle/torch_ref.py, pinned against the C oracle in tests/test_oracle.py): the
     yardstick for what an fp32 forward of this depth can hold at a given flow magnitude."""
     from oracle import torch_ref as TR
-    torch.set_num_threads(max(1, (os.cpu_count() or 2) // 2))
     w64 = {k: torch.from_numpy(v).to(torch.float64) for k, v in w.items()}
     with torch.no_grad():
         out = TR.TorchPWCDCNet(w64, use_dc=use_dc)(torch.from_numpy(im0).double(), torch.from_numpy(im1).double())
