@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .modules import View, _p, _wino_pays, _h2_workspace, as_view
+from .modules import View, _conv_launch, _p, _packed, _wino_pays, as_view
 
 F16X2 = True      # training FORWARD: route the layers pwc_conv3x3_h2_supported names to conv3x3_h2 (activations of order 1)
 # ... and the DATA GRADIENT (dy as the split operand): off by default.  The two-term fp16 split is exact to 22 bits
@@ -180,61 +180,33 @@ def conv3x3_raw(x, w_hwio, bias, y, stride=1, dilation=1, slope=None, keep=None,
     the PHYSICAL channel order of x.  Packed weights are temporaries (appended to `keep`).  f16x2: may the F16-pipe kernels
     take it (None: the module's F16X2)."""
     L = _L()
-    s = _s()
     dev = w_hwio.device
     cout = y.C
     if bias is None:
         bias = torch.zeros((cout,), dtype=torch.float32, device=dev)
-    act, sl = (0, 0.0) if slope is None else (1, float(slope))
     Ho, Wo = -(-x.H // stride), -(-x.W // stride)
     assert (y.H, y.W) == (Ho, Wo) and tuple(w_hwio.shape) == (3, 3, x.C, cout), (tuple(w_hwio.shape), x, y)
     w_hwio = w_hwio.contiguous()
     tmp = [w_hwio, bias]
     use_mfma = cout % 16 == 0 and x.C % 16 == 0 and x.cs % 4 == 0 and x.ptr % 16 == 0
     h2_ok = use_mfma and (F16X2 if f16x2 is None else f16x2) and cout % 32 == 0 and y.cs % 4 == 0 and y.ptr % 16 == 0
+    # the big stride-1 layers, forward and data gradient alike, go to the F16 matrix pipe with exact-to-22-bit operand
+    # splits (more accurate than the fp32 Winograd kernel; include/pwc_hip.h); Winograd without the channel split
     if h2_ok and stride == 2 and dilation == 1 and L.pwc_conv3x3_h2_stride2_supported(x.N, x.H, x.W, x.C, cout):
-        packed = torch.empty((L.pwc_conv3x3_h2_stride2_packed_floats(x.C, cout),), dtype=torch.float32, device=dev)
-        _lib.check(L.pwc_conv3x3_h2_stride2_pack_f32(_p(w_hwio.data_ptr()), None, x.C, x.C, cout, _p(packed.data_ptr()), s), "h2 stride-2 pack")
-        wsf = L.pwc_conv3x3_h2_stride2_workspace_floats(x.N, x.H, x.W, x.C, cout)
-        ws = _h2_workspace(dev, wsf) if wsf else None
-        _lib.check(L.pwc_conv3x3_h2_stride2_f32(_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.data_ptr()), _p(y.ptr), y.cs,
-                                                x.N, x.H, x.W, x.C, cout, act, sl,
-                                                _p(ws.data_ptr()) if ws is not None else None, ws.numel() if ws is not None else 0,
-                                                _p(status_words(dev).data_ptr()), s),
-                   "conv3x3_h2 stride 2 (raw)")
-        tmp.append(packed)
-    elif (h2_ok and stride == 1
-            and L.pwc_conv3x3_h2_supported(x.N, x.H, x.W, x.C, cout, dilation)):
-        # the big stride-1 layers, forward and data gradient alike: direct convolution on the F16 matrix pipe with
-        # exact-to-22-bit operand splits (more accurate than the fp32 Winograd kernel below; include/pwc_hip.h)
-        packed = torch.empty((L.pwc_conv3x3_h2_packed_floats(x.C, cout),), dtype=torch.float32, device=dev)
-        _lib.check(L.pwc_conv3x3_h2_pack_f32(_p(w_hwio.data_ptr()), None, x.C, x.C, cout, _p(packed.data_ptr()), s), "h2 pack")
-        wsf = L.pwc_conv3x3_h2_workspace_floats(x.N, x.H, x.W, x.C, cout, dilation)
-        ws = _h2_workspace(dev, wsf) if wsf else None
-        _lib.check(L.pwc_conv3x3_h2_ex_f32(_p(x.ptr), x.cs, 0, None, 0, _p(packed.data_ptr()), _p(bias.data_ptr()), _p(y.ptr), y.cs,
-                                           x.N, x.H, x.W, x.C, cout, dilation, act, sl,
-                                           _p(ws.data_ptr()) if ws is not None else None, ws.numel() if ws is not None else 0,
-                                           _p(status_words(dev).data_ptr()), s),
-                   "conv3x3_h2 (raw)")
-        tmp.append(packed)
+        fam = "h2s2"
+    elif h2_ok and stride == 1 and L.pwc_conv3x3_h2_supported(x.N, x.H, x.W, x.C, cout, dilation):
+        fam = "h2"
     elif use_mfma and stride == 1 and _wino_pays(L, x.N, x.H, x.W, cout, dilation):
-        packed = torch.empty((L.pwc_conv3x3_wino_packed_floats(x.C, cout),), dtype=torch.float32, device=dev)
-        _lib.check(L.pwc_conv3x3_wino_pack_f32(_p(w_hwio.data_ptr()), None, x.C, x.C, cout, _p(packed.data_ptr()), s), "wino pack")
-        _lib.check(L.pwc_conv3x3_wino_f32(_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.data_ptr()), _p(y.ptr), y.cs,
-                                          x.N, x.H, x.W, x.C, cout, dilation, act, sl, s), "conv3x3_wino (raw)")
-        tmp.append(packed)
-    elif use_mfma:
-        packed = torch.empty((L.pwc_conv3x3_packed_floats(x.C, cout),), dtype=torch.float32, device=dev)
-        _lib.check(L.pwc_conv3x3_pack_f32(_p(w_hwio.data_ptr()), None, x.C, x.C, cout, _p(packed.data_ptr()), s), "conv pack")
-        ws = _ws(dev, L.pwc_conv3x3_workspace_floats(x.N * Ho * Wo, cout))
-        _lib.check(L.pwc_conv3x3_f32(_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.data_ptr()), _p(y.ptr), y.cs,
-                                     x.N, x.H, x.W, x.C, cout, stride, dilation, act, sl, -1, 0, _p(ws.data_ptr()),
-                                     ws.numel(), s), "conv3x3 (raw)")
-        tmp.append(packed)
+        fam = "wino"
     else:
-        _lib.check(L.pwc_conv3x3_direct_f32(_p(x.ptr), x.cs, _p(w_hwio.data_ptr()), _p(bias.data_ptr()), _p(y.ptr), y.cs,
-                                            None, 0, x.N, x.H, x.W, x.C, cout, stride, dilation, act, sl, s),
-                   "conv3x3_direct (raw)")
+        fam = "mfma" if use_mfma else "direct"
+    w = w_hwio
+    if fam != "direct":
+        w = _packed(fam, [w_hwio], (x.C, x.C, cout))
+        tmp.append(w)
+    # stream-K always on; the training path's own status words and scratch
+    _conv_launch(fam, "(raw)", x, y, w, bias, x.C, stride, dilation, slope,
+                 status=status_words(dev) if fam in ("h2", "h2s2") else None, channel_split=False, scratch=_ws)
     if keep is not None:
         keep.extend(tmp)
     return tmp

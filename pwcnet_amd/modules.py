@@ -222,7 +222,7 @@ class _ConvRunner:
         a shape pwc_conv3x3_c16pair_supported names: ONE launch with the intermediate in LDS; otherwise two conv() calls.
         Returns (View y, tensor)."""
         L = _lib.lib()
-        fused = (x.C == 16 and cout == 16 and slope is not None and getattr(self.owner, "f16x2", True)
+        fused = (x.C == 16 and cout == 16 and slope is not None and self.owner.f16x2
                  and x.cs % 4 == 0 and x.ptr % 16 == 0 and L.pwc_conv3x3_c16pair_supported(x.N, x.H, x.W))
         if not fused:
             x, _ = self.conv(x, cout, slope=slope)
@@ -235,24 +235,16 @@ class _ConvRunner:
         b1 = self.store.get(names[0] + "/bias", (16,), "bias")
         k2 = self.store.get(names[1] + "/kernel", (3, 3, 16, 16), "kernel")
         b2 = self.store.get(names[1] + "/bias", (16,), "bias")
-        dev = k1.value.device
-        s = _lib.current_stream()
-        y_t = torch.empty((x.N, x.H, x.W, 16), dtype=torch.float32, device=dev)
+        y_t = torch.empty((x.N, x.H, x.W, 16), dtype=torch.float32, device=k1.value.device)
         y = View(y_t.data_ptr(), 16, x.N, x.H, x.W, 16)
-        cache = self.owner._cache
-        key = (names[0], "c16pair", self.store.version)
-        packed = cache.get(key)
-        if packed is None:
-            packed = torch.empty((L.pwc_conv3x3_c16pair_packed_floats(),), dtype=torch.float32, device=dev)
-            _lib.check(L.pwc_conv3x3_c16pair_pack_f32(_p(k1.value.data_ptr()), _p(k2.value.data_ptr()), _p(packed.data_ptr()), s),
-                       "conv3x3 c16pair pack")
-            cache[key] = packed
+        packed = _packed("c16pair", [k1.value, k2.value], cache=self.owner._cache,
+                         key=(names[0], "c16pair", self.store.version))
         _keep(packed, y_t)
         M = x.N * x.H * x.W
         _track_max(self.owner, x)
         _launch(L.pwc_conv3x3_c16pair_f32,
                 (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(b1.value.data_ptr()), _p(b2.value.data_ptr()), _p(y.ptr), y.cs,
-                 x.N, x.H, x.W, float(slope), s),
+                 x.N, x.H, x.W, float(slope), _lib.current_stream()),
                 f"conv3x3_c16pair {names[0]}+{names[1]}", "conv3x3_c16pair_kernel",
                 2.0 * 2.0 * M * 9 * 16 * 16, 4.0 * (M * 16 + M * 16),
                 # executed: 14 MFMAs of 16x16x32 per 16 pixels and layer on 1.27 / 1.13 x the tile's pixels (halo, row wrap)
@@ -267,7 +259,7 @@ class _ConvRunner:
         L = _lib.lib()
         v0 = image_views[0]
         n_tot = sum(v.N for v in image_views)
-        ok = (self.k == 0 and len(image_views) <= 2 and slope is not None and getattr(self.owner, "f16x2", True)
+        ok = (self.k == 0 and len(image_views) <= 2 and slope is not None and self.owner.f16x2
               and all(v.C == 3 and v.cs == 3 and v.ptr % 16 == 0 and v.H == v0.H and v.W == v0.W for v in image_views)
               and L.pwc_conv3x3_c3c16pair_supported(n_tot, v0.H, v0.W))
         if not ok:
@@ -277,20 +269,11 @@ class _ConvRunner:
         shapes = [(3, 3, 3, 16), (3, 3, 16, 16), (3, 3, 16, 16)]
         ks = [self.store.get(nm + "/kernel", sh, "kernel") for nm, sh in zip(names, shapes)]
         bs = [self.store.get(nm + "/bias", (16,), "bias") for nm in names]
-        dev = ks[0].value.device
-        s = _lib.current_stream()
         Ho, Wo = _same_out(v0.H, 2), _same_out(v0.W, 2)
-        y_t = torch.empty((n_tot, Ho, Wo, 16), dtype=torch.float32, device=dev)
+        y_t = torch.empty((n_tot, Ho, Wo, 16), dtype=torch.float32, device=ks[0].value.device)
         y = View(y_t.data_ptr(), 16, n_tot, Ho, Wo, 16)
-        cache = self.owner._cache
-        key = (names[0], "c3c16pair", self.store.version)
-        packed = cache.get(key)
-        if packed is None:
-            packed = torch.empty((L.pwc_conv3x3_c3c16pair_packed_floats(),), dtype=torch.float32, device=dev)
-            _lib.check(L.pwc_conv3x3_c3c16pair_pack_f32(_p(ks[0].value.data_ptr()), _p(ks[1].value.data_ptr()),
-                                                        _p(ks[2].value.data_ptr()), _p(packed.data_ptr()), s),
-                       "conv3x3 c3c16pair pack")
-            cache[key] = packed
+        packed = _packed("c3c16pair", [k.value for k in ks], cache=self.owner._cache,
+                         key=(names[0], "c3c16pair", self.store.version))
         _keep(packed, y_t)
         va = image_views[0]
         vb = image_views[1] if len(image_views) == 2 else None
@@ -300,15 +283,15 @@ class _ConvRunner:
         _launch(L.pwc_conv3x3_c3c16pair_f32,
                 (_p(va.ptr), va.N, _p(vb.ptr) if vb is not None else None, vb.N if vb is not None else 0, _p(packed.data_ptr()),
                  _p(bs[0].value.data_ptr()), _p(bs[1].value.data_ptr()), _p(bs[2].value.data_ptr()), _p(y.ptr), y.cs,
-                 v0.H, v0.W, float(slope), s),
+                 v0.H, v0.W, float(slope), _lib.current_stream()),
                 f"conv3x3_c3c16pair {names[0]}+{names[1]}+{names[2]}", "conv3x3_c16pair_kernel",
                 2.0 * M * 9 * (3 * 16 + 2 * 16 * 16), 4.0 * (n_tot * v0.H * v0.W * 3 + M * 16),
                 # executed: 3 MFMAs of 16x16x32 per 16 patch pixels (45 tiles) + 14 per 16 pixels and layer (41 + 36 tiles)
                 exec_flops=2.0 * 16 * 16 * 32 * (3 * 45 + 14 * (41 + 36)) * (M / 512.0))
         return y, y_t
 
-    def conv(self, x, cout, y=None, stride=1, dilation=1, slope=0.1, cin_map=None,
-             cin_logical=None, residual=None, tile=-1, split=0, x2=None, x3=None):
+    def conv(self, x, cout, y=None, stride=1, dilation=1, slope=0.1, cin_map=None, cin_logical=None, residual=None,
+             x2=None, x3=None):
         """x: View over the PHYSICAL input channels.  cin_map: physical->logical map (or
         None = identity).  x2 (round 5): a second View over the same pixels whose channels follow x's in the physical order
         (cin_map covers both) -- only the F16-pipe kernel takes it: the caller asks h2_two_operand_ok first.  x3 (round 6): a
@@ -326,272 +309,77 @@ class _ConvRunner:
             y_t = torch.empty((x.N, Ho, Wo, cout), dtype=torch.float32, device=kern.value.device)
             y = View(y_t.data_ptr(), cout, x.N, Ho, Wo, cout)
         assert (y.N, y.H, y.W, y.C) == (x.N, Ho, Wo, cout), (y, x, stride)
-        L = _lib.lib()
-        s = _lib.current_stream()
-        act = 0 if slope is None else 1
-        sl = 0.0 if slope is None else float(slope)
         assert x3 is None or x2 is not None
         c_phys = x.C + (x2.C if x2 is not None else 0) + (x3.C if x3 is not None else 0)
-        use_mfma = (cout % 16 == 0 and x.C % 16 == 0 and x.cs % 4 == 0 and x.ptr % 16 == 0
-                    and residual is None)
-        cache = self.owner._cache
-        use_wino = (use_mfma and getattr(self.owner, "winograd", False) and stride == 1
-                    and tile < 0 and split == 0 and _wino_pays(L, x.N, x.H, x.W, cout, dilation))
-        use_wino4 = (use_wino and getattr(self.owner, "winograd4", True) and y.cs % 4 == 0 and y.ptr % 16 == 0
-                     and L.pwc_conv3x3_wino4_supported(x.N, x.H, x.W, x.C, cout, dilation))
-        use_h2 = (use_mfma and getattr(self.owner, "f16x2", True) and stride == 1 and tile < 0 and split == 0
-                  and (x3 is None or dilation == 1)
-                  and cout % 32 == 0 and y.cs % 4 == 0 and y.ptr % 16 == 0
-                  and L.pwc_conv3x3_h2_supported(x.N, x.H, x.W, c_phys, cout, dilation))
-        # (experiment switch, scripts/exp_ab_model.py h2_relaxed: the F16-pipe kernel wherever it HAS a plan, also below the
-        # tile count its _supported asks for)
-        if (not use_h2 and getattr(self.owner, "h2_relaxed", False) and use_mfma and getattr(self.owner, "f16x2", True)
-                and stride == 1 and dilation == 1 and tile < 0 and split == 0 and cout % 32 == 0 and c_phys >= 32
-                and y.cs % 4 == 0 and y.ptr % 16 == 0 and x.H >= 7 and x.W >= 24
-                and L.pwc_conv3x3_h2_plan(x.N, x.H, x.W, c_phys, cout, 1) != 0):
-            use_h2 = True
-        # small launches (round 5): the K dimension dealt to the waves of one workgroup, ONE dispatch (conv3x3_sk.hip)
-        use_sk = (use_mfma and getattr(self.owner, "f16x2", True) and getattr(self.owner, "small_conv", True) and x2 is None
-                  and tile < 0 and split == 0 and x.C % 32 == 0 and y.cs % 4 == 0 and y.ptr % 16 == 0
-                  and L.pwc_conv3x3_sk_supported(x.N, x.H, x.W, x.C, cout, stride, dilation))
-        # thin inputs to 32 channels (round 5): weights stationary in registers (conv3x3_t32.hip)
-        use_t32 = (use_mfma and getattr(self.owner, "f16x2", True) and getattr(self.owner, "thin_conv", True) and x2 is None
-                   and tile < 0 and split == 0 and dilation == 1 and cout == 32 and y.cs % 4 == 0 and y.ptr % 16 == 0
-                   and (x.C == 16 or getattr(self.owner, "thin_conv32", True))
-                   and x.N * Ho * Wo * y.cs * 4 < (1 << 31)      # (32-bit store offsets: ADVICE r5)
-                   and L.pwc_conv3x3_t32_supported(x.N, x.H, x.W, x.C, cout, stride))
-        if x2 is not None and not use_h2:
+        fam = self._family(x, y, stride, dilation, residual, x2, x3, c_phys)
+        if x2 is not None and fam != "h2":
             raise _lib.PwcHipError(f"{name}: a two-operand input needs the F16-pipe kernel (h2_two_operand_ok)")
-        # 32 output channels from 32 / 64 input channels (round 6): the weights resident in the LDS (conv3x3_w32.hip)
-        use_w32 = (use_mfma and getattr(self.owner, "f16x2", True) and getattr(self.owner, "w32_conv", True) and x2 is None
-                   and tile < 0 and split == 0 and stride == 1 and dilation == 1 and cout == 32 and x.C in (32, 64)
-                   and y.cs % 4 == 0 and y.ptr % 16 == 0 and x.N * Ho * Wo * y.cs * 4 < (1 << 31)
-                   and L.pwc_conv3x3_w32_supported(x.N, x.H, x.W, x.C, cout, stride, dilation))
-        if use_w32:
-            key = (name, "w32", x.C, None if cin_map is None else cin_map.tobytes(), self.store.version)
-            packed = cache.get(key)
-            if packed is None:
-                packed = torch.empty((L.pwc_conv3x3_w32_packed_floats(x.C),), dtype=torch.float32, device=kern.value.device)
-                cm = None
-                if cin_map is not None:
-                    assert len(cin_map) == x.C
-                    cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(kern.value.device)
-                _lib.check(L.pwc_conv3x3_w32_pack_f32(_p(kern.value.data_ptr()), _p(cm.data_ptr()) if cm is not None else None,
-                                                      cin, x.C, _p(packed.data_ptr()), s), "conv3x3 w32 pack")
-                cache[key] = packed
-            _keep(packed, y_t)
-            _track_max(self.owner, x)
-            _launch(L.pwc_conv3x3_w32_f32,
-                    (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                     x.N, x.H, x.W, x.C, cout, act, sl, s),
-                    f"conv3x3_w32 {name}", "conv3x3_w32_kernel",
-                    2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout),
-                    exec_flops=3.0 * 2.0 * x.N * Ho * Wo * 9 * x.C * cout)
-            return y, y_t
-        if use_t32:
-            key = (name, "t32", x.C, None if cin_map is None else cin_map.tobytes(), self.store.version)
-            packed = cache.get(key)
-            if packed is None:
-                packed = torch.empty((L.pwc_conv3x3_t32_packed_floats(x.C),), dtype=torch.float32, device=kern.value.device)
-                cm = None
-                if cin_map is not None:
-                    assert len(cin_map) == x.C
-                    cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(kern.value.device)
-                _lib.check(L.pwc_conv3x3_t32_pack_f32(_p(kern.value.data_ptr()), _p(cm.data_ptr()) if cm is not None else None,
-                                                      cin, x.C, _p(packed.data_ptr()), s), "conv3x3 t32 pack")
-                cache[key] = packed
-            _keep(packed, y_t)
-            _track_max(self.owner, x)
-            _launch(L.pwc_conv3x3_t32_f32,
-                    (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                     x.N, x.H, x.W, x.C, cout, stride, act, sl, s),
-                    f"conv3x3_t32 {name}", "conv3x3_t32_kernel",
-                    2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout),
-                    exec_flops=3.0 * 2.0 * x.N * Ho * Wo * 9 * x.C * cout)
-            return y, y_t
-        if use_sk:
-            key = (name, "sk", x.C, None if cin_map is None else cin_map.tobytes(), self.store.version)
-            packed = cache.get(key)
-            if packed is None:
-                packed = torch.empty((L.pwc_conv3x3_sk_packed_floats(x.C, cout),), dtype=torch.float32, device=kern.value.device)
-                cm = None
-                if cin_map is not None:
-                    assert len(cin_map) == x.C
-                    cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(kern.value.device)
-                _lib.check(L.pwc_conv3x3_sk_pack_f32(_p(kern.value.data_ptr()), _p(cm.data_ptr()) if cm is not None else None,
-                                                     cin, x.C, cout, _p(packed.data_ptr()), s), "conv3x3 sk pack")
-                cache[key] = packed
-            _keep(packed, y_t)
-            _track_max(self.owner, x)
-            _launch(L.pwc_conv3x3_sk_f32,
-                    (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                     x.N, x.H, x.W, x.C, cout, stride, dilation, act, sl, s),
-                    f"conv3x3_sk {name}", "conv3x3_sk_kernel",
-                    2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout),
-                    exec_flops=3.0 * 2.0 * x.N * Ho * Wo * 9 * x.C * cout)
-            return y, y_t
-        use_h2s2 = (use_mfma and getattr(self.owner, "f16x2", True) and stride == 2 and dilation == 1 and tile < 0 and split == 0
-                    and cout % 32 == 0 and y.cs % 4 == 0 and y.ptr % 16 == 0
-                    and L.pwc_conv3x3_h2_stride2_supported(x.N, x.H, x.W, x.C, cout))
-        if use_h2 or use_h2s2:
-            # direct convolution on the F16 matrix pipe, fp32 operands as two-term fp16 splits (conv3x3_h2.hip); stride 2 = the
-            # same kernel over the input's four parity planes (round 5)
-            key = (name, "h2s2" if use_h2s2 else "h2", c_phys, None if cin_map is None else cin_map.tobytes(), self.store.version)
-            packed = cache.get(key)
-            if packed is None:
-                nfl = (L.pwc_conv3x3_h2_stride2_packed_floats if use_h2s2 else L.pwc_conv3x3_h2_packed_floats)(c_phys, cout)
-                packed = torch.empty((nfl,), dtype=torch.float32, device=kern.value.device)
-                cm = None
-                if cin_map is not None:
-                    assert len(cin_map) == c_phys
-                    cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(kern.value.device)
-                _lib.check((L.pwc_conv3x3_h2_stride2_pack_f32 if use_h2s2 else L.pwc_conv3x3_h2_pack_f32)(
-                    _p(kern.value.data_ptr()), _p(cm.data_ptr()) if cm is not None else None,
-                    cin, c_phys, cout, _p(packed.data_ptr()), s), "conv3x3 h2 pack")
-                cache[key] = packed
-            _keep(packed, y_t)
-            # more tiles than CUs: one workgroup per CU with an equal share of the (tile, stage) sequence (stream-K)
-            wsf = (L.pwc_conv3x3_h2_stride2_workspace_floats(x.N, x.H, x.W, c_phys, cout) if use_h2s2 else
-                   L.pwc_conv3x3_h2_workspace_floats(x.N, x.H, x.W, c_phys, cout, dilation))
-            ws = _h2_workspace(kern.value.device, wsf) if wsf and getattr(self.owner, "f16x2_stream_k", True) else None
-            if ws is not None:
-                _keep(ws)
-            wsa = (_p(ws.data_ptr()) if ws is not None else None, ws.numel() if ws is not None else 0)
-            status = getattr(self.owner, "status", None)      # the model's status words (stream-K timeout)
-            if status is not None:
-                _keep(status)
+        cache = self.owner._cache
+        key = (name, fam, c_phys, None if cin_map is None else cin_map.tobytes(), self.store.version)
+        if fam != "direct":
+            w = _packed(fam, [kern.value], (cin, c_phys) if fam in ("w32", "t32") else (cin, c_phys, cout), cin_map,
+                        cache, key)
+        elif cin_map is not None:
+            w = cache.get(key)
+            if w is None:
+                idx = torch.from_numpy(np.ascontiguousarray(cin_map, np.int64)).to(kern.value.device)
+                w = torch.zeros((3, 3, x.C, cout), dtype=torch.float32, device=kern.value.device)
+                valid = idx >= 0
+                w[:, :, valid, :] = kern.value[:, :, idx[valid], :]
+                cache[key] = w = w.contiguous()
+        elif x.C != cin:
+            raise ValueError(f"{name}: input has {x.C} channels, kernel expects {cin}")
+        else:
+            w = kern.value
+        _keep(w, y_t)
+        if fam in ("w32", "t32", "sk", "h2", "h2s2"):        # the F16-pipe families
             for v in (x, x2, x3):
                 if v is not None:
                     _track_max(self.owner, v._replace(C=min(v.C, v.cs)))
-            if use_h2 and x3 is not None:
-                fn = L.pwc_conv3x3_h2_ex3_f32
-                args = (_p(x.ptr), x.cs, x.C, _p(x2.ptr), x2.cs, x2.C, _p(x3.ptr), x3.cs,
-                        _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                        x.N, x.H, x.W, c_phys, cout, act, sl) + wsa + (_p(status.data_ptr()) if status is not None else None, s)
-            elif use_h2:
-                fn = L.pwc_conv3x3_h2_ex_f32
-                args = (_p(x.ptr), x.cs, x.C if x2 is not None else 0, _p(x2.ptr) if x2 is not None else None,
-                        x2.cs if x2 is not None else 0, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                        x.N, x.H, x.W, c_phys, cout, dilation, act, sl) + wsa + (_p(status.data_ptr()) if status is not None else None, s)
-            else:
-                fn = L.pwc_conv3x3_h2_stride2_f32
-                args = (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                        x.N, x.H, x.W, x.C, cout, act, sl) + wsa + (_p(status.data_ptr()) if status is not None else None, s)
-            _launch(fn, args, f"conv3x3_h2 {name}", "conv3x3_h2_kernel",
-                    2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout),
-                    # executed: three fp16 products per multiply-add, per physical input channel (stride 2: 16 products per
-                    # output and channel -- four taps on each of the four parity planes)
-                    exec_flops=3.0 * 2.0 * x.N * Ho * Wo * (16 if use_h2s2 else 9) * c_phys * cout)
-        elif use_wino4:
-            # F(4x4,3x3): 36 multiplies per 4x4 outputs (the big full-resolution layers)
-            key = (name, "wino4", x.C, None if cin_map is None else cin_map.tobytes(), self.store.version)
-            packed = cache.get(key)
-            if packed is None:
-                nfl = L.pwc_conv3x3_wino4_packed_floats(x.C, cout)
-                packed = torch.empty((nfl,), dtype=torch.float32, device=kern.value.device)
-                cm = None
-                if cin_map is not None:
-                    assert len(cin_map) == x.C
-                    cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(kern.value.device)
-                _lib.check(L.pwc_conv3x3_wino4_pack_f32(_p(kern.value.data_ptr()),
-                                                        _p(cm.data_ptr()) if cm is not None else None,
-                                                        cin, x.C, cout, _p(packed.data_ptr()), s), "conv3x3 wino4 pack")
-                cache[key] = packed
-            _keep(packed, y_t)
-            _launch(L.pwc_conv3x3_wino4_f32,
-                    (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                     x.N, x.H, x.W, x.C, cout, dilation, act, sl, s),
-                    f"conv3x3_wino4 {name}", "conv3x3_wino4_kernel",
-                    2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout),
-                    # executed: 36 multiplies per 4x4 output tile (per sub-lattice of a dilated conv), per physical input channel
-                    exec_flops=2.0 * x.N * dilation * dilation * (-(-(-(-Ho // dilation)) // 4)) * (-(-(-(-Wo // dilation)) // 4))
-                    * 36 * x.C * cout)
-        elif use_wino:
-            key = (name, "wino", x.C, None if cin_map is None else cin_map.tobytes(), self.store.version)
-            packed = cache.get(key)
-            if packed is None:
-                nfl = L.pwc_conv3x3_wino_packed_floats(x.C, cout)
-                packed = torch.empty((nfl,), dtype=torch.float32, device=kern.value.device)
-                cm = None
-                if cin_map is not None:
-                    assert len(cin_map) == x.C
-                    cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(kern.value.device)
-                _lib.check(L.pwc_conv3x3_wino_pack_f32(_p(kern.value.data_ptr()),
-                                                       _p(cm.data_ptr()) if cm is not None else None,
-                                                       cin, x.C, cout, _p(packed.data_ptr()), s), "conv3x3 wino pack")
-                cache[key] = packed
-            _keep(packed, y_t)
-            # launches that would leave most workgroup slots empty deal their channel stages to several workgroups
-            csplit = (L.pwc_conv3x3_wino_split_plan(x.N, x.H, x.W, x.C, cout, dilation)
-                      if getattr(self.owner, "wino_channel_split", True) else 1)
-            if csplit > 1:
-                ws = _workspace(kern.value.device, L.pwc_conv3x3_wino_split_workspace_floats(x.N, x.H, x.W, cout, csplit))
-                _keep(ws)
-                fn, extra = L.pwc_conv3x3_wino_split_f32, (csplit, _p(ws.data_ptr()), ws.numel(), s)
-            else:
-                fn, extra = L.pwc_conv3x3_wino_f32, (s,)
-            _launch(fn,
-                    (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                     x.N, x.H, x.W, x.C, cout, dilation, act, sl) + extra,
-                    f"conv3x3_wino {name}", "conv3x3_wino_kernel",
-                    2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout),
-                    # executed: 16 multiplies per 2x2 output tile, per physical input channel
-                    exec_flops=2.0 * x.N * (-(-Ho // 2)) * (-(-Wo // 2)) * 16 * x.C * cout)
-        elif use_mfma:
-            key = (name, "mfma", x.C, None if cin_map is None else cin_map.tobytes(), self.store.version)
-            packed = cache.get(key)
-            if packed is None:
-                nfl = L.pwc_conv3x3_packed_floats(x.C, cout)
-                packed = torch.empty((nfl,), dtype=torch.float32, device=kern.value.device)
-                cm = None
-                if cin_map is not None:
-                    assert len(cin_map) == x.C
-                    cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(kern.value.device)
-                _lib.check(L.pwc_conv3x3_pack_f32(_p(kern.value.data_ptr()),
-                                                  _p(cm.data_ptr()) if cm is not None else None,
-                                                  cin, x.C, cout, _p(packed.data_ptr()), s), "conv3x3 pack")
-                cache[key] = packed
-                cache[key + ("cm",)] = cm
-            flops = 2.0 * x.N * Ho * Wo * 9 * cin * cout     # algorithmic: logical Cin, no padding
-            ws = _workspace(kern.value.device, L.pwc_conv3x3_workspace_floats(x.N * Ho * Wo, cout))
-            _keep(ws, packed, y_t)
-            _launch(L.pwc_conv3x3_f32,
-                    (_p(x.ptr), x.cs, _p(packed.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs,
-                     x.N, x.H, x.W, x.C, cout, stride, dilation, act, sl, tile, split, _p(ws.data_ptr()),
-                     ws.numel(), s),
-                    f"conv3x3 {name}",
-                    (f"conv3x3_halo_kernel<{x.C},{cout}>"
-                     if tile < 0 and split == 0 and L.pwc_conv3x3_uses_halo_kernel(x.N * Ho * Wo, x.C, cout, stride, dilation)
-                     else _mfma_kernel_name(L, x.N * Ho * Wo, cout, x.C, tile, split)), flops,
-                    4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout))
-        else:
-            w = kern.value
-            if cin_map is not None:
-                key = (name, "direct", x.C, cin_map.tobytes(), self.store.version)
-                w = cache.get(key)
-                if w is None:
-                    idx = torch.from_numpy(np.ascontiguousarray(cin_map, np.int64)).to(kern.value.device)
-                    w = torch.zeros((3, 3, x.C, cout), dtype=torch.float32, device=kern.value.device)
-                    valid = idx >= 0
-                    w[:, :, valid, :] = kern.value[:, :, idx[valid], :]
-                    w = w.contiguous()
-                    cache[key] = w
-            elif x.C != cin:
-                raise ValueError(f"{name}: input has {x.C} channels, kernel expects {cin}")
-            r_ptr, r_cs = (None, 0) if residual is None else (_p(residual.ptr), residual.cs)
-            _keep(w, y_t)
-            _launch(L.pwc_conv3x3_direct_f32,
-                    (_p(x.ptr), x.cs, _p(w.data_ptr()), _p(bias.value.data_ptr()), _p(y.ptr), y.cs, r_ptr, r_cs,
-                     x.N, x.H, x.W, x.C, cout, stride, dilation, act, sl, s),
-                    f"conv3x3_direct {name}", f"conv3x3_direct_kernel<cout={cout}>",
-                    2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout))
+        _conv_launch(fam, name, x, y, w, bias.value, cin, stride, dilation, slope, x2, x3, residual,
+                     status=self.owner.status, stream_k=self.owner.f16x2_stream_k,
+                     channel_split=self.owner.wino_channel_split)
         return y, y_t
+
+    def _family(self, x, y, stride, dilation, residual, x2, x3, c_phys):
+        """The kernel family of one conv: the first of w32, t32, sk, h2 / h2s2, wino4, wino, mfma whose conditions hold,
+        else direct."""
+        o, L, cout = self.owner, _lib.lib(), y.C
+        if not (cout % 16 == 0 and x.C % 16 == 0 and x.cs % 4 == 0 and x.ptr % 16 == 0 and residual is None):
+            return "direct"
+        y_ok = y.cs % 4 == 0 and y.ptr % 16 == 0
+        f16 = o.f16x2 and y_ok
+        y_fits = x.N * y.H * y.W * y.cs * 4 < (1 << 31)      # (32-bit store offsets: ADVICE r5)
+        # 32 output channels from 32 / 64 input channels (round 6): the weights resident in the LDS (conv3x3_w32.hip)
+        if (f16 and o.w32_conv and x2 is None and stride == 1 and dilation == 1 and cout == 32 and x.C in (32, 64)
+                and y_fits and L.pwc_conv3x3_w32_supported(x.N, x.H, x.W, x.C, cout, stride, dilation)):
+            return "w32"
+        # thin inputs to 32 channels (round 5): weights stationary in registers (conv3x3_t32.hip)
+        if (f16 and o.thin_conv and x2 is None and dilation == 1 and cout == 32 and (x.C == 16 or o.thin_conv32)
+                and y_fits and L.pwc_conv3x3_t32_supported(x.N, x.H, x.W, x.C, cout, stride)):
+            return "t32"
+        # small launches (round 5): the K dimension dealt to the waves of one workgroup, ONE dispatch (conv3x3_sk.hip)
+        if (f16 and o.small_conv and x2 is None and x.C % 32 == 0
+                and L.pwc_conv3x3_sk_supported(x.N, x.H, x.W, x.C, cout, stride, dilation)):
+            return "sk"
+        if (f16 and stride == 1 and (x3 is None or dilation == 1) and cout % 32 == 0
+                and L.pwc_conv3x3_h2_supported(x.N, x.H, x.W, c_phys, cout, dilation)):
+            return "h2"
+        if (f16 and stride == 2 and dilation == 1 and cout % 32 == 0
+                and L.pwc_conv3x3_h2_stride2_supported(x.N, x.H, x.W, x.C, cout)):
+            return "h2s2"
+        if o.winograd and stride == 1 and _wino_pays(L, x.N, x.H, x.W, cout, dilation):
+            # F(4x4,3x3): 36 multiplies per 4x4 outputs (the big full-resolution layers)
+            if o.winograd4 and y_ok and L.pwc_conv3x3_wino4_supported(x.N, x.H, x.W, x.C, cout, dilation):
+                return "wino4"
+            return "wino"
+        return "mfma"
 
 
 def _track_max(owner, v):
     """PWCDCNet(track_max=True): the largest |value| of an operand of an F16-pipe kernel goes into the model's status words
     (pwc_absmax_f32) -- a debugging aid, one small launch per operand."""
-    if getattr(owner, "track_max", False) and getattr(owner, "status", None) is not None:
+    if owner.track_max and owner.status is not None:
         _keep(owner.status)
         _launch(_lib.lib().pwc_absmax_f32, (_p(v.ptr), v.cs, v.N * v.H * v.W, v.C, _p(owner.status.data_ptr()), _lib.current_stream()),
                 "absmax", "absmax_kernel", 0.0, 4.0 * v.N * v.H * v.W * v.C)
@@ -662,12 +450,9 @@ def _wino_pays(L, N, H, W, cout, dilation):
     return L.pwc_conv3x3_wino_workgroups(N, H, W, cout, dilation) >= 24 and fill >= 0.6
 
 
-def _mfma_kernel_name(L, M, cout, cin_phys, tile, split):
+def _mfma_kernel_name(L, M, cout, cin_phys):
     plan = (_lib.ctypes.c_int * 4)()
-    if tile >= 0:
-        plan[0], plan[1], plan[3] = tile, -1, max(split, 1)
-    else:
-        L.pwc_conv3x3_plan(M, cout, cin_phys, plan)
+    L.pwc_conv3x3_plan(M, cout, cin_phys, plan)
     bm, bn = _lib.ctypes.c_int(), _lib.ctypes.c_int()
     L.pwc_conv3x3_tile_shape(plan[0], bm, bn)
     name = f"conv3x3_mfma_kernel<{bm.value}x{bn.value},KC{32 if cin_phys % 32 == 0 else 16}>"
@@ -679,13 +464,127 @@ def _mfma_kernel_name(L, M, cout, cin_phys, tile, split):
     return name
 
 
+def _packed(fam, weights, dims=(), cin_map=None, cache=None, key=None):
+    """The weights of one launch of kernel family `fam` in its packed form: cache[key], else a new buffer that the family's
+    packer fills.  Conv packers: pwc_conv3x3_<fam>_pack_f32(kernel, cin_map, *dims, out, stream) with dims = (logical Cin,
+    physical Cin[, Cout]) and cin_map the physical -> logical input channel map (numpy; None = identity); the fused-layer
+    packers (c16pair, c3c16pair) take their kernels only.  cache None: a temporary, left to the caller."""
+    packed = None if cache is None else cache.get(key)
+    if packed is None:
+        L = _lib.lib()
+        entry = {"h2s2": "pwc_conv3x3_h2_stride2", "mfma": "pwc_conv3x3"}.get(fam, "pwc_conv3x3_" + fam)
+        dev = weights[0].device
+        packed = torch.empty((getattr(L, entry + "_packed_floats")(*dims[1:]),), dtype=torch.float32, device=dev)
+        args = [_p(w.data_ptr()) for w in weights]
+        if dims:
+            cm = None
+            if cin_map is not None:
+                assert len(cin_map) == dims[1]
+                cm = torch.from_numpy(np.ascontiguousarray(cin_map, np.int32)).to(dev)
+            args += [_p(cm.data_ptr()) if cm is not None else None, *dims]
+        _lib.check(getattr(L, entry + "_pack_f32")(*args, _p(packed.data_ptr()), _lib.current_stream()), f"conv3x3 {fam} pack")
+        if cache is not None:
+            cache[key] = packed
+    return packed
+
+
+def _conv_launch(fam, name, x, y, w, bias, cin, stride=1, dilation=1, slope=None, x2=None, x3=None, residual=None,
+                 status=None, stream_k=True, channel_split=True, scratch=_workspace):
+    """One conv launch of kernel family `fam` -- the inference forward's (_ConvRunner.conv) and the training path's
+    (grad_ops.conv3x3_raw).  w: the packed weights (direct: the (3,3,x.C,Cout) kernel in x's physical channel order); cin:
+    the logical input channel count the algorithmic work is counted with.  The caller's policy: status = the words the
+    F16-pipe kernels report a stream-K timeout in (or None); stream_k: may h2 use its stream-K form; channel_split: may the
+    F(2x2) Winograd kernel deal its channel stages to several workgroups; scratch(device, floats): the scratch of the
+    channel split and of the fp32 MFMA kernel's tap split."""
+    L = _lib.lib()
+    s = _lib.current_stream()
+    cout, Ho, Wo = y.C, y.H, y.W
+    act, sl = (0, 0.0) if slope is None else (1, float(slope))
+    c_phys = x.C + (x2.C if x2 is not None else 0) + (x3.C if x3 is not None else 0)
+    head = (_p(x.ptr), x.cs, _p(w.data_ptr()), _p(bias.data_ptr()), _p(y.ptr), y.cs)
+    geo = (x.N, x.H, x.W, x.C, cout)
+    label = {"mfma": "conv3x3", "h2s2": "conv3x3_h2"}.get(fam, "conv3x3_" + fam)
+    kname = label + "_kernel"
+    # executed flops of the F16-pipe kernels: three fp16 products per multiply-add, per physical input channel
+    xflops = 3.0 * 2.0 * x.N * Ho * Wo * 9 * c_phys * cout
+    if fam == "w32":
+        fn, args = L.pwc_conv3x3_w32_f32, head + geo + (act, sl, s)
+    elif fam == "t32":
+        fn, args = L.pwc_conv3x3_t32_f32, head + geo + (stride, act, sl, s)
+    elif fam == "sk":
+        fn, args = L.pwc_conv3x3_sk_f32, head + geo + (stride, dilation, act, sl, s)
+    elif fam in ("h2", "h2s2"):
+        # direct convolution on the F16 matrix pipe, fp32 operands as two-term fp16 splits (conv3x3_h2.hip); stride 2 = the
+        # same kernel over the input's four parity planes (round 5).  More tiles than CUs: one workgroup per CU with an
+        # equal share of the (tile, stage) sequence (stream-K)
+        wsf = (L.pwc_conv3x3_h2_stride2_workspace_floats(x.N, x.H, x.W, c_phys, cout) if fam == "h2s2" else
+               L.pwc_conv3x3_h2_workspace_floats(x.N, x.H, x.W, c_phys, cout, dilation))
+        ws = _h2_workspace(w.device, wsf) if wsf and stream_k else None
+        _keep(ws, status)
+        tail = (act, sl, _p(ws.data_ptr()) if ws is not None else None, ws.numel() if ws is not None else 0,
+                _p(status.data_ptr()) if status is not None else None, s)
+        if fam == "h2s2":
+            fn, args = L.pwc_conv3x3_h2_stride2_f32, head + geo + tail
+            xflops = 3.0 * 2.0 * x.N * Ho * Wo * 16 * c_phys * cout     # 16 products: four taps on each parity plane
+        elif x3 is not None:
+            fn = L.pwc_conv3x3_h2_ex3_f32
+            args = ((_p(x.ptr), x.cs, x.C, _p(x2.ptr), x2.cs, x2.C, _p(x3.ptr), x3.cs) + head[2:]
+                    + (x.N, x.H, x.W, c_phys, cout) + tail)
+        else:
+            fn = L.pwc_conv3x3_h2_ex_f32
+            args = ((_p(x.ptr), x.cs, x.C if x2 is not None else 0, _p(x2.ptr) if x2 is not None else None,
+                     x2.cs if x2 is not None else 0) + head[2:] + (x.N, x.H, x.W, c_phys, cout, dilation) + tail)
+    elif fam == "wino4":
+        fn, args = L.pwc_conv3x3_wino4_f32, head + geo + (dilation, act, sl, s)
+        # executed: 36 multiplies per 4x4 output tile (per sub-lattice of a dilated conv), per physical input channel
+        xflops = (2.0 * x.N * dilation * dilation * (-(-(-(-Ho // dilation)) // 4)) * (-(-(-(-Wo // dilation)) // 4))
+                  * 36 * x.C * cout)
+    elif fam == "wino":
+        # launches that would leave most workgroup slots empty deal their channel stages to several workgroups
+        csplit = L.pwc_conv3x3_wino_split_plan(x.N, x.H, x.W, x.C, cout, dilation) if channel_split else 1
+        if csplit > 1:
+            ws = scratch(w.device, L.pwc_conv3x3_wino_split_workspace_floats(x.N, x.H, x.W, cout, csplit))
+            _keep(ws)
+            fn, extra = L.pwc_conv3x3_wino_split_f32, (csplit, _p(ws.data_ptr()), ws.numel(), s)
+        else:
+            fn, extra = L.pwc_conv3x3_wino_f32, (s,)
+        args = head + geo + (dilation, act, sl) + extra
+        # executed: 16 multiplies per 2x2 output tile, per physical input channel
+        xflops = 2.0 * x.N * (-(-Ho // 2)) * (-(-Wo // 2)) * 16 * x.C * cout
+    elif fam == "mfma":
+        M = x.N * Ho * Wo
+        ws = scratch(w.device, L.pwc_conv3x3_workspace_floats(M, cout))
+        _keep(ws)
+        fn = L.pwc_conv3x3_f32
+        args = head + geo + (stride, dilation, act, sl, -1, 0, _p(ws.data_ptr()), ws.numel(), s)
+        kname = (f"conv3x3_halo_kernel<{x.C},{cout}>" if L.pwc_conv3x3_uses_halo_kernel(M, x.C, cout, stride, dilation)
+                 else _mfma_kernel_name(L, M, cout, x.C))
+        xflops = None
+    else:
+        assert fam == "direct", fam
+        fn = L.pwc_conv3x3_direct_f32
+        args = (head + ((None, 0) if residual is None else (_p(residual.ptr), residual.cs))
+                + geo + (stride, dilation, act, sl, s))
+        kname, xflops = f"conv3x3_direct_kernel<cout={cout}>", None
+    _launch(fn, args, f"{label} {name}", kname,
+            2.0 * x.N * Ho * Wo * 9 * cin * cout, 4.0 * (x.N * x.H * x.W * cin + x.N * Ho * Wo * cout), exec_flops=xflops)
+
+
 class _Module:
-    winograd = False     # route eligible convs (stride 1, dilation 1, Cout % 32 == 0) to the Winograd kernel
-    winograd4 = True     # ... and the big ones among them to the F(4x4,3x3) kernel (pwc_conv3x3_wino4_supported)
+    # routing switches: PWCDCNet sets winograd, winograd4, f16x2, track_max and status on its modules; the others are
+    # for experiments (scripts/exp_ab_model.py toggles them by name)
+    winograd = False             # eligible stride-1 convs go to the Winograd kernels where _wino_pays says they win
+    winograd4 = True             # ... the big ones among them to the F(4x4,3x3) kernel (pwc_conv3x3_wino4_supported)
     wino_channel_split = True    # F(2x2) launches that leave most workgroup slots empty deal their channel stages to several workgroups
-    f16x2_stream_k = True    # ... with one workgroup per CU and an equal share of the work each where a launch has more tiles than CUs
-    f16x2 = True         # the layers pwc_conv3x3_h2_supported names go to the direct F16-matrix-pipe kernel (fp32 operands as
-                         # exact-to-22-bit fp16 pairs, fp32 accumulation; inputs must stay below 65504)
+    f16x2 = True                 # the F16-matrix-pipe kernels (conv families w32, t32, sk, h2, c16pair and the correlation's):
+                                 # fp32 operands as exact-to-22-bit fp16 pairs, fp32 accumulation; inputs must stay below 65504
+    f16x2_stream_k = True        # h2: one workgroup per CU and an equal share of the work each where a launch has more tiles than CUs
+    small_conv = True            # conv3x3_sk: small launches, the K dimension dealt to the waves of one workgroup
+    thin_conv = True             # conv3x3_t32: 16 input channels to 32, the weights stationary in registers
+    thin_conv32 = True           # ... and 32 input channels to 32
+    w32_conv = True              # conv3x3_w32: 32 / 64 input channels to 32, the weights resident in the LDS
+    track_max = False            # the largest |value| of every F16-pipe operand goes into `status` (_track_max)
+    status = None                # the model's status words (device int32 x 2), or None
 
     def __init__(self, name):
         self.name = name
@@ -865,7 +764,7 @@ class CostVolumeLayer(_Module):
     def blk_ok(self, f0, f1, out, flow=None, f0_copy=None):
         """True if pwc_warp_cost_volume_concat_blk_f32 (F16 matrix pipe, one 4 x 4 block per workgroup: the small pyramid
         levels) takes this geometry and is the faster launch for it."""
-        if not getattr(self, "f16x2", True) or f0.C not in (64, 96, 128, 192):
+        if not self.f16x2 or f0.C not in (64, 96, 128, 192):
             return False
         if f0.C <= 96 and f0.N * f0.H * f0.W > self.BLK_MAX_PIXELS:
             return False
@@ -890,7 +789,7 @@ class CostVolumeLayer(_Module):
         npix = f0.N * f0.H * f0.W
         flops = 2.0 * npix * D * f0.C
         if concat:
-            h2 = getattr(self, "f16x2", True)        # correlation on the F16 matrix pipe (two-term operand splits), round 5
+            h2 = self.f16x2        # correlation on the F16 matrix pipe (two-term operand splits), round 5
             if h2:
                 _track_max(self, f0)
                 _track_max(self, f1)
@@ -978,7 +877,7 @@ class OpticalFlowEstimator_custom(_Module):
     def two_operand_ok(self, N, h, w, c_cv, c_f0, has_flow, fu_map):
         """True where the first conv of this (non-DC) estimator can read features_0 from the pyramid tensor: its launch goes
         to the F16-pipe kernel (the one with a second operand pointer) at the channel count the two-operand layout gives."""
-        if self.use_dc or not getattr(self, "f16x2", True) or not c_f0 or c_f0 % 16:
+        if self.use_dc or not self.f16x2 or not c_f0 or c_f0 % 16:
             return False
         lay = self._layout(c_cv, c_f0, has_flow, fu_map, f0_external=True)
         return bool(_lib.lib().pwc_conv3x3_h2_supported(N, h, w, lay.n_phys + c_f0, self.filters[0], 1))
@@ -1002,7 +901,7 @@ class OpticalFlowEstimator_custom(_Module):
     def three_operand_ok(self, N, h, w, c_cv, c_f0, c_fu):
         """True where the first conv of this (non-DC) estimator takes the three-tensor input (the F16-pipe kernel, at the stage
         count that input has)."""
-        if self.use_dc or not getattr(self, "f16x2", True) or not c_f0 or c_f0 % 16 or not c_fu or c_fu % 16 or c_cv != 81:
+        if self.use_dc or not self.f16x2 or not c_f0 or c_f0 % 16 or not c_fu or c_fu % 16 or c_cv != 81:
             return False
         return bool(_lib.lib().pwc_conv3x3_h2_supported(N, h, w, 96 + c_f0 + c_fu, self.filters[0], 1))
 
