@@ -242,9 +242,9 @@ int pwc_conv3x3_wino4_supported(int N, int H, int W, int Cin_phys, int Cout, int
  * above 2^-22 are formed (uh vh, uh vm', um' vh; v_mfma_f32_32x32x16_f16) in two fp32 accumulators.  Measured error
  * against a float64 convolution: 0.1x that of pwc_conv3x3_wino4_f32 and 0.7x that of pwc_conv3x3_wino_f32 on every
  * layer shape (profiles/r04_exp_h2.txt), 0.4x that of a v_mfma_f32_16x16x4_f32 chain (profiles/
- * r04_exp_f16x2_numerics.txt).  RANGE: inputs and weights must be below 65504 in magnitude (fp16's largest finite
- * value); a larger input makes the outputs that depend on it NaN (inf - inf in the split), never a silently wrong
- * number.  LOWER END: the split is exact to 22 bits for |x| >= 2^-14 (6e-5); below that h and m' reach fp16's subnormals and
+ * r04_exp_f16x2_numerics.txt).  RANGE: inputs and weights below 65520 in magnitude (fp16's largest finite value is 65504;
+ * up to 65520 h rounds to it and the split stays exact); 65520 and beyond makes the outputs that depend on it NaN (inf - inf
+ * in the split), never a silently wrong number.  LOWER END: the split is exact to 22 bits for |x| >= 2^-14 (6e-5); below that h and m' reach fp16's subnormals and
  * the operand carries an ABSOLUTE error of up to 1.5e-11 (3e-4 relative at |x| = 1e-7) -- harmless for activations and
  * weights that are summed with terms of ordinary size, not for a tensor that is small as a whole: the training path keeps its
  * data gradients on the fp32 kernels for that reason (pwcnet_amd/train.py, Trainer(f16x2_dgrad=False)).  packed_w comes from pwc_conv3x3_h2_pack_f32 (split weights, pwc_conv3x3_h2_packed_floats floats; same
@@ -276,8 +276,10 @@ int pwc_conv3x3_h2_supported(int N, int H, int W, int Cin_phys, int Cout, int di
  * them, launches only OR bits into status[0] / atomic-max status[1]; NULL: no report).
  *   status[0] & PWC_STATUS_NONFINITE        pwc_resize_bilinear_status_f32 wrote a value that is not finite.  The F16-pipe
  *                                           kernels (pwc_conv3x3_h2*, pwc_conv3x3_c16pair*, pwc_warp_cost_volume_concat_h2_f32)
- *                                           turn an operand at or beyond 65504 in magnitude into NaN outputs (inf - inf in the
- *                                           split), NaN survives every later layer of the network, so the model's LAST launch
+ *                                           turn an operand at or beyond 65520 in magnitude into NaN outputs (inf - inf in the
+ *                                           split; the band 65504-65519, which still splits exactly, is measured on the conv
+ *                                           kernels h2 / sk / t32 / w32 only -- c16pair and the correlation are tested at 1e5:
+ *                                           keep their operands below 65504), NaN survives every later layer of the network, so the model's LAST launch
  *                                           sees it: repeat the forward on the fp32 kernels (the reference, plain fp32, has no
  *                                           such limit).  Watching the operands inside the kernels instead was measured at 2-3 %
  *                                           of every launch (profiles/r05_timeline_range_tracking_cost.txt).
@@ -363,7 +365,7 @@ int pwc_conv3x3_h2_stride2_supported(int N, int H, int W, int Cin_phys, int Cout
 
 /* Round 5: 3x3 convolution for SMALL launches (csrc/conv3x3_sk.hip) -- the 7 x 16 and 14 x 32 pyramid levels of a batch of
  * 8, every level of a single pair -- on the F16 matrix pipe, arithmetic and RANGE of pwc_conv3x3_h2_f32 (two-term fp16
- * operand splits, fp32 accumulation; |x|, |w| < 65504).  Same operation as pwc_conv3x3_f32 (TF 'SAME' padding, stride 1 | 2,
+ * operand splits, fp32 accumulation; |x|, |w| < 65520).  Same operation as pwc_conv3x3_f32 (TF 'SAME' padding, stride 1 | 2,
  * any dilation, + bias, + leaky_relu when apply_act): the K dimension (9 taps x Cin_phys) of a 16-pixel x 16-channel tile is
  * dealt to the eight waves of ONE workgroup, every wave requests all its operands at once, the eight partial sums are added
  * in wave order (launches repeat bitwise) -- one dispatch where the tiled kernels need a tap / channel split over workgroups

@@ -11,7 +11,7 @@
 // v_mfma_f32_16x16x4_f32 chain's on every distribution tried (the matrix pipe rounds once per 16 products).  No Winograd
 // transform: no transform rounding (F(4x4) rounds ~6x coarser than F(2x2)), no per-position operand split, no 36-position
 // accumulator set -- the kernel is an implicit GEMM whose tiles are bounded by LDS and registers like any GEMM.
-// Range: |x| must stay below 65504 (fp16); the fp32 kernels remain for anything else.
+// Range: |x| must stay below 65520 (fp16 rounds it to 65504 at most); the fp32 kernels remain for anything else.
 // The matrix work: 9 taps x 3 products at the F16 rate (16x the fp32 MFMA rate) = 27/16 fp32-MFMA-equivalents per
 // multiply-add against F(4x4)'s 36/16 -- 0.75x the matrix time of the fp32 Winograd kernel, with nothing else on the SIMD that
 // serialises with it (no packed fp32 VALU: the split is plain v_cvt / v_sub / v_mul, once per workgroup and 16-channel stage).

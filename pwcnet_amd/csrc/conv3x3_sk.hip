@@ -18,7 +18,7 @@
 // wave order -- a fixed order: launches repeat bitwise.  One dispatch, one round trip for the operands, one for the store.
 //
 // Arithmetic: the two-term fp16 split of conv3x3_h2.hip (x = h + 2^-11 m', three v_mfma_f32_16x16x32_f16 per K step and tile,
-// fp32 accumulation: hh and the cross terms in separate accumulators).  RANGE as there: |x|, |w| < 65504, beyond: NaN.
+// fp32 accumulation: hh and the cross terms in separate accumulators).  RANGE as there: |x|, |w| < 65520, beyond: NaN.
 // Stride 1 or 2, any dilation (a tap is an address).  C_in (physical) % 32 == 0, C_out % 16 == 0.
 #include "pwc_common.h"
 

@@ -23,7 +23,7 @@
 //              the LDS (one fp32 addition of two finished sums, fixed order: launches repeat bitwise).  The operand image of 8 rows
 //              would not fit beside 72 KB of weights.
 // Arithmetic and RANGE of conv3x3_h2.hip: x = h + 2^-11 m' per operand, hh and cross terms in separate fp32 accumulators, combined
-// once; |x| >= 65504 gives NaN outputs (PWC_STATUS_NONFINITE at the end of the forward).
+// once; |x| >= 65520 gives NaN outputs (PWC_STATUS_NONFINITE at the end of the forward).
 #include "pwc_common.h"
 
 typedef float w32_f32x16 __attribute__((ext_vector_type(16)));

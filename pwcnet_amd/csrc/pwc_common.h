@@ -99,7 +99,8 @@ __device__ __forceinline__ int pwc_xcd_remap(int b, int nblocks) {
 // m' out of fp16's subnormals).  Two values in four vector instructions: v_cvt_pk_f16_f32, v_pk_mul_f32 (x 2^11 of both) and
 // one mixed-precision FMA per value that reads the fp16 half in place and writes its half of the pair -- the same values as
 //   h = (_Float16)x;  m' = (_Float16)fmaf((float)h, -2048.f, x * 2048.f);
-// which the compiler turns into seven.  |x| >= 65504 gives h = inf and a NaN m': the range condition of these kernels.
+// which the compiler turns into seven.  |x| >= 65520 rounds h to inf (m' is then -inf / NaN): the range condition of these
+// kernels; [65504, 65520) still rounds h to 65504 with a finite m' (< 2^15) and stays exact (tests/test_gpu_forward_f64.py).
 __device__ __forceinline__ void pwc_split2(const float x0, const float x1, unsigned& h_pair, unsigned& m_pair) {
     const f32x2 xs = {x0, x1};
     const pwc_f16x2 h2 = __builtin_convertvector(xs, pwc_f16x2);

@@ -122,8 +122,8 @@ class PWCDCNet(object):
             mod.f16x2 = bool(f16x2)
             mod.status = None
             mod.track_max = False
-        # F16-pipe kernels (f16x2) compute with operands split into fp16 pairs: exact to 22 bits, but only below 65504 in
-        # magnitude -- beyond it they produce NaN, NaN survives every later layer, and the forward's last launch (the x4
+        # F16-pipe kernels (f16x2) compute with operands split into fp16 pairs: exact to 22 bits, but only in fp16's range
+        # (the convolutions stay exact up to 65520, tests/test_gpu_forward_f64.py) -- from 65520 on they produce NaN, NaN survives every later layer, and the forward's last launch (the x4
         # upsampling of model.py:127) sets PWC_STATUS_NONFINITE in `status` (two uint32 in device memory; include/pwc_hip.h)
         # when it writes a value that is not finite.  The reference is plain fp32 (nothing bounds its activations; test.py:31
         # only divides the frames by 255), so a flagged forward is REPEATED on the fp32 kernels into the very tensors it
@@ -235,6 +235,13 @@ class PWCDCNet(object):
                     and images_0.is_cuda and not torch.cuda.is_current_stream_capturing())
         if checking:
             self._examine(wait=False)                       # the previous forward's words, if they have arrived
+            if len(self._pending) >= self._STATUS_SLOTS - 1:
+                # the ring is full (a slot is reused only after its forward has been looked at): drain it BEFORE this forward
+                # is issued.  Examined after it, a flagged older forward would repeat only the forwards already in the ring,
+                # and the zero_() of the words behind this one would wipe its own flag.
+                self._examine(wait=True)
+                checking = self.f16x2                       # (a flag moved the model to the fp32 kernels: nothing to record)
+        if checking:
             self._attach_status(images_0.device)
         out = self._dispatch(images_0, images_1, with_features)
         if checking and self.f16x2:
@@ -269,9 +276,10 @@ class PWCDCNet(object):
             mod.track_max = self.track_max
 
     def _record(self, images_0, images_1, out):
-        """The status words as they stand behind this forward, copied (asynchronously) into a host slot of its own."""
-        if len(self._pending) >= self._STATUS_SLOTS - 1:    # (a slot is reused only after its forward has been looked at)
-            self._examine(wait=True)
+        """The status words as they stand behind this forward, copied (asynchronously) into a host slot of its own.  __call__
+        has drained a full ring before issuing the forward, so the slot is free."""
+        if len(self._pending) >= self._STATUS_SLOTS - 1:
+            raise RuntimeError("PWCDCNet: status ring full at _record (__call__ drains it before the forward is issued)")
         st = self._status[str(images_0.device)]
         words, ring, nxt = st[0], st[1], st[2]
         host = ring[nxt % self._STATUS_SLOTS]
@@ -318,7 +326,7 @@ class PWCDCNet(object):
             self._pending.clear()
             why = []
             if flags & _lib.STATUS_NONFINITE:
-                why.append("the flows are not finite: an activation left fp16's range (|x| >= 65504) in a kernel that splits its "
+                why.append("the flows are not finite: an activation left fp16's range (65504; |x| >= 65520 rounds to inf) in a kernel that splits its "
                            "operands into fp16 pairs (or the frames are not finite)")
             if flags & _lib.STATUS_STREAMK_TIMEOUT:
                 why.append("a stream-K workgroup gave up waiting for a partial sum")

@@ -577,7 +577,7 @@ class _Module:
     winograd4 = True             # ... the big ones among them to the F(4x4,3x3) kernel (pwc_conv3x3_wino4_supported)
     wino_channel_split = True    # F(2x2) launches that leave most workgroup slots empty deal their channel stages to several workgroups
     f16x2 = True                 # the F16-matrix-pipe kernels (conv families w32, t32, sk, h2, c16pair and the correlation's):
-                                 # fp32 operands as exact-to-22-bit fp16 pairs, fp32 accumulation; inputs must stay below 65504
+                                 # fp32 operands as exact-to-22-bit fp16 pairs, fp32 accumulation; inputs must stay below 65520
     f16x2_stream_k = True        # h2: one workgroup per CU and an equal share of the work each where a launch has more tiles than CUs
     small_conv = True            # conv3x3_sk: small launches, the K dimension dealt to the waves of one workgroup
     thin_conv = True             # conv3x3_t32: 16 input channels to 32, the weights stationary in registers

@@ -32,6 +32,17 @@ def gpu(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
+# Bounds of flows_final against the float64 restatement (util.check_float64; pyramid levels against bound / 20), beside the
+# fp32 oracle's 1e-3 px: max(10 x the worst error measured on an MI355X, 1e-5 px), as tests/test_gpu_model.py.
+# Measured (px): see the comment at each entry.
+F64_BOUND_PX = {
+    "config1": 1.9e-5,          # 1.9e-6 (pair 0, pyramid)
+    "config3": 6.4e-5,          # 6.3e-6 (single pair 0, pyramid)
+    "config4": 1.8e-5,          # 1.8e-6 (pair 1)
+    "config4_b8": 2.2e-5,       # 2.1e-6 (pair 7)
+}
+
+
 def make_net(pa, use_dc=False, **kw):
     w = util.model_weights(use_dc)
     net = pa.PWCDCNet(use_dc=use_dc, **kw)
@@ -55,6 +66,8 @@ def test_config1_batch8_448x1024_winograd_pairs_vs_oracle(pa):
         assert err <= 1e-3, (i, err)
         for p, e in zip(pyr, e_pyr):
             assert float(np.abs(p[i:i + 1].cpu().numpy() - e).max()) <= 5e-5
+        util.check_float64(f"config1 pair {i}", got[i:i + 1], [p[i:i + 1] for p in pyr],
+                           util.float64_flows(w, False, im0[i:i + 1], im1[i:i + 1]), F64_BOUND_PX["config1"])
 
 
 def test_config3_dc_448x1024_vs_oracle_and_batch8(pa):
@@ -63,11 +76,12 @@ def test_config3_dc_448x1024_vs_oracle_and_batch8(pa):
     which pairs 0 and 7 must reproduce the single-pair runs."""
     net, w = make_net(pa, True)
     im0, im1 = util.smooth_images(8, 448, 1024, seed=42, shift=(4, 2))
-    one, _ = net(gpu(im0[:1]), gpu(im1[:1]))
+    one, pyr1 = net(gpu(im0[:1]), gpu(im1[:1]))
     e_final, _ = orc.OraclePWCDCNet(w, use_dc=True)(im0[:1], im1[:1])
     err = float(np.abs(one.cpu().numpy() - e_final).max())
     assert err <= 1e-3, err
-    f8, _ = net(gpu(im0), gpu(im1))
+    util.check_float64("config3 single pair 0", one, pyr1, util.float64_flows(w, True, im0[:1], im1[:1]), F64_BOUND_PX["config3"])
+    f8, pyr8 = net(gpu(im0), gpu(im1))
     assert f8.shape == (8, 448, 1024, 2)
     # different batch sizes may pick different tile plans (same arithmetic, other summation order)
     assert float((f8[0:1] - one).abs().max()) <= 2e-4
@@ -75,6 +89,8 @@ def test_config3_dc_448x1024_vs_oracle_and_batch8(pa):
     e7, _ = orc.OraclePWCDCNet(w, use_dc=True)(im0[7:8], im1[7:8])
     err7 = float(np.abs(f8[7:8].cpu().numpy() - e7).max())
     assert err7 <= 1e-3, err7
+    util.check_float64("config3 b8 pair 7", f8[7:8], [p[7:8] for p in pyr8], util.float64_flows(w, True, im0[7:8], im1[7:8]),
+                       F64_BOUND_PX["config3"])
 
 
 def test_config4_960x1920_vs_oracle(pa):
@@ -89,6 +105,8 @@ def test_config4_960x1920_vs_oracle(pa):
     assert err <= 1e-3, err
     for p, e in zip(pyr, e_pyr):
         assert float(np.abs(p[1:2].cpu().numpy() - e).max()) <= 5e-5
+    util.check_float64("config4 pair 1", final[1:2], [p[1:2] for p in pyr], util.float64_flows(w, False, im0[1:2], im1[1:2]),
+                       F64_BOUND_PX["config4"])
 
 
 def test_config4_per_gpu_batch8_960x1920_pairs_vs_oracle(pa):
@@ -106,6 +124,8 @@ def test_config4_per_gpu_batch8_960x1920_pairs_vs_oracle(pa):
         assert err <= 1e-3, (i, err)
         for p, e in zip(pyr, e_pyr):
             assert float(np.abs(p[i:i + 1].cpu().numpy() - e).max()) <= 5e-5
+        util.check_float64(f"config4_b8 pair {i}", final[i:i + 1], [p[i:i + 1] for p in pyr],
+                           util.float64_flows(w, False, im0[i:i + 1], im1[i:i + 1]), F64_BOUND_PX["config4_b8"])
 
 
 # ------------------------------------------------------------------ output ownership

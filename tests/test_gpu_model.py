@@ -41,6 +41,29 @@ def close(got, exp, rel=1e-5, floor=1e-6):
     assert err <= tol, f"max abs err {err:.3e} > tol {tol:.3e}"
 
 
+# Bounds of flows_final against the float64 restatement (util.check_float64; the pyramid levels, in px / 20, against bound / 20),
+# next to every end-to-end assertion against the fp32 oracle -- whose own error is of the order of the kernels', so that it
+# cannot tell a 1e-5 px defect from a correct forward.  Rule of the training path's float64 tests: max(10 x the worst error
+# measured on an MI355X, 1e-5 px); forwards with flows of 100-400 px (real motion, kernel gain 1.6: the error is amplified
+# through some 60 layers) take 3 x, the forwards being bit-deterministic.  Measured (px): see the comment at each entry.
+F64_BOUND_PX = {
+    "golden_64x128_dc0": 1e-5,                  # 9.2e-7 (10 x is under the floor)
+    "golden_64x128_dc1": 3.8e-5,                # 3.8e-6
+    "b2_128x192_features": 1.1e-5,              # 1.1e-6 (pyramid)
+    "b1_448x1024": 1.8e-5,                      # 1.7e-6
+    "large_flows_gain1.35_dc0": 6.4e-5,         # 6.3e-6 (11 px flows)
+    "large_flows_gain1.6_dc0": 6.8e-4,          # 2.2e-4 (pyramid; 298 px flows: 3 x)
+    "large_flows_gain1.25_dc1": 1.1e-4,         # 1.1e-5 (4.4 px flows)
+    "f4x4_b8_448x1024": 1.1e-4,                 # 1.1e-5 (pair 7; 9 px flows)
+    "f16x2_b8_448x1024": 1.1e-4,                # 1.1e-5 (pair 7; the same forward as the F(4x4) test's)
+    "real_motion_100px_dc0": 1.8e-4,            # 5.8e-5 (pyramid; 135 px: 3 x)
+    "real_motion_100px_dc1": 4.0e-4,            # 1.3e-4 (pyramid; 120 px: 3 x)
+    "real_motion_300px_dc0": 5.2e-4,            # 1.7e-4 (401 px: 3 x; the fp32 oracle is off by 6.6e-4)
+    "real_motion_300px_dc1": 9.8e-4,            # 3.3e-4 (367 px: 3 x; the fp32 oracle is off by 1.4e-3)
+}
+F64_FEATURES_REL = 4e-6      # pyramid_0 of with_features=True, max error over max |feature| per level: 4.0e-7 (64x96 level)
+
+
 def make_net(pa, use_dc=False, **kw):
     w = util.model_weights(use_dc)
     net = pa.PWCDCNet(use_dc=use_dc, **kw)
@@ -124,7 +147,7 @@ def test_lazy_variable_creation_names_and_count(pa):
 @pytest.mark.parametrize("use_dc", [False, True])
 def test_e2e_golden_64x128(pa, use_dc, golden_dir):
     g = np.load(os.path.join(golden_dir, f"e2e_64x128_dc{int(use_dc)}.npz"))
-    net, _ = make_net(pa, use_dc)
+    net, w = make_net(pa, use_dc)
     final, pyr = net(gpu(g["images_0"]), gpu(g["images_1"]))
     assert final.shape == (1, 64, 128, 2) and len(pyr) == 5
     err = float(np.abs(final.cpu().numpy() - g["flows_final"]).max())
@@ -132,6 +155,8 @@ def test_e2e_golden_64x128(pa, use_dc, golden_dir):
     for l, p in enumerate(pyr):
         assert float(np.abs(p.cpu().numpy() - g[f"flows_{l}"]).max()) <= 5e-5
     assert float(np.abs(g["flows_final"]).max()) > 0.5      # the comparison is not vacuous
+    tag = f"golden_64x128_dc{int(use_dc)}"
+    util.check_float64(tag, final, pyr, util.float64_flows(w, use_dc, g["images_0"], g["images_1"]), F64_BOUND_PX[tag])
 
 
 def test_e2e_batch_and_features_vs_oracle(pa):
@@ -146,6 +171,16 @@ def test_e2e_batch_and_features_vs_oracle(pa):
         close(f, e)
     # EPE (reference losses.py:11-13) between HIP and oracle flows
     assert orc.epe(e_final, final.cpu().numpy()) <= 1e-4
+    util.check_float64("b2_128x192_features", final, pyr, util.float64_flows(w, False, im0, im1), F64_BOUND_PX["b2_128x192_features"])
+    from oracle import torch_ref as TR
+    w64 = {k: torch.from_numpy(v).double() for k, v in w.items()}
+    with torch.no_grad():
+        f64 = TR.TorchPWCDCNet(w64).extractor(torch.from_numpy(im0).double())
+    for f, e in zip(feats, f64):                            # the pyramid handed out, per level, relative to its largest value
+        e = e.numpy()
+        rel = float(np.abs(f.cpu().numpy() - e).max()) / float(np.abs(e).max())
+        print(f"float64 features {tuple(e.shape)}: max err / max |f| = {rel:.2e}")
+        assert rel <= F64_FEATURES_REL, rel
 
 
 def test_e2e_unfused_warp_and_nearest_variants(pa):
@@ -184,6 +219,7 @@ def test_e2e_full_size_448x1024_vs_oracle(pa):
     assert err <= 1e-3, err
     assert final.shape == (1, 448, 1024, 2)
     assert [tuple(p.shape[1:3]) for p in pyr] == [(7, 16), (14, 32), (28, 64), (56, 128), (112, 256)]
+    util.check_float64("b1_448x1024", final, pyr, util.float64_flows(w, False, im0, im1), F64_BOUND_PX["b1_448x1024"])
 
 
 def test_e2e_batch8_matches_single_pair(pa):
@@ -455,6 +491,8 @@ def test_e2e_large_flows_vs_oracle(pa, gain, use_dc):
     print(f"gain {gain} use_dc {use_dc}: max |flow| {mag:.3f} px, max abs err {err:.3e}")
     assert np.isfinite(mag) and mag >= 2.0, mag
     assert err <= 1e-3
+    tag = f"large_flows_gain{gain}_dc{int(use_dc)}"
+    util.check_float64(tag, final, pyr, util.float64_flows(w, use_dc, im0, im1), F64_BOUND_PX[tag])
 
 
 def test_f4x4_layers_leave_the_flows_where_f2x2_puts_them(pa):
@@ -480,6 +518,9 @@ def test_f4x4_layers_leave_the_flows_where_f2x2_puts_them(pa):
     err = float(np.abs(a[:1].cpu().numpy() - e_final).max())
     print(f"F(4x4) layers: max |flow| {mag:.2f} px, vs F(2x2) {float((a - b).abs().max()):.2e}, vs oracle {err:.2e}")
     assert err <= 1e-3 / 3, err
+    for i in (0, 7):
+        util.check_float64(f"f4x4_b8_448x1024 pair {i}", a[i:i + 1], [p[i:i + 1] for p in pyr_a],
+                           util.float64_flows(w, False, im0[i:i + 1], im1[i:i + 1]), F64_BOUND_PX["f4x4_b8_448x1024"])
 
 
 def test_f16x2_layers_leave_the_flows_where_fp32_puts_them(pa):
@@ -497,7 +538,7 @@ def test_f16x2_layers_leave_the_flows_where_fp32_puts_them(pa):
     from pwcnet_amd.profiler import OpTimer
     t = OpTimer()
     with t:
-        a, _ = net_h(gpu(im0), gpu(im1))
+        a, pyr_h = net_h(gpu(im0), gpu(im1))
     names = sorted(t.summary())
     assert any(k.startswith("conv3x3_h2") for k in names), names
     a = a.clone()
@@ -515,6 +556,9 @@ def test_f16x2_layers_leave_the_flows_where_fp32_puts_them(pa):
     err_f = float(np.abs(b[:1].cpu().numpy() - e_final).max())
     print(f"f16x2 layers: max |flow| {mag:.2f} px, vs fp32 kernels {float((a - b).abs().max()):.2e}, vs oracle {err_h:.2e} (fp32 kernels: {err_f:.2e})")
     assert err_h <= 1e-3 / 3 and err_h <= 2.0 * err_f + 1e-6, (err_h, err_f)
+    for i in (0, 7):
+        util.check_float64(f"f16x2_b8_448x1024 pair {i}", a[i:i + 1], [p[i:i + 1] for p in pyr_h],
+                           util.float64_flows(w, False, im0[i:i + 1], im1[i:i + 1]), F64_BOUND_PX["f16x2_b8_448x1024"])
 
 
 @pytest.mark.parametrize("mode,streams", [("sync", 1), ("lazy", 1), ("lazy", None)])
@@ -672,16 +716,6 @@ def motion_weights(use_dc, head_bias, gain=1.3):
     return w
 
 
-def float64_forward(w, use_dc, im0, im1):
-    """flows_final of the float64 restatement (oracle/torch_ref.py, pinned against the C oracle in tests/test_oracle.py): the
-    yardstick for what an fp32 forward of this depth can hold at a given flow magnitude."""
-    from oracle import torch_ref as TR
-    w64 = {k: torch.from_numpy(v).to(torch.float64) for k, v in w.items()}
-    with torch.no_grad():
-        out = TR.TorchPWCDCNet(w64, use_dc=use_dc)(torch.from_numpy(im0).double(), torch.from_numpy(im1).double())
-    return out[0].numpy()
-
-
 @pytest.mark.parametrize("head_bias,floor_px,use_dc", [((5.2, -3.1), 100.0, False), ((15.5, -9.0), 300.0, False),
                                                         ((5.2, -3.1), 100.0, True), ((15.5, -9.0), 300.0, True)])
 def test_e2e_real_motion_vs_oracle(pa, head_bias, floor_px, use_dc):
@@ -712,19 +746,23 @@ def test_e2e_real_motion_vs_oracle(pa, head_bias, floor_px, use_dc):
     msg = (f"real motion use_dc={use_dc}: oracle max |flow| {mag:.1f} px; HIP vs fp32 oracle {err:.3e} px = {err / 1e-3:.2f} of the "
            f"1e-3 budget (the same forward on the fp32 kernels: {err32:.3e})")
     assert np.isfinite(mag) and mag >= floor_px, mag
+    tag = f"real_motion_{int(floor_px)}px_dc{int(use_dc)}"
     if floor_px <= 100.0:
         print(msg)
         assert err <= 1e-3, err
         for g, e in zip(pyr, e_pyr):
             assert float(np.abs(g.cpu().numpy() - e).max()) <= 1e-3 / 20.0
+        util.check_float64(tag, final, pyr, util.float64_flows(w, use_dc, im0, im1), F64_BOUND_PX[tag])
         return
-    truth = float64_forward(w, use_dc, im0, im1)
+    ref = util.float64_flows(w, use_dc, im0, im1)
+    truth = ref[0]
     e_h = float(np.abs(got - truth).max())
     e_o = float(np.abs(e_final - truth).max())
     e_32 = float(np.abs(final32.cpu().numpy() - truth).max())
     print(msg + f"; vs float64: HIP {e_h:.3e}, fp32 oracle {e_o:.3e}, HIP on fp32 kernels {e_32:.3e}")
     assert e_h <= max(1e-3, 1.5 * e_o), (e_h, e_o)
     assert err <= 2.5e-3, err
+    util.check_float64(tag, final, pyr, ref, F64_BOUND_PX[tag])
 
 
 def test_activations_near_the_fp16_range_stay_on_the_fast_kernels(pa):
@@ -793,6 +831,68 @@ def test_lazy_range_check_maps_each_flag_to_its_forward(pa):
     for i in (2, 3):
         assert torch.equal(outs[i], want[i]), i                        # repeated on the fp32 kernels
     assert bool(torch.isnan(outs[4]).all())                            # inputs modified since: invalidated, not recomputed
+
+
+@pytest.mark.parametrize("culprit", ["older", "ring_filler"])
+def test_lazy_range_check_with_a_full_status_ring(pa, culprit):
+    """the status ring holds 64 slots; when it is full, a call must look at the pending forwards before it issues
+    its own.  A device-side spin holds the stream, so no status copy lands while the ring fills.  culprit="older": forward 2
+    overflows and in-range forwards follow until the ring is full; every forward from 2 on, the one that found the ring
+    full included, must come back bit-equal to the fp32 kernels' (examined after it was issued, the ring-full forward kept
+    its F16-pipe flows, and the zero_() of the words behind it wiped its own flag).  culprit="ring_filler": the forward that
+    finds the ring full is itself the overflowing one: it must be repeated too, never handed back as NaN with flags = 0."""
+    w = util.model_weights(False)
+    im0, im1 = util.smooth_images(2, 64, 128, seed=37, shift=(2, -1))
+    ref = pa.PWCDCNet(f16x2=False)
+    ref.load_weights(w)
+    net = pa.PWCDCNet(range_check="lazy")
+    net.load_weights(w)
+    slots = net._STATUS_SLOTS
+    assert slots == 64
+    scales = (1.0, 0.5, 2.0, 0.25)
+    frames = {s: (gpu(im0 * s), gpu(im1 * s)) for s in scales + (1e7,)}
+    want = {s: ref(*frames[s])[0].clone() for s in frames}
+    assert bool(torch.isfinite(want[1e7]).all())
+    net(*frames[1.0])                                                   # records the plan of the shape
+    assert net.status()["flags"] == 0
+    torch.cuda.synchronize()
+    seen = []                                                           # (wait, pending forwards) of every _examine
+    examine = net._examine
+
+    def spy(wait):
+        seen.append((wait, len(net._pending)))
+        return examine(wait)
+    net._examine = spy
+    from pwcnet_amd import _lib
+    issued, outs, full_at = [], [], None
+    with pytest.warns(RuntimeWarning, match="fp16's range"):
+        for i in range(slots + 8):
+            if i == 2:
+                # a device-side spin (~1 s) in front of forward 2: no status copy behind it lands while the ring fills
+                _lib.check(_lib.lib().pwc_device_spin(100_000_000, _lib.current_stream()))
+            examine(False)                                              # (what the call does first)
+            ring_full = len(net._pending) >= slots - 1
+            if culprit == "older":
+                s = 1e7 if i == 2 else scales[i % len(scales)]
+            else:
+                s = 1e7 if ring_full else scales[i % len(scales)]
+            n_seen = len(seen)
+            issued.append(s)
+            outs.append(net(*frames[s])[0])
+            if ring_full:
+                full_at = i
+                assert any(wt and n >= slots - 1 for wt, n in seen[n_seen:]), seen[n_seen:]   # the ring-full path ran
+                break
+        rep = net.status()
+    assert full_at is not None, f"the ring never filled: {len(net._pending)} forwards pending after {len(outs)} calls"
+    assert full_at >= slots - 1
+    assert rep["f16x2"] is False and net.status()["flags"] == 0
+    torch.cuda.synchronize()
+    first = 2 if culprit == "older" else full_at
+    for i in range(first, full_at + 1):
+        assert torch.equal(outs[i], want[issued[i]]), (i, full_at, float((outs[i] - want[issued[i]]).abs().max()))
+    for i in range(first):
+        assert float((outs[i] - want[issued[i]]).abs().max()) <= 1e-4, i   # (in range, before the culprit: F16-pipe flows)
 
 
 @pytest.mark.parametrize("streams", [1, 2])

@@ -45,3 +45,32 @@ def flow_field(n, h, w, seed=3, sigma=3.0, outliers=True):
         m = rng.uniform(size=(n, h, w)) < 0.02
         f[m] = rng.choice([-50.0, 50.0, -7.0, 3.0, 0.0], size=(int(m.sum()), 2)).astype(np.float32)
     return f
+
+
+def float64_flows(w, use_dc, im0, im1):
+    """(flows_final, flows_pyramid) of the float64 restatement (oracle/torch_ref.py, pinned against the C oracle in
+    tests/test_oracle.py) on numpy frames: the yardstick for the fp32 forwards, whose own error the fp32 oracle shares."""
+    import torch
+    from oracle import torch_ref as TR
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    w64 = {k: torch.from_numpy(v).to(torch.float64) for k, v in w.items()}
+    with torch.no_grad():
+        final, pyr = TR.TorchPWCDCNet(w64, use_dc=use_dc)(torch.from_numpy(im0).double(), torch.from_numpy(im1).double())
+    return final.numpy(), [p.numpy() for p in pyr]
+
+
+def check_float64(tag, got_final, got_pyr, ref, bound_px):
+    """Max abs error of a forward's flows_final (px) and of every pyramid level (px / 20: bound_px / 20) against
+    float64_flows' `ref`; printed, then asserted.  Returns the flows_final error."""
+    def as_np(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else t
+    final = as_np(got_final)
+    assert final.shape == ref[0].shape, (final.shape, ref[0].shape)
+    err = float(np.abs(final - ref[0]).max())
+    err_p = [float(np.abs(as_np(p) - e).max()) for p, e in zip(got_pyr, ref[1])]
+    assert len(err_p) == len(ref[1])
+    print(f"float64 {tag}: flows_final max |flow| {float(np.abs(ref[0]).max()):.3f} px, err {err:.3e} px (bound {bound_px:.1e}); "
+          f"pyramid err x20 {20.0 * max(err_p):.3e} px")
+    assert err <= bound_px, (tag, err, bound_px)
+    assert max(err_p) <= bound_px / 20.0, (tag, err_p, bound_px)
+    return err
