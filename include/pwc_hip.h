@@ -559,6 +559,13 @@ size_t pwc_conv3x3_wgrad_workspace_floats(int N, int H, int W, int Cin_phys, int
 int pwc_conv3x3_wgrad_f32(const float* x, int x_cs, const float* dy, int dy_cs, const int32_t* cin_map, int Cin,
                           int Cin_phys, int Cout, float* dw_hwio, int accumulate, int N, int H, int W, int stride,
                           int dilation, float* workspace, size_t workspace_floats, pwc_stream_t stream);
+/* Data gradient of tf.layers.Conv2D(...,(3,3),(2,2),'same') for an input of 1..4 channels (the images of the first
+ * extractor conv): dx (+)= d conv / d x . dy, w_hwio = the forward kernel (3,3,Cx,Cy), dx of size H x W (both even),
+ * dy of size H/2 x W/2.  One pass over dy, no zero-stuffed map.  Cy % 4 == 0, dy 16-byte aligned with dy_cs % 4 == 0,
+ * w_hwio 16-byte aligned (PWC_EALIGN); odd H or W, Cx outside 1..4, Cy % 4 != 0: PWC_EUNSUPPORTED; null pointers,
+ * non-positive sizes, channel strides below the channel counts: PWC_EINVAL.  Every check precedes the launch. */
+int pwc_conv3x3_dgrad_s2_narrow_f32(const float* dy, int dy_cs, const float* w_hwio, float* dx, int dx_cs, int N, int H,
+                                    int W, int Cx, int Cy, int accumulate, pwc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,7 @@ SIGNATURES = {
     "pwc_conv3x3_wgrad_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "pwc_flow_norm_workspace_floats": (_sz, [_i, _i, _i]),
     "pwc_flow_norm_sums_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp]),
+    "pwc_conv3x3_dgrad_s2_narrow_f32": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 if HARNESS:

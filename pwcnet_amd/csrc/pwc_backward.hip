@@ -16,6 +16,7 @@
 //   pwc_cost_volume_grad        d/df0 and d/df1w of the cost volume modules.py:158-204
 //   pwc_flow_norm_grad_f32      gradient of L1loss / L2loss terms  losses.py:4-8,20-29
 //   pwc_adam_step_f32           tf.train.AdamOptimizer update + the weights' L2 term  train.py:75,90
+//   pwc_conv3x3_dgrad_s2_narrow_f32   data gradient of a stride-2 conv with 1..4 input channels (the images)
 #include "pwc_common.h"
 #include <cstdint>
 
@@ -666,5 +667,122 @@ extern "C" int pwc_adam_step_f32(float* params, const float* grads, float* m, fl
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, n, lr_t,
                        beta1, beta2, eps, l2_gamma, grad_scale);
+    return pwc_launch_status();
+}
+
+// ------------------------------------------------------------------ stride-2 data gradient, narrow input
+// TF 'SAME' stride 2 on an even size pads bottom / right only: forward output o reads input 2o + t, t = 0..2.  Its data
+// gradient dx[i, j, ci] = sum over (t, s) with i - t, j - s even of dy[(i - t) / 2, (j - s) / 2, :] . w[t, s, ci, :].
+// One lane per 2x2 quad of dx at rows 2a, 2a+1 and columns 2b, 2b+1; the quad needs the dy pixels at rows a-1, a and
+// columns b-1, b and 9 taps across its four pixels:
+//   dx(2a,   2b)   = dy(a, b) w00 + dy(a, b-1) w02 + dy(a-1, b) w20 + dy(a-1, b-1) w22
+//   dx(2a,   2b+1) = dy(a, b) w01 + dy(a-1, b) w21
+//   dx(2a+1, 2b)   = dy(a, b) w10 + dy(a, b-1) w12
+//   dx(2a+1, 2b+1) = dy(a, b) w11
+// (row / column -1 is outside the image: zero).  dy is read with 16-byte loads (the neighbouring quads' re-reads hit the
+// caches: HBM sees dy once); the weight index is uniform across the wave, so the weights come in through the scalar
+// cache and feed the FMAs as scalar operands.  The dot products over Cy run as fp32 pairs (v_pk_fma_f32) and are folded
+// at the end.
+struct DgradS2Args {
+    const float* dy;
+    const float* w;        // (3, 3, Cx, Cy): the forward kernel
+    float* dx;
+    int dy_cs, dx_cs;
+    int N, Ho, Wo, Cy;     // dy grid (dx is 2Ho x 2Wo)
+    int accumulate;
+};
+
+// CY: Cy as a compile-time constant (the extractor's 16: the loop unrolls and every dy load is in flight at once), 0: a.Cy
+template <int CX, int CY>
+__global__ __launch_bounds__(256) void conv3x3_dgrad_s2_narrow_kernel(const DgradS2Args a) {
+    const long q = blockIdx.x * 256L + threadIdx.x;
+    const long total = (long)a.N * a.Ho * a.Wo;
+    if (q >= total) return;
+    const int b = (int)(q % a.Wo);
+    const long r = q / a.Wo;
+    const int ar = (int)(r % a.Ho);
+    const int n = (int)(r / a.Ho);
+    const bool up = ar > 0, left = b > 0;
+    const long p11 = ((long)n * a.Ho + ar) * a.Wo + b;          // dy(a, b); the others are -1 / -Wo / -Wo-1 pixels away
+    const float* d11 = a.dy + p11 * a.dy_cs;
+    const float* d10 = d11 - a.dy_cs;
+    const float* d01 = d11 - (long)a.Wo * a.dy_cs;
+    const float* d00 = d01 - a.dy_cs;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    // acc[pixel][ci], pixel = 2 * (row in quad) + (column in quad), pair-wise partial sums
+    f32x2 acc[4][CX];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int c = 0; c < CX; ++c) acc[p][c] = f32x2{0.f, 0.f};
+    const int Cy = CY ? CY : a.Cy;
+#pragma unroll
+    for (int co = 0; co < Cy; co += 4) {
+        const f32x4 v11 = *reinterpret_cast<const f32x4*>(d11 + co);
+        const f32x4 v10 = left ? *reinterpret_cast<const f32x4*>(d10 + co) : zero;
+        const f32x4 v01 = up ? *reinterpret_cast<const f32x4*>(d01 + co) : zero;
+        const f32x4 v00 = (up && left) ? *reinterpret_cast<const f32x4*>(d00 + co) : zero;
+#pragma unroll
+        for (int c = 0; c < CX; ++c) {
+            // w[t][s][c][co..co+3]
+            auto W4 = [&](int t, int s) { return *reinterpret_cast<const f32x4*>(a.w + ((long)(t * 3 + s) * CX + c) * Cy + co); };
+            auto fma4 = [](f32x2 acc2, f32x4 d, f32x4 w) {
+                acc2 += f32x2{d[0], d[1]} * f32x2{w[0], w[1]};
+                acc2 += f32x2{d[2], d[3]} * f32x2{w[2], w[3]};
+                return acc2;
+            };
+            acc[0][c] = fma4(acc[0][c], v11, W4(0, 0));
+            acc[0][c] = fma4(acc[0][c], v10, W4(0, 2));
+            acc[0][c] = fma4(acc[0][c], v01, W4(2, 0));
+            acc[0][c] = fma4(acc[0][c], v00, W4(2, 2));
+            acc[1][c] = fma4(acc[1][c], v11, W4(0, 1));
+            acc[1][c] = fma4(acc[1][c], v01, W4(2, 1));
+            acc[2][c] = fma4(acc[2][c], v11, W4(1, 0));
+            acc[2][c] = fma4(acc[2][c], v10, W4(1, 2));
+            acc[3][c] = fma4(acc[3][c], v11, W4(1, 1));
+        }
+    }
+    // two runs of 2 * CX floats (contiguous when dx_cs == CX)
+    const int H = 2 * a.Ho, W = 2 * a.Wo;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        float* d = a.dx + (((long)n * H + 2 * ar + (p >> 1)) * W + 2 * b + (p & 1)) * a.dx_cs;
+#pragma unroll
+        for (int c = 0; c < CX; ++c) {
+            const float v = acc[p][c][0] + acc[p][c][1];
+            d[c] = a.accumulate ? d[c] + v : v;
+        }
+    }
+}
+
+extern "C" int pwc_conv3x3_dgrad_s2_narrow_f32(const float* dy, int dy_cs, const float* w_hwio, float* dx, int dx_cs, int N,
+                                               int H, int W, int Cx, int Cy, int accumulate, pwc_stream_t stream) {
+    if (!dy || !w_hwio || !dx || N <= 0 || H <= 0 || W <= 0 || Cx <= 0 || Cy <= 0 || dy_cs < Cy || dx_cs < Cx)
+        return PWC_EINVAL;
+    if ((H & 1) || (W & 1) || Cx > 4 || (Cy & 3)) return PWC_EUNSUPPORTED;
+    if ((dy_cs & 3) || !pwc_aligned16(dy) || !pwc_aligned16(w_hwio)) return PWC_EALIGN;
+    const long quads = (long)N * (H / 2) * (W / 2);
+    const long blocks = (quads + 255) / 256;
+    if ((long)N * H * W * dx_cs >= (1L << 40) || blocks > 0x7fffffffL) return PWC_ERANGE;
+    DgradS2Args a;
+    a.dy = dy; a.w = w_hwio; a.dx = dx; a.dy_cs = dy_cs; a.dx_cs = dx_cs;
+    a.N = N; a.Ho = H / 2; a.Wo = W / 2; a.Cy = Cy; a.accumulate = accumulate;
+    const dim3 g((unsigned)blocks), blk(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (Cy == 16) {
+        switch (Cx) {
+            case 1: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<1, 16>), g, blk, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<2, 16>), g, blk, 0, st, a); break;
+            case 3: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<3, 16>), g, blk, 0, st, a); break;
+            default: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<4, 16>), g, blk, 0, st, a); break;
+        }
+    } else {
+        switch (Cx) {
+            case 1: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<1, 0>), g, blk, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<2, 0>), g, blk, 0, st, a); break;
+            case 3: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<3, 0>), g, blk, 0, st, a); break;
+            default: hipLaunchKernelGGL((conv3x3_dgrad_s2_narrow_kernel<4, 0>), g, blk, 0, st, a); break;
+        }
+    }
     return pwc_launch_status();
 }

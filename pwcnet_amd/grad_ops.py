@@ -231,3 +231,13 @@ def conv3x3_dgrad(dy, w_hwio_phys, dx, stride=1, dilation=1, keep=None, dy_tenso
     if keep is not None:
         keep.append(up)
     return tmp + [up]
+
+
+def conv3x3_dgrad_s2_narrow(dy, w_hwio, dx, accumulate=False):
+    """dx (+)= gradient of conv3x3_same(x, w_hwio, stride=2) w.r.t. x for a narrow x (1..4 channels, even H and W): one pass
+    over dy on pwc_conv3x3_dgrad_s2_narrow_f32, no zero-stuffed map.  dy, dx: Views; w_hwio: the forward kernel
+    (3, 3, dx.C, dy.C), contiguous float32 on the device."""
+    assert tuple(w_hwio.shape) == (3, 3, dx.C, dy.C) and w_hwio.is_contiguous(), (tuple(w_hwio.shape), dx, dy)
+    assert (dy.N, 2 * dy.H, 2 * dy.W) == (dx.N, dx.H, dx.W), (dy, dx)
+    _lib.check(_L().pwc_conv3x3_dgrad_s2_narrow_f32(_p(dy.ptr), dy.cs, _p(w_hwio.data_ptr()), _p(dx.ptr), dx.cs, dx.N, dx.H,
+                                                    dx.W, dx.C, dy.C, 1 if accumulate else 0, _s()), "conv3x3_dgrad_s2_narrow")
