@@ -36,7 +36,7 @@
 // biased, activated, zeroed outside the image, split and written into the operand image the pair reads.  165 -> 123 us for the
 // three layers at 16 x 448 x 1024 (profiles/r04_exp_c16pair.txt): the 117 MB level-1 input of the pair is never written or read.
 // The stride-2 stage costs 42 us of the 123 and is VALU ISSUE (2 waves per SIMD x 6 tiles x 4 cycles an instruction; about 100
-// vector instructions per 16 pixels with the compiler's 3.5-instruction operand split, 131 us; c16_split2 made it 123).  Running it for
+// vector instructions per 16 pixels with the compiler's 3.5-instruction operand split, 131 us; pwc_split2 made it 123).  Running it for
 // tile t + 1 BESIDE layer 2 of tile t (waves 0-3 one order, waves 4-7 the other, two barriers per tile) changed nothing
 // (130.8 us): every wave still executes both in series and neither saturates a unit the other needs.  Delaying waves 4-7 by
 // 256 - 900 cycles behind every barrier (so that one wave of a SIMD reads while the other multiplies) ADDS the delay: 126 -> 126 /
@@ -47,37 +47,6 @@
 #pragma once
 #include "pwc_common.h"
 #include <type_traits>
-
-typedef _Float16 c16_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 c16_f16x4 __attribute__((ext_vector_type(4)));
-
-typedef _Float16 c16_f16x2 __attribute__((ext_vector_type(2)));
-
-// The operand split of TWO fp32 values in four vector instructions: h = fp16(x) of both (v_cvt_pk_f16_f32), x 2^11 of both
-// (v_pk_mul_f32), and m' = fp16(fma(h, -2^11, x 2^11)) = fp16((x - h) 2^11) per value with the fp16 half read in place and
-// the result written to its half of the pair (v_fma_mixlo / mixhi_f16): the same values as the scalar form
-//   h = (_Float16)x;  m' = (_Float16)fmaf((float)h, -2048.f, x * 2048.f);
-// which the compiler turns into seven.
-__device__ __forceinline__ void c16_split2(const float x0, const float x1, unsigned& h_pair, unsigned& m_pair) {
-    const f32x2 xs = {x0, x1};
-    const c16_f16x2 h2 = __builtin_convertvector(xs, c16_f16x2);
-    const f32x2 xm = xs * 2048.f;
-    const unsigned hp = __builtin_bit_cast(unsigned, h2);
-    const float neg = -2048.f;
-    unsigned mp;
-    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(mp) : "v"(hp), "s"(neg), "v"(xm[0]));
-    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(mp) : "v"(hp), "s"(neg), "v"(xm[1]));
-    h_pair = hp; m_pair = mp;
-}
-__device__ __forceinline__ void c16_split4(const float x0, const float x1, const float x2, const float x3, c16_f16x4& h, c16_f16x4& m) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    u32x2 hp, mp;
-    unsigned a, b;
-    c16_split2(x0, x1, a, b); hp[0] = a; mp[0] = b;
-    c16_split2(x2, x3, a, b); hp[1] = a; mp[1] = b;
-    h = __builtin_bit_cast(c16_f16x4, hp);
-    m = __builtin_bit_cast(c16_f16x4, mp);
-}
 
 struct C16Args {
     const float* x;
@@ -124,17 +93,17 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
     const int n16 = lane & 15, kq = lane >> 4;
 
     // ---- the 28 weight operands and the lane's four biases of each layer
-    c16_f16x8 A1[14], A2[14];
+    pwc_f16x8 A1[14], A2[14];
 #pragma unroll
     for (int m = 0; m < 14; ++m) {
-        A1[m] = reinterpret_cast<const c16_f16x8*>(a.wp)[m * 64 + lane];
-        A2[m] = reinterpret_cast<const c16_f16x8*>(a.wp)[(14 + m) * 64 + lane];
+        A1[m] = reinterpret_cast<const pwc_f16x8*>(a.wp)[m * 64 + lane];
+        A2[m] = reinterpret_cast<const pwc_f16x8*>(a.wp)[(14 + m) * 64 + lane];
     }
-    c16_f16x8 A0h = {}, A0m = {};
+    pwc_f16x8 A0h = {}, A0m = {};
     f32x4 b0v = {0.f, 0.f, 0.f, 0.f};
     if (FIRST) {
-        A0h = reinterpret_cast<const c16_f16x8*>(a.wp)[28 * 64 + lane];
-        A0m = reinterpret_cast<const c16_f16x8*>(a.wp)[29 * 64 + lane];
+        A0h = reinterpret_cast<const pwc_f16x8*>(a.wp)[28 * 64 + lane];
+        A0m = reinterpret_cast<const pwc_f16x8*>(a.wp)[29 * 64 + lane];
         b0v = *reinterpret_cast<const f32x4*>(a.b0 + 4 * kq);
     }
     const f32x4 b1v = *reinterpret_cast<const f32x4*>(a.b1 + 4 * kq);
@@ -200,16 +169,15 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
             }
         }
     };
-#define C16_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // one 16-pixel tile of a layer: 14 fragment reads, 14 matrix instructions; returns hh + 2^-11 cross
-    auto mtile = [&](const char* img, int p0, const c16_f16x8* A, const f32x4 bias) -> f32x4 {
-        c16_f16x8 B[14];
+    auto mtile = [&](const char* img, int p0, const pwc_f16x8* A, const f32x4 bias) -> f32x4 {
+        pwc_f16x8 B[14];
         const char* base = img + p0 * 16;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) B[j] = *reinterpret_cast<const c16_f16x8*>(base + hoff[j]);
+        for (int j = 0; j < 5; ++j) B[j] = *reinterpret_cast<const pwc_f16x8*>(base + hoff[j]);
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) B[5 + tp] = *reinterpret_cast<const c16_f16x8*>(base + coff + tap_shift(tp) * 16);
+        for (int tp = 0; tp < 9; ++tp) B[5 + tp] = *reinterpret_cast<const pwc_f16x8*>(base + coff + tap_shift(tp) * 16);
         f32x4 hh = bias, cx = {0.f, 0.f, 0.f, 0.f};        // (the bias rides in the accumulator)
 #pragma unroll
         for (int m = 0; m < 14; ++m) {
@@ -240,7 +208,7 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
         const int y0 = by * 16, x0 = bx * 32;
         const bool interior = y0 >= 2 && y0 + 18 <= a.H && x0 >= 2 && x0 + 34 <= a.W;      // no patch pixel outside the image
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        C16_BAR();                                   // the patch has landed; everybody is done with the images of the previous tile
+        pwc_lds_barrier_raw();                       // the patch has landed; everybody is done with the images of the previous tile
         if (FIRST) {
             // ---- the stride-2 convolution of the raw patch: 45 tiles of 16 patch pixels, K = 27 of 32 (quarter dy < 3: the first
             // 8 of the 9 floats of raw row 2 pr + dy at columns 2 pc .. 2 pc + 2; quarter 3: the ninth float of the three rows),
@@ -278,11 +246,11 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
                 f32x4 hh[3], cx[3];
 #pragma unroll
                 for (int u = 0; u < 3; ++u) {
-                    c16_f16x4 hl, ml, hu, mu;
-                    c16_split4(v[u][0], v[u][1], v[u][2], v[u][3], hl, ml);
-                    c16_split4(v[u][4], v[u][5], v[u][6], v[u][7], hu, mu);
-                    const c16_f16x8 Bh = __builtin_shufflevector(hl, hu, 0, 1, 2, 3, 4, 5, 6, 7);
-                    const c16_f16x8 Bm = __builtin_shufflevector(ml, mu, 0, 1, 2, 3, 4, 5, 6, 7);
+                    pwc_f16x4 hl, ml, hu, mu;
+                    pwc_split4(v[u][0], v[u][1], v[u][2], v[u][3], hl, ml);
+                    pwc_split4(v[u][4], v[u][5], v[u][6], v[u][7], hu, mu);
+                    const pwc_f16x8 Bh = __builtin_shufflevector(hl, hu, 0, 1, 2, 3, 4, 5, 6, 7);
+                    const pwc_f16x8 Bm = __builtin_shufflevector(ml, mu, 0, 1, 2, 3, 4, 5, 6, 7);
                     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
                     hh[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0h, Bh, b0v, 0, 0, 0);        // (the bias rides in the accumulator)
                     cx[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0h, Bm, z, 0, 0, 0);
@@ -292,7 +260,7 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
                 for (int u = 0; u < 3; ++u) {
                     const int i = 3 * g + u;
                     if (wave + 8 * i >= ((ABL & 2) ? 0 : C16_NPIX / 16)) continue;
-                    c16_f16x4 h, m;
+                    pwc_f16x4 h, m;
                     float o[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -300,10 +268,10 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
                         o[e] = fmaxf(o[e], o[e] * a.slope);
                         if (!INTERIOR) o[e] = in_image[u] ? o[e] : 0.f;
                     }
-                    c16_split4(o[0], o[1], o[2], o[3], h, m);
+                    pwc_split4(o[0], o[1], o[2], o[3], h, m);
                     char* dst = sm + C16_IN0 + dst_lane + i * 2048;
-                    *reinterpret_cast<c16_f16x4*>(dst) = h;
-                    *reinterpret_cast<c16_f16x4*>(dst + 2 * C16_CH) = m;
+                    *reinterpret_cast<pwc_f16x4*>(dst) = h;
+                    *reinterpret_cast<pwc_f16x4*>(dst + 2 * C16_CH) = m;
                 }
             }
             };
@@ -316,15 +284,15 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
             if (it < C16_NPIX * 4 && !(ABL & 2)) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(sm + C16_S0 + it * 16);
                 const int rec = it >> 2, g = it & 3;
-                c16_f16x4 h, m;
-                c16_split4(v[0], v[1], v[2], v[3], h, m);
+                pwc_f16x4 h, m;
+                pwc_split4(v[0], v[1], v[2], v[3], h, m);
                 char* dst = sm + C16_IN0 + (g >> 1) * C16_CH + rec * 16 + (g & 1) * 8;
-                *reinterpret_cast<c16_f16x4*>(dst) = h;
-                *reinterpret_cast<c16_f16x4*>(dst + 2 * C16_CH) = m;
+                *reinterpret_cast<pwc_f16x4*>(dst) = h;
+                *reinterpret_cast<pwc_f16x4*>(dst + 2 * C16_CH) = m;
             }
         }
         }
-        C16_BAR();
+        pwc_lds_barrier_raw();
         if (tile + 1 < tile1) {                      // the next patch, under the two layers
             patch_prepare(tile + 1);
             patch_issue();
@@ -341,20 +309,20 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
                     const int pr = p / C16_P, pc = p - pr * C16_P;
                     in_image = (unsigned)(y0 - 2 + pr) < (unsigned)a.H && (unsigned)(x0 - 2 + pc) < (unsigned)a.W;
                 }
-                c16_f16x4 h, m;
+                pwc_f16x4 h, m;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     o[e] = fmaxf(o[e], o[e] * a.slope);
                     if (!INTERIOR) o[e] = in_image ? o[e] : 0.f;
                 }
-                c16_split4(o[0], o[1], o[2], o[3], h, m);
+                pwc_split4(o[0], o[1], o[2], o[3], h, m);
                 char* dst = sm + C16_MID0 + (kq >> 1) * C16_CH + p * 16 + (kq & 1) * 8;
-                *reinterpret_cast<c16_f16x4*>(dst) = h;
-                *reinterpret_cast<c16_f16x4*>(dst + 2 * C16_CH) = m;
+                *reinterpret_cast<pwc_f16x4*>(dst) = h;
+                *reinterpret_cast<pwc_f16x4*>(dst + 2 * C16_CH) = m;
             }
         };
         if (interior) layer1(std::true_type{}); else layer1(std::false_type{});
-        C16_BAR();
+        pwc_lds_barrier_raw();
         // ---- layer 2: output rows 2 .. 17 of the patch -> bias, leaky-relu, 16 bytes (4 couts) per lane
         const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(a.y + (size_t)n * a.H * a.W * a.y_cs), 0, a.H * a.W * a.y_cs * 4, 0x00020000);
@@ -370,7 +338,6 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, (int)vo, 0, 0);
         }
     }
-#undef C16_BAR
 }
 
 // ---------------------------------------------------------------- weight split + packing
@@ -388,8 +355,8 @@ __global__ void conv3x3_c16pair_pack_kernel(const float* __restrict__ w1, const 
     else { tap = m - 5; ch = 8 * (kq & 1) + e; low = kq >= 2; }
     float u = 0.f;
     if (tap < 9) u = w[(tap * 16 + ch) * 16 + i];
-    const _Float16 h = (_Float16)u;
-    const _Float16 lo = (_Float16)((u - (float)h) * 2048.f);
+    _Float16 h, lo;
+    pwc_split1(u, h, lo);
     packed[idx] = __builtin_bit_cast(unsigned short, low ? lo : h);
 }
 
@@ -405,8 +372,8 @@ __global__ void conv3x3_c16pair_pack0_kernel(const float* __restrict__ w0, unsig
     else if (e < 3) { dy = e; j = 8; }
     float u = 0.f;
     if (dy >= 0) u = w0[((dy * 3 + j / 3) * 3 + j % 3) * 16 + i];   // HWIO (3,3,3,16)
-    const _Float16 h = (_Float16)u;
-    const _Float16 lo = (_Float16)((u - (float)h) * 2048.f);
+    _Float16 h, lo;
+    pwc_split1(u, h, lo);
     packed[28 * 64 * 8 + idx] = __builtin_bit_cast(unsigned short, low ? lo : h);
 }
 
@@ -443,15 +410,6 @@ extern "C" int pwc_conv3x3_c3c16pair_supported(int N, int H0, int W0) {
     return pwc_conv3x3_c16pair_supported(N, (H0 + 1) / 2, W0 / 2);
 }
 
-static int c16pair_grid(int ntiles) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    return ntiles < cus ? ntiles : cus;
-}
-
 // images: N_a at x_a and N_b at x_b (x_b may be null with N_b = 0), NHWC with exactly 3 channels (channel stride 3), H0 x W0,
 // W0 % 4 == 0; y: (N_a + N_b) x ceil(H0 / 2) x W0 / 2 x 16 at channel stride y_cs.
 template <int ABL = 0>
@@ -473,10 +431,8 @@ static int c3c16pair_run(const float* x_a, int N_a, const float* x_b, int N_b, c
     const long nt = (long)a.N * a.tiles_x * a.tiles_y;
     if (nt >= (1L << 31)) return PWC_ERANGE;
     a.ntiles = (int)nt;
-    const int grid = c16pair_grid(a.ntiles);
-    static PwcDevOnce attr_once;
-    if (pwc_first_on_device(&attr_once))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c16pair_kernel<ABL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C16_LDS);
+    const int grid = a.ntiles < pwc_cu_count() ? a.ntiles : pwc_cu_count();
+    pwc_allow_dynamic_lds<&conv3x3_c16pair_kernel<ABL, true>>(C16_LDS);
     hipLaunchKernelGGL((conv3x3_c16pair_kernel<ABL, true>), dim3((unsigned)grid), dim3(512), C16_LDS, (hipStream_t)stream, a);
     return pwc_launch_status();
 }
@@ -490,11 +446,9 @@ extern "C" int pwc_conv3x3_c3c16pair_f32(const float* x_a, int N_a, const float*
 template <int ABL = 0>
 static int c16pair_run(const float* x, int x_cs, const float* packed, const float* bias1, const float* bias2,
                        float* y, int y_cs, int N, int H, int W, float slope, pwc_stream_t stream) {
-    if (!x || !packed || !bias1 || !bias2 || !y) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || x_cs < 16 || y_cs < 16) return PWC_EINVAL;
-    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed) || !pwc_aligned16(bias1) ||
-        !pwc_aligned16(bias2))
-        return PWC_EALIGN;
+    if (!bias2) return PWC_EINVAL;
+    if (const int rc = pwc_conv_io_check(x, x_cs, 16, y, y_cs, 16, packed, bias1, N, H, W, true)) return rc;
+    if (!pwc_aligned16(bias2)) return PWC_EALIGN;
     if ((long)H * W * x_cs * 4 >= (long)C16_OOB || (long)H * W * y_cs * 4 >= (long)C16_OOB) return PWC_ERANGE;
     C16Args a;
     a.x = x; a.wp = packed; a.b1 = bias1; a.b2 = bias2; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;
@@ -504,10 +458,8 @@ static int c16pair_run(const float* x, int x_cs, const float* packed, const floa
     if (nt >= (1L << 31)) return PWC_ERANGE;
     a.ntiles = (int)nt;
     a.x_b = nullptr; a.b0 = nullptr; a.N_a = N; a.H0 = 0; a.W0 = 0; a.pad_t = 0;
-    const int grid = c16pair_grid(a.ntiles);
-    static PwcDevOnce attr_once;
-    if (pwc_first_on_device(&attr_once))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c16pair_kernel<ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, C16_LDS);
+    const int grid = a.ntiles < pwc_cu_count() ? a.ntiles : pwc_cu_count();
+    pwc_allow_dynamic_lds<&conv3x3_c16pair_kernel<ABL>>(C16_LDS);
     hipLaunchKernelGGL((conv3x3_c16pair_kernel<ABL>), dim3((unsigned)grid), dim3(512), C16_LDS, (hipStream_t)stream, a);
     return pwc_launch_status();
 }

@@ -58,7 +58,7 @@
 //   allocation holds (0 - 27 registers spilled), but the launches got slower, 128 -> 128 202 - 212 us against 175 - 180 and
 //   64 -> 32 41 against 39 (a pair-major first tap in EVERY stage, instructions the scheduler cannot see into), before its
 //   results were right.  Left there.
-//   The split in five instructions per value pair instead of seven (conv3x3_c16pair.hip's c16_split2 with plain multiplies)
+//   The split in five instructions per value pair instead of seven (pwc_split2 with plain multiplies)
 //   changes no launch by more than the noise (128 -> 128, 96 -> 64, 64 -> 32, 32 -> 32, d = 16): the split already hides
 //   behind the matrix instructions of its taps.
 #pragma once
@@ -269,7 +269,6 @@ __global__ __launch_bounds__(512) void conv3x3_h2_kernel(const H2Args a) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (lptr_t)(sm + C::A0 + r * C::AP + pc * 1024), 16, (int)w_lane,
                                                      soff + pc * 1024, 0, 0);
     };
-#define H2_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // ---- split of the staging image into an operand image: item = (patch pixel, 4-channel group); item j of a thread is
     // t + 512 j.  cv_read / cv_write are the two halves of an item so that they can sit in different issue slots of a tap.
@@ -479,9 +478,9 @@ __global__ __launch_bounds__(512) void conv3x3_h2_kernel(const H2Args a) {
     for (int j = 0; j < C::APW; ++j) issue_w_piece(j, c16, tcur.cb, 1);
     if (t < a.Cout) reinterpret_cast<float*>(sm + C::BIAS)[t] = a.bias[t];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    H2_BAR();
+    pwc_lds_barrier_raw();
     convert(0);
-    H2_BAR();
+    pwc_lds_barrier_raw();
     if (g0 + 1 < g1) {
         if (c1 == 0) patch_tile(t1);
         select_operand(t1, c1);
@@ -566,7 +565,7 @@ __global__ __launch_bounds__(512) void conv3x3_h2_kernel(const H2Args a) {
         }
         drain = false;
         if (ABL & 2048) { const unsigned long long tk1 = __builtin_readcyclecounter(); tk_wait += tk1 - tk0; tk0 = tk1; }
-        H2_BAR();                          // ... everybody's; every wave is done with slot 2
+        pwc_lds_barrier_raw();                          // ... everybody's; every wave is done with slot 2
         if (ABL & 2048) tk_bar += __builtin_readcyclecounter() - tk0;
         H2_STAMP(1);
         if (fresh0 && !S2) tap(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, g, buf, more, true);
@@ -579,7 +578,7 @@ __global__ __launch_bounds__(512) void conv3x3_h2_kernel(const H2Args a) {
         if (ABL & 2048) tk0 = __builtin_readcyclecounter();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // part (g, 2) and the patch of g + 1
         if (ABL & 2048) { const unsigned long long tk1 = __builtin_readcyclecounter(); tk_wait += tk1 - tk0; tk0 = tk1; }
-        H2_BAR();
+        pwc_lds_barrier_raw();
         if (ABL & 2048) tk_bar += __builtin_readcyclecounter() - tk0;
         H2_STAMP(5);
         tap(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, g, buf, more, false);
@@ -592,7 +591,7 @@ __global__ __launch_bounds__(512) void conv3x3_h2_kernel(const H2Args a) {
         if (ABL & 2048) tk0 = __builtin_readcyclecounter();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // part (g + 1, 0)
         if (ABL & 2048) { const unsigned long long tk1 = __builtin_readcyclecounter(); tk_wait += tk1 - tk0; tk0 = tk1; }
-        H2_BAR();
+        pwc_lds_barrier_raw();
         if (ABL & 2048) tk_bar += __builtin_readcyclecounter() - tk0;
         H2_STAMP(9);
         tap(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, g, buf, more, false);
@@ -628,7 +627,6 @@ __global__ __launch_bounds__(512) void conv3x3_h2_kernel(const H2Args a) {
         unsigned* o = a.dbg + (lw * 8 + wave) * 4;
         o[0] = (unsigned)(__builtin_readcyclecounter() - tk_start); o[1] = (unsigned)tk_wait; o[2] = (unsigned)tk_bar; o[3] = (unsigned)tk_fin;
     }
-#undef H2_BAR
 #undef H2_STAMP
 }
 
@@ -662,8 +660,8 @@ __global__ void conv3x3_h2_pack_kernel(const float* __restrict__ w, const int32_
         }
         float u = 0.f;
         if (wtap >= 0 && clog >= 0 && clog < Cin && co < Cout) u = w[((size_t)wtap * Cin + clog) * Cout + co];
-        const _Float16 h = (_Float16)u;
-        const _Float16 m = (_Float16)((u - (float)h) * 2048.f);
+        _Float16 h, m;
+        pwc_split1(u, h, m);
         const int tr = tap / 3, dx = tap - 3 * tr;
         unsigned short* base = packed + (((((size_t)c16 * 3 + tr) * nct + ct) * 3 + dx) * 4) * 256;      // 4 chunks x 32 couts x 8
         base[(ch >> 3) * 256 + i * 8 + (ch & 7)] = __builtin_bit_cast(unsigned short, h);
@@ -772,15 +770,8 @@ constexpr int h2_reserve_cus = 0;
 #endif
 
 static int h2_cu_count() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev] - h2_reserve_cus > 0 ? cus[dev] - h2_reserve_cus : 1;
+    const int cus = pwc_cu_count() - h2_reserve_cus;
+    return cus > 0 ? cus : 1;
 }
 
 // 1 where this kernel is the faster one for the shape (measured against conv3x3_wino4.hip / conv3x3_wino.hip on isolated layers:
@@ -818,11 +809,7 @@ static int h2_launch(H2Args& a, int hs, int ws, float* workspace, size_t workspa
         grid = cus;
         a.ws_partial = workspace;
     }
-    static PwcDevOnce attr_once;
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_h2_kernel<CT, PT, WCG, ABL, XS, S2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    }
+    pwc_allow_dynamic_lds<&conv3x3_h2_kernel<CT, PT, WCG, ABL, XS, S2>>(C::LDS);
     hipLaunchKernelGGL((conv3x3_h2_kernel<CT, PT, WCG, ABL, XS, S2>), dim3((unsigned)grid), dim3(512), C::LDS, stream, a);
     return pwc_launch_status();
 }
@@ -835,10 +822,10 @@ static int h2_run(const float* x, int x_cs, const float* packed_w, const float* 
                   int Cin_a_phys = 0, uint32_t* status = nullptr, const float* x3 = nullptr, int x3_cs = 0, int Cin_b_phys = 0) {
     if (!x || !packed_w || !bias || !y) return PWC_EINVAL;
     if (x3 && !x2) return PWC_EINVAL;
+    // (three operands: an operand's channel stride may be up to 12 channels short of its stage count x 16 -- its last stage then
+    // runs into the next pixel's record, see H2Args::x3)
+    const int slack = x3 ? 12 : 0;
     if (x2) {
-        // (three operands: an operand's channel stride may be up to 12 channels short of its stage count x 16 -- its last stage then
-        // runs into the next pixel's record, see H2Args::x3)
-        const int slack = x3 ? 12 : 0;
         const int cb = x3 ? Cin_b_phys : Cin_phys - Cin_a_phys;
         if (Cin_a_phys <= 0 || Cin_a_phys >= Cin_phys || (Cin_a_phys % 16) || x_cs < Cin_a_phys - slack || x2_cs < cb - slack) return PWC_EINVAL;
         if ((x2_cs & 3) || !pwc_aligned16(x2)) return PWC_EALIGN;
@@ -851,12 +838,11 @@ static int h2_run(const float* x, int x_cs, const float* packed_w, const float* 
         if ((long)H * W * x3_cs * 4 >= (long)H2_OOB) return PWC_ERANGE;
     }
     if (reinterpret_cast<uintptr_t>(status) & 7u) return PWC_EALIGN;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0 || dilation < 1 || (stride != 1 && stride != 2)) return PWC_EINVAL;
-    if (Cin_phys % 16 || Cout % 32 || Cout > H2_MAX_COUT || (stride == 2 && (dilation != 1 || (H & 1) || (W & 1) || x2))) return PWC_EUNSUPPORTED;
-    if ((!x2 && x_cs < Cin_phys) || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed_w) || !pwc_aligned16(bias) ||
-        !pwc_aligned16(workspace))
-        return PWC_EALIGN;
+    if (dilation < 1 || (stride != 1 && stride != 2)) return PWC_EINVAL;
+    const bool shape_ok = !(Cin_phys % 16 || Cout % 32 || Cout > H2_MAX_COUT || (stride == 2 && (dilation != 1 || (H & 1) || (W & 1) || x2)));
+    // (the channels x itself must hold: all of them, or -- checked above -- its share of two or three operands)
+    if (const int rc = pwc_conv_io_check(x, x_cs, x2 ? Cin_a_phys - slack : Cin_phys, y, y_cs, Cout, packed_w, bias, N, H, W, shape_ok)) return rc;
+    if (!pwc_aligned16(workspace)) return PWC_EALIGN;
     if (((long)H * W + W + 2) * x_cs * 4 >= (long)H2_OOB || (long)H * W * y_cs * 4 >= (long)H2_OOB) return PWC_ERANGE;
     H2Args a;
     a.x = x; a.wp = packed_w; a.bias = bias; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;

@@ -43,20 +43,30 @@ struct SkArgs {
     int nsteps;             // 9 cg
 };
 
+// The workgroup's tile (both kernels), output-channel tile fastest: the workgroups of one XCD (blockIdx % 8) then share few
+// weight tiles.  (The kernels' other common passages -- weight-fragment fetch, split + matrix step, the LDS epilogue -- stay
+// spelled out in each: lifted into functions they compile to different code.)
+struct SkTile { int ct, tx, by, n; };
+__device__ __forceinline__ SkTile sk_tile(const SkArgs& a) {
+    SkTile tl;
+    int b = blockIdx.x;
+    tl.ct = b % a.nct;
+    b /= a.nct;
+    tl.tx = b % a.ntx;
+    b /= a.ntx;
+    tl.by = b % a.nby;
+    tl.n = b / a.nby;
+    return tl;
+}
+
 // PB: K steps a wave requests at a time (registers: PB (MT + NT) 8)
 template <int MT, int NT, int PB>
 __global__ __launch_bounds__(512, 2) void conv3x3_sk_kernel(const SkArgs a) {
     __shared__ __attribute__((aligned(16))) float part[8 * MT * NT * 256];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    // output-channel tile fastest: the workgroups of one XCD (blockIdx % 8) then share few weight tiles
-    int b = blockIdx.x;
-    const int ct = b % a.nct;
-    b /= a.nct;
-    const int tx = b % a.ntx;
-    b /= a.ntx;
-    const int by = b % a.nby;
-    const int n = b / a.nby;
+    const SkTile tl = sk_tile(a);
+    const int ct = tl.ct, tx = tl.tx, by = tl.by, n = tl.n;
 
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
         (void*)a.x, 0, (int)((size_t)a.N * a.H * a.W * a.x_cs * 4), 0x00020000);
@@ -182,13 +192,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_skp_kernel(const SkArgs a) {
     const int ps = a.Cin_phys * 4 + 16;                                     // bytes of a pixel record
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    int b = blockIdx.x;
-    const int ct = b % a.nct;
-    b /= a.nct;
-    const int tx = b % a.ntx;
-    b /= a.ntx;
-    const int by = b % a.nby;
-    const int n = b / a.nby;
+    const SkTile tl = sk_tile(a);
+    const int ct = tl.ct, tx = tl.tx, by = tl.by, n = tl.n;
 
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
         (void*)a.x, 0, (int)((size_t)a.N * a.H * a.W * a.x_cs * 4), 0x00020000);
@@ -336,11 +341,8 @@ __global__ void conv3x3_sk_pack_kernel(const float* __restrict__ w, const int32_
         const int clog = cin_map ? cin_map[cphys] : (cphys < Cin ? cphys : -1);
         float v = 0.f;
         if (clog >= 0 && clog < Cin) v = w[((size_t)tap * Cin + clog) * Cout + co];
-        const _Float16 h = (_Float16)v;
-        const _Float16 mm = (_Float16)fmaf((float)h, -2048.f, v * 2048.f);
         _Float16* dst = packed + ((size_t)(cb * nsteps + s) * 2) * 512 + lane * 8 + e;
-        dst[0] = h;
-        dst[512] = mm;
+        pwc_split1(v, dst[0], dst[512]);
     }
 }
 
@@ -388,7 +390,7 @@ extern "C" int pwc_conv3x3_sk_supported(int N, int H, int W, int Cin_phys, int C
     int Ho, Wo, pt, pl;
     pwc_same_pad(H, stride, dilation, &Ho, &pt);
     pwc_same_pad(W, stride, dilation, &Wo, &pl);
-    if ((long)N * H * W * Cin_phys * 4 >= (1L << 31)) return 0;
+    if (!pwc_fits_2g(N, H, W, Cin_phys)) return 0;
     const long M = (long)N * Ho * Wo, macs = M * Cin_phys * Cout;
     if (stride == 1 && dilation == 1 && Cin_phys >= 96 && Cin_phys <= 288 && M <= PWC_SK_LP_MAX_PIXELS && macs <= PWC_SK_LP_MAX_MACS)
         return 1;
@@ -417,11 +419,7 @@ static int skp_launch(SkArgs a, hipStream_t s) {
     constexpr int NPX = (3 * S + 3) * ((4 * MT - 1) * S + 3);
     size_t lds = (size_t)NPX * (a.Cin_phys * 4 + 16);                      // the patch; the partial tiles reuse its space
     if (lds < (size_t)8 * MT * NT * 1024) lds = (size_t)8 * MT * NT * 1024;
-    static PwcDevOnce attr_once;
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_skp_kernel<MT, NT, PB, S>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, NPX * ((S == 1 ? 288 : 128) * 4 + 16));
-    }
+    pwc_allow_dynamic_lds<&conv3x3_skp_kernel<MT, NT, PB, S>>(NPX * ((S == 1 ? 288 : 128) * 4 + 16));
     hipLaunchKernelGGL((conv3x3_skp_kernel<MT, NT, PB, S>), dim3((unsigned)wgs), dim3(512), lds, s, a);
     return pwc_launch_status();
 }
@@ -439,13 +437,10 @@ extern "C" int pwc_debug_conv3x3_sk_tile(int tile) { sk_tile_override = tile; re
 static int sk_run(const float* x, int x_cs, const float* packed_w, const float* bias, float* y, int y_cs,
                   int N, int H, int W, int Cin_phys, int Cout, int stride, int dilation, int apply_act,
                   float slope, int tile_req, pwc_stream_t stream) {
-    if (!x || !packed_w || !bias || !y) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0 || stride < 1 || stride > 2 || dilation < 1) return PWC_EINVAL;
-    if (Cin_phys % 32 || Cout % 16) return PWC_EUNSUPPORTED;
-    if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed_w) || !pwc_aligned16(bias))
-        return PWC_EALIGN;
-    if ((long)N * H * W * x_cs * 4 >= (1L << 31)) return PWC_ERANGE;
+    if (stride < 1 || stride > 2 || dilation < 1) return PWC_EINVAL;
+    const bool shape_ok = !(Cin_phys % 32 || Cout % 16);
+    if (const int rc = pwc_conv_io_check(x, x_cs, Cin_phys, y, y_cs, Cout, packed_w, bias, N, H, W, shape_ok)) return rc;
+    if (!pwc_fits_2g(N, H, W, x_cs)) return PWC_ERANGE;
     SkArgs a;
     a.x = x; a.wp = packed_w; a.bias = bias; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;
     a.N = N; a.H = H; a.W = W;

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void conv3x3_t32_kernel(const T32Args a) {
             *reinterpret_cast<pwc_f16x8*>(dst + G::PLANE) = __builtin_shufflevector(m0, m1, 0, 1, 2, 3, 4, 5, 6, 7);
         }
         // the operand image is complete, the raw patch free
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        pwc_lds_barrier_raw();
         int n, y0, x0;
         decode(tile, n, y0, x0);
         const int nxt = tile + (int)gridDim.x;
@@ -254,27 +254,7 @@ __global__ __launch_bounds__(256) void conv3x3_t32_kernel(const T32Args a) {
     }
 }
 
-// packed[tap][j][hm][lane][e] (fp16): weight of output channel lane & 31, tap, physical input channel 16 j + 8 (lane >> 5) + e
-__global__ void conv3x3_t32_pack_kernel(const float* __restrict__ w, const int32_t* __restrict__ cin_map, int Cin, int Cin_phys,
-                                        _Float16* __restrict__ packed) {
-    const int j16 = Cin_phys >> 4;
-    const int total = 9 * j16 * 512;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int e = idx & 7, lane = (idx >> 3) & 63;
-        const int r = idx >> 9;
-        const int j = r % j16, tap = r / j16;
-        const int cphys = j * 16 + (lane >> 5) * 8 + e, co = lane & 31;
-        const int clog = cin_map ? cin_map[cphys] : (cphys < Cin ? cphys : -1);
-        float v = 0.f;
-        if (clog >= 0 && clog < Cin) v = w[((size_t)tap * Cin + clog) * 32 + co];
-        const _Float16 h = (_Float16)v;
-        const _Float16 mm = (_Float16)fmaf((float)h, -2048.f, v * 2048.f);
-        _Float16* dst = packed + (size_t)r * 1024 + lane * 8 + e;
-        dst[0] = h;
-        dst[512] = mm;
-    }
-}
-
+// packed weights: conv3x3_c32_pack_kernel (pwc_common.h), 9 x C_in / 16 K steps of 1024 fp16
 extern "C" size_t pwc_conv3x3_t32_packed_floats(int Cin_phys) {
     if (Cin_phys != 16 && Cin_phys != 32) return 0;
     return (size_t)9 * (Cin_phys / 16) * 512;
@@ -285,7 +265,7 @@ extern "C" int pwc_conv3x3_t32_pack_f32(const float* w_hwio, const int32_t* cin_
     if (!w_hwio || !packed_w || Cin <= 0 || Cin_phys < Cin) return PWC_EINVAL;
     if (Cin_phys != 16 && Cin_phys != 32) return PWC_EUNSUPPORTED;
     if (!pwc_aligned16(packed_w)) return PWC_EALIGN;
-    hipLaunchKernelGGL(conv3x3_t32_pack_kernel, dim3(36), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map, Cin, Cin_phys,
+    hipLaunchKernelGGL(conv3x3_c32_pack_kernel<>, dim3(36), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map, Cin, Cin_phys,
                        reinterpret_cast<_Float16*>(packed_w));
     return pwc_launch_status();
 }
@@ -294,16 +274,13 @@ extern "C" int pwc_conv3x3_t32_pack_f32(const float* w_hwio, const int32_t* cin_
 // (at least 256 tiles of 8 x 32 -- stride 2: 4 x 32 -- output pixels: one per CU)
 extern "C" int pwc_conv3x3_t32_supported(int N, int H, int W, int Cin_phys, int Cout, int stride) {
     if (N <= 0 || H <= 0 || W <= 0 || (Cin_phys != 16 && Cin_phys != 32) || Cout != 32 || stride < 1 || stride > 2) return 0;
-    if (Cin_phys == 32 && stride == 2) return 0;                 // (two parity planes of 32 channels do not fit the LDS twice)
-    // 32 input channels: the entry point takes them, but 144 weight registers beside the fragments and accumulators leave one wave
-    // per SIMD (or spill) and the launch loses to conv3x3_h2_kernel (52 - 77 us against 48 at 16 x 112 x 256; in the forward
-    // 2.599 against 2.582 ms)
+    // 32 input channels: the entry point takes them at stride 1 (at stride 2 two parity planes of 32 channels do not fit the LDS
+    // twice), but 144 weight registers beside the fragments and accumulators leave one wave per SIMD (or spill) and the launch
+    // loses to conv3x3_h2_kernel (52 - 77 us against 48 at 16 x 112 x 256; in the forward 2.599 against 2.582 ms)
     if (Cin_phys == 32) return 0;
-    // 32 input channels: the entry point takes them, but 144 weight registers beside the fragments and accumulators spill into
-    // the accumulation registers and the launch loses to conv3x3_h2_kernel (52 - 73 us against 48 at 16 x 112 x 256)
-    if ((long)N * H * W * Cin_phys * 4 >= (1L << 31)) return 0;
+    if (!pwc_fits_2g(N, H, W, Cin_phys)) return 0;
     const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-    if ((long)N * Ho * Wo * Cout * 4 >= (1L << 31)) return 0;   // (a dense output; a wider y_cs is the entry point's PWC_ERANGE)
+    if (!pwc_fits_2g(N, Ho, Wo, Cout)) return 0;                 // (a dense output; a wider y_cs is the entry point's PWC_ERANGE)
     const int tr = 4;
     return (long)N * ((Ho + tr - 1) / tr) * ((Wo + 31) / 32) >= 256 ? 1 : 0;
 }
@@ -322,18 +299,9 @@ static int t32_launch(T32Args& a, hipStream_t s) {
     a.dbg = 0;
 #endif
     using G = T32Geom<CIN, S>;
-    static PwcDevOnce attr_once;
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_t32_kernel<CIN, S>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    }
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
+    pwc_allow_dynamic_lds<&conv3x3_t32_kernel<CIN, S>>(G::LDS);
     const int per_cu = (160 * 1024) / G::LDS > 0 ? (160 * 1024) / G::LDS : 1;
-    int grid = cus * per_cu;
+    int grid = pwc_cu_count() * per_cu;
     if (grid > a.ntiles) grid = a.ntiles;
     hipLaunchKernelGGL((conv3x3_t32_kernel<CIN, S>), dim3((unsigned)grid), dim3(256), G::LDS, s, a);
     return pwc_launch_status();
@@ -342,18 +310,13 @@ static int t32_launch(T32Args& a, hipStream_t s) {
 extern "C" int pwc_conv3x3_t32_f32(const float* x, int x_cs, const float* packed_w, const float* bias, float* y, int y_cs,
                                    int N, int H, int W, int Cin_phys, int Cout, int stride, int apply_act, float slope,
                                    pwc_stream_t stream) {
-    if (!x || !packed_w || !bias || !y) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0 || stride < 1 || stride > 2) return PWC_EINVAL;
-    if ((Cin_phys != 16 && Cin_phys != 32) || Cout != 32 || (Cin_phys == 32 && stride == 2)) return PWC_EUNSUPPORTED;
-    if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed_w) || !pwc_aligned16(bias))
-        return PWC_EALIGN;
-    if ((long)N * H * W * x_cs * 4 >= (1L << 31)) return PWC_ERANGE;
-    {   // the OUTPUT's buffer resource and store offsets are 32-bit too (a stride-1 launch writes twice the input's
-        // bytes, a slice of a wide buffer more)
-        const long Ho_ = (H + stride - 1) / stride, Wo_ = (W + stride - 1) / stride;
-        if ((long)N * Ho_ * Wo_ * y_cs * 4 >= (1L << 31)) return PWC_ERANGE;
-    }
+    if (stride < 1 || stride > 2) return PWC_EINVAL;
+    const bool shape_ok = (Cin_phys == 16 || Cin_phys == 32) && Cout == 32 && !(Cin_phys == 32 && stride == 2);
+    if (const int rc = pwc_conv_io_check(x, x_cs, Cin_phys, y, y_cs, Cout, packed_w, bias, N, H, W, shape_ok)) return rc;
+    if (!pwc_fits_2g(N, H, W, x_cs)) return PWC_ERANGE;
+    // the OUTPUT's buffer resource and store offsets are 32-bit too (a stride-1 launch writes twice the input's bytes,
+    // a slice of a wide buffer more)
+    if (!pwc_fits_2g(N, (H + stride - 1) / stride, (W + stride - 1) / stride, y_cs)) return PWC_ERANGE;
     T32Args a;
     a.x = x; a.wp = packed_w; a.bias = bias; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;
     a.N = N; a.H = H; a.W = W;

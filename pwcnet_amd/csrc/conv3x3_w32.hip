@@ -33,7 +33,7 @@ typedef __attribute__((address_space(3))) void* w32_lptr;
 
 struct W32Args {
     const float* x;
-    const float* wp;        // packed split weights: [tap 9][C_in / 16][h | m'][64 lanes][8 fp16]  (conv3x3_w32_pack_kernel)
+    const float* wp;        // packed split weights: [tap 9][C_in / 16][h | m'][64 lanes][8 fp16]  (conv3x3_c32_pack_kernel)
     const float* bias;
     float* y;
     int x_cs, y_cs;
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_w32_kernel(const W32Args a) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         flush();
         split();
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // the operand image is complete (and the sums read)
+        pwc_lds_barrier_raw();                                     // the operand image is complete (and the sums read)
         const int nxt = tile + (int)gridDim.x;
         if (nxt < a.ntiles) {
             int nn, ny0, nx0;
@@ -245,32 +245,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_w32_kernel(const W32Args a) {
             o_n = n; o_y0 = y0; o_x0 = x0; have_prev = true;
         }
     }
-    if (KS == 2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (KS == 2) pwc_lds_barrier_raw();
     flush();
 }
 
-// packed[tap][j][hm][lane][e] (fp16): weight of output channel lane & 31, tap, physical input channel 16 j + 8 (lane >> 5) + e
-// (the layout of conv3x3_t32.hip, for 32 or 64 physical input channels)
-__global__ void conv3x3_w32_pack_kernel(const float* __restrict__ w, const int32_t* __restrict__ cin_map, int Cin, int Cin_phys,
-                                        _Float16* __restrict__ packed) {
-    const int j16 = Cin_phys >> 4;
-    const int total = 9 * j16 * 512;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int e = idx & 7, lane = (idx >> 3) & 63;
-        const int r = idx >> 9;
-        const int j = r % j16, tap = r / j16;
-        const int cphys = j * 16 + (lane >> 5) * 8 + e, co = lane & 31;
-        const int clog = cin_map ? cin_map[cphys] : (cphys < Cin ? cphys : -1);
-        float v = 0.f;
-        if (clog >= 0 && clog < Cin) v = w[((size_t)tap * Cin + clog) * 32 + co];
-        const _Float16 h = (_Float16)v;
-        const _Float16 mm = (_Float16)fmaf((float)h, -2048.f, v * 2048.f);
-        _Float16* dst = packed + (size_t)r * 1024 + lane * 8 + e;
-        dst[0] = h;
-        dst[512] = mm;
-    }
-}
-
+// packed weights: conv3x3_c32_pack_kernel (pwc_common.h) -- the layout of conv3x3_t32.hip, for 32 or 64 physical input channels
 extern "C" size_t pwc_conv3x3_w32_packed_floats(int Cin_phys) {
     if (Cin_phys != 32 && Cin_phys != 64) return 0;
     return (size_t)9 * (Cin_phys / 16) * 512;
@@ -281,25 +260,16 @@ extern "C" int pwc_conv3x3_w32_pack_f32(const float* w_hwio, const int32_t* cin_
     if (!w_hwio || !packed_w || Cin <= 0 || Cin_phys < Cin) return PWC_EINVAL;
     if (Cin_phys != 32 && Cin_phys != 64) return PWC_EUNSUPPORTED;
     if (!pwc_aligned16(packed_w)) return PWC_EALIGN;
-    hipLaunchKernelGGL(conv3x3_w32_pack_kernel, dim3(72), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map, Cin, Cin_phys,
+    hipLaunchKernelGGL(conv3x3_c32_pack_kernel<>, dim3(72), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map, Cin, Cin_phys,
                        reinterpret_cast<_Float16*>(packed_w));
     return pwc_launch_status();
-}
-
-static int w32_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    return cus;
 }
 
 // C_in (physical) 32 or 64, C_out 32, stride 1, no dilation; 1 where it is the fastest kernel of the library for the shape: a
 // launch of at least one tile (8 / 4 rows x 32 columns) per CU
 extern "C" int pwc_conv3x3_w32_supported(int N, int H, int W, int Cin_phys, int Cout, int stride, int dilation) {
     if (N <= 0 || H <= 0 || W <= 0 || (Cin_phys != 32 && Cin_phys != 64) || Cout != 32 || stride != 1 || dilation != 1) return 0;
-    if ((long)N * H * W * Cin_phys * 4 >= (1L << 31)) return 0;
+    if (!pwc_fits_2g(N, H, W, Cin_phys)) return 0;
     const int tr = Cin_phys == 32 ? 8 : 4;
     return (long)N * ((H + tr - 1) / tr) * ((W + 31) / 32) >= 256 ? 1 : 0;
 }
@@ -311,12 +281,8 @@ static int w32_launch(W32Args& a, hipStream_t s) {
     const long nt = (long)a.N * a.tiles_x * a.tiles_y;
     if (nt >= (1L << 30)) return PWC_ERANGE;
     a.ntiles = (int)nt;
-    static PwcDevOnce attr_once;
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_w32_kernel<CIN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    }
-    int grid = w32_cus();
+    pwc_allow_dynamic_lds<&conv3x3_w32_kernel<CIN>>(G::LDS);
+    int grid = pwc_cu_count();
     if (grid > a.ntiles) grid = a.ntiles;
     hipLaunchKernelGGL((conv3x3_w32_kernel<CIN>), dim3((unsigned)grid), dim3(512), G::LDS, s, a);
     return pwc_launch_status();
@@ -325,13 +291,9 @@ static int w32_launch(W32Args& a, hipStream_t s) {
 extern "C" int pwc_conv3x3_w32_f32(const float* x, int x_cs, const float* packed_w, const float* bias, float* y, int y_cs,
                                    int N, int H, int W, int Cin_phys, int Cout, int apply_act, float slope,
                                    pwc_stream_t stream) {
-    if (!x || !packed_w || !bias || !y) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0) return PWC_EINVAL;
-    if ((Cin_phys != 32 && Cin_phys != 64) || Cout != 32) return PWC_EUNSUPPORTED;
-    if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed_w) || !pwc_aligned16(bias))
-        return PWC_EALIGN;
-    if ((long)N * H * W * x_cs * 4 >= (1L << 31) || (long)N * H * W * y_cs * 4 >= (1L << 31)) return PWC_ERANGE;
+    const bool shape_ok = (Cin_phys == 32 || Cin_phys == 64) && Cout == 32;
+    if (const int rc = pwc_conv_io_check(x, x_cs, Cin_phys, y, y_cs, Cout, packed_w, bias, N, H, W, shape_ok)) return rc;
+    if (!pwc_fits_2g(N, H, W, x_cs) || !pwc_fits_2g(N, H, W, y_cs)) return PWC_ERANGE;
     W32Args a;
     a.x = x; a.wp = packed_w; a.bias = bias; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;
     a.N = N; a.H = H; a.W = W;

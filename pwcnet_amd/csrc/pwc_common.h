@@ -32,7 +32,48 @@ static inline bool pwc_first_on_device(PwcDevOnce* o) {
     return true;
 }
 
+// "Set the dynamic-LDS ceiling of this kernel once per device", in front of a launch: one flag set per kernel (the template is
+// instantiated per kernel POINTER, not per kernel type -- the instantiations of a kernel template share a type).
+template <auto Kernel>
+static inline void pwc_allow_dynamic_lds(int bytes) {
+    static PwcDevOnce once;
+    if (pwc_first_on_device(&once))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+// Compute units of the current device, asked once per device (256 where the runtime cannot say): the grid of the persistent kernels.
+static inline int pwc_cu_count() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cus[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus[dev] = n;
+    }
+    return cus[dev];
+}
+
 static inline bool pwc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// The argument checks the F16-matrix-pipe conv entry points share, in the order they report: null pointers and non-positive
+// sizes (PWC_EINVAL), the family's own shape rule (`supported` false: PWC_EUNSUPPORTED), a channel stride below the channel
+// count (PWC_EINVAL), channel strides that are not whole 16-byte chunks and pointers off a 16-byte boundary (PWC_EALIGN).
+// What a family checks besides -- stride and dilation, further operands, the 32-bit range of ITS buffer resources -- stays with
+// it, in front of or behind this call as the code it reports has to win or lose.
+static inline int pwc_conv_io_check(const void* x, int x_cs, int Cin_phys, const void* y, int y_cs, int Cout, const void* packed_w,
+                                    const void* bias, int N, int H, int W, bool supported) {
+    if (!x || !packed_w || !bias || !y) return PWC_EINVAL;
+    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0) return PWC_EINVAL;
+    if (!supported) return PWC_EUNSUPPORTED;
+    if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
+    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed_w) || !pwc_aligned16(bias))
+        return PWC_EALIGN;
+    return PWC_OK;
+}
+// A whole tensor behind ONE buffer resource with 32-bit byte offsets (an out-of-range offset, 2^31, is how a lane asks for
+// zeros): n x h x w records of cs floats must end below 2^31 bytes.
+static inline bool pwc_fits_2g(long n, long h, long w, long cs) { return n * h * w * cs * 4 < (1L << 31); }
 
 // TF 'SAME' padding of one axis for a 3-tap kernel (see include/pwc_hip.h, conv).
 static inline void pwc_same_pad(int in, int stride, int dil, int* out, int* before) {
@@ -69,13 +110,15 @@ __device__ __forceinline__ float pwc_mul_rounded(float a, float b) {
 #ifndef PWC_FENCE_BARRIER
 #define PWC_FENCE_BARRIER 1
 #endif
+// The spelled-out form: this wave's LDS operations are complete, then the barrier -- fetches and stores in flight stay in flight.
+__device__ __forceinline__ void pwc_lds_barrier_raw() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void pwc_lds_barrier() {
 #if PWC_FENCE_BARRIER
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 #else
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    pwc_lds_barrier_raw();
 #endif
 }
 
@@ -120,4 +163,35 @@ __device__ __forceinline__ void pwc_split4(const f32x4 x, pwc_f16x4& h, pwc_f16x
     pwc_split2(x[2], x[3], a, b); hp[1] = a; mp[1] = b;
     h = __builtin_bit_cast(pwc_f16x4, hp);
     m = __builtin_bit_cast(pwc_f16x4, mp);
+}
+__device__ __forceinline__ void pwc_split4(const float x0, const float x1, const float x2, const float x3, pwc_f16x4& h, pwc_f16x4& m) {
+    pwc_split4(f32x4{x0, x1, x2, x3}, h, m);
+}
+// One value, for the weight pack kernels.  fma(h, -2^11, x 2^11) and (x - h) 2^11 are the same bits for every finite
+// |x| < 65520: x - h, h 2^11 and x 2^11 are all exact in fp32 there, so either spelling rounds the same number to fp16 once.
+__device__ __forceinline__ void pwc_split1(const float x, _Float16& h, _Float16& m) {
+    h = (_Float16)x;
+    m = (_Float16)__builtin_fmaf((float)h, -2048.f, x * 2048.f);
+}
+
+// ---- packed weights of the kernels that keep all 32 output channels as the row operand of one 32 x 32 x 16 instruction
+// (conv3x3_t32.hip, conv3x3_w32.hip): packed[tap][j][hm][lane][e] (fp16) = weight of output channel lane & 31, tap, physical
+// input channel 16 j + 8 (lane >> 5) + e, h halves then m' halves; cin_map as in pwc_conv3x3_pack_f32.
+template <int COUT = 32>
+__global__ void conv3x3_c32_pack_kernel(const float* __restrict__ w, const int32_t* __restrict__ cin_map, int Cin, int Cin_phys,
+                                        _Float16* __restrict__ packed) {
+    static_assert(COUT == 32, "the row operand of v_mfma_f32_32x32x16_f16");
+    const int j16 = Cin_phys >> 4;
+    const int total = 9 * j16 * 512;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+        const int e = idx & 7, lane = (idx >> 3) & 63;
+        const int r = idx >> 9;
+        const int j = r % j16, tap = r / j16;
+        const int cphys = j * 16 + (lane >> 5) * 8 + e, co = lane & (COUT - 1);
+        const int clog = cin_map ? cin_map[cphys] : (cphys < Cin ? cphys : -1);
+        float v = 0.f;
+        if (clog >= 0 && clog < Cin) v = w[((size_t)tap * Cin + clog) * COUT + co];
+        _Float16* dst = packed + (size_t)r * 1024 + lane * 8 + e;
+        pwc_split1(v, dst[0], dst[512]);
+    }
 }

@@ -100,6 +100,108 @@ def test_production_library_has_no_debug_knobs():
     assert v(al, 320, al, al, al, 32, 1, 8, 8, 320, 32, 1, 1, 1, 0.1, 41, None) == -4    # ... and at most 288 input channels
 
 
+_AL, _MIS = 4096, 4100      # an aligned and a 4-byte-aligned-only non-null address: argument checks only, nothing is launched
+_EINVAL, _EALIGN, _ERANGE, _EUNSUP = -1, -2, -3, -4
+# entry point -> (argument names in call order, a call that passes every check)
+_F16_CONV_CALLS = {
+    "pwc_conv3x3_h2_f32": (
+        "x x_cs pw bias y y_cs N H W Cin Cout dil act slope ws wsf stream",
+        dict(x=_AL, x_cs=64, pw=_AL, bias=_AL, y=_AL, y_cs=64, N=1, H=16, W=32, Cin=64, Cout=64, dil=1, act=1, slope=0.1, ws=None, wsf=0, stream=None)),
+    "pwc_conv3x3_h2_ex_f32": (
+        "x x_cs Cin_a x2 x2_cs pw bias y y_cs N H W Cin Cout dil act slope ws wsf status stream",
+        dict(x=_AL, x_cs=32, Cin_a=32, x2=_AL, x2_cs=32, pw=_AL, bias=_AL, y=_AL, y_cs=64, N=1, H=16, W=32, Cin=64, Cout=64, dil=1, act=1,
+             slope=0.1, ws=None, wsf=0, status=None, stream=None)),
+    "pwc_conv3x3_h2_ex3_f32": (
+        "x x_cs Cin_a x2 x2_cs Cin_b x3 x3_cs pw bias y y_cs N H W Cin Cout act slope ws wsf status stream",
+        dict(x=_AL, x_cs=84, Cin_a=96, x2=_AL, x2_cs=32, Cin_b=32, x3=_AL, x3_cs=32, pw=_AL, bias=_AL, y=_AL, y_cs=64, N=1, H=16, W=32,
+             Cin=160, Cout=64, act=1, slope=0.1, ws=None, wsf=0, status=None, stream=None)),
+    "pwc_conv3x3_h2_stride2_f32": (
+        "x x_cs pw bias y y_cs N H W Cin Cout act slope ws wsf status stream",
+        dict(x=_AL, x_cs=16, pw=_AL, bias=_AL, y=_AL, y_cs=32, N=1, H=16, W=32, Cin=16, Cout=32, act=1, slope=0.1, ws=None, wsf=0, status=None,
+             stream=None)),
+    "pwc_conv3x3_sk_f32": (
+        "x x_cs pw bias y y_cs N H W Cin Cout stride dil act slope stream",
+        dict(x=_AL, x_cs=64, pw=_AL, bias=_AL, y=_AL, y_cs=32, N=1, H=16, W=32, Cin=64, Cout=32, stride=1, dil=1, act=1, slope=0.1, stream=None)),
+    "pwc_conv3x3_t32_f32": (
+        "x x_cs pw bias y y_cs N H W Cin Cout stride act slope stream",
+        dict(x=_AL, x_cs=16, pw=_AL, bias=_AL, y=_AL, y_cs=32, N=1, H=16, W=32, Cin=16, Cout=32, stride=1, act=1, slope=0.1, stream=None)),
+    "pwc_conv3x3_w32_f32": (
+        "x x_cs pw bias y y_cs N H W Cin Cout act slope stream",
+        dict(x=_AL, x_cs=32, pw=_AL, bias=_AL, y=_AL, y_cs=32, N=1, H=16, W=32, Cin=32, Cout=32, act=1, slope=0.1, stream=None)),
+    "pwc_conv3x3_c16pair_f32": (
+        "x x_cs pw b1 b2 y y_cs N H W slope stream",
+        dict(x=_AL, x_cs=16, pw=_AL, b1=_AL, b2=_AL, y=_AL, y_cs=16, N=1, H=16, W=32, slope=0.1, stream=None)),
+    "pwc_conv3x3_c3c16pair_f32": (
+        "x N x_b N_b pw b0 b1 b2 y y_cs H W slope stream",
+        dict(x=_AL, N=1, x_b=None, N_b=0, pw=_AL, b0=_AL, b1=_AL, b2=_AL, y=_AL, y_cs=16, H=32, W=64, slope=0.1, stream=None)),
+}
+_BIG = dict(H=16384, W=16384)          # 2^28 pixels of one image: past every family's 32-bit byte range, the 3-channel frames' too
+_OPERANDS_FIRST = ("pwc_conv3x3_h2_ex_f32", "pwc_conv3x3_h2_ex3_f32")      # the rules of operands 2 / 3 (their range too) come first
+# (entry point, the bad arguments, the code): one fault per row first, then rows with two faults that pin which one is reported
+_F16_CONV_FAULTS = [(name, bad, code) for name in _F16_CONV_CALLS for bad, code in (
+    (dict(x=None), _EINVAL), (dict(pw=None), _EINVAL), (dict(y=None), _EINVAL),           # a null pointer
+    (dict(N=0), _EINVAL), (dict(H=-1), _EINVAL),                                        # a non-positive size
+    (dict(y_cs=12), _EINVAL),                                                           # a channel stride below the channel count
+    (dict(y=_MIS), _EALIGN), (dict(pw=_MIS), _EALIGN),                                  # a misaligned pointer
+    (dict(y_cs=66), _EALIGN),                                                           # a misaligned channel stride
+    (dict(_BIG), _ERANGE),                                                              # a shape past the 32-bit range
+    (dict(x=None, y=_MIS), _EINVAL), (dict(y_cs=12, y=_MIS), _EINVAL),
+    (dict(_BIG, y=_MIS), _ERANGE if name in _OPERANDS_FIRST else _EALIGN), (dict(_BIG, N=0), _ERANGE if name in _OPERANDS_FIRST else _EINVAL))] + [
+    ("pwc_conv3x3_h2_f32", dict(bias=None), _EINVAL), ("pwc_conv3x3_h2_f32", dict(W=0), _EINVAL), ("pwc_conv3x3_h2_f32", dict(dil=0), _EINVAL),
+    ("pwc_conv3x3_h2_f32", dict(x_cs=48), _EINVAL), ("pwc_conv3x3_h2_f32", dict(x=_MIS), _EALIGN), ("pwc_conv3x3_h2_f32", dict(bias=_MIS), _EALIGN),
+    ("pwc_conv3x3_h2_f32", dict(ws=_MIS), _EALIGN), ("pwc_conv3x3_h2_f32", dict(x_cs=66), _EALIGN),
+    ("pwc_conv3x3_h2_f32", dict(Cout=48), _EUNSUP), ("pwc_conv3x3_h2_f32", dict(Cin=24), _EUNSUP), ("pwc_conv3x3_h2_f32", dict(Cout=1024, y_cs=1024), _EUNSUP),
+    ("pwc_conv3x3_h2_f32", dict(Cin=0), _EINVAL), ("pwc_conv3x3_h2_f32", dict(Cin=-16), _EINVAL),
+    ("pwc_conv3x3_h2_f32", dict(dil=0, Cout=48), _EINVAL), ("pwc_conv3x3_h2_f32", dict(Cout=48, y_cs=32), _EUNSUP),
+    ("pwc_conv3x3_h2_f32", dict(Cin=24, x_cs=16), _EUNSUP), ("pwc_conv3x3_h2_f32", dict(_BIG, ws=_MIS), _EALIGN),
+    ("pwc_conv3x3_h2_ex_f32", dict(x2=_MIS, N=0), _EALIGN), ("pwc_conv3x3_h2_ex_f32", dict(status=_MIS, N=0), _EALIGN),
+    ("pwc_conv3x3_h2_ex_f32", dict(x_cs=16), _EINVAL), ("pwc_conv3x3_h2_ex_f32", dict(x2_cs=16), _EINVAL), ("pwc_conv3x3_h2_ex_f32", dict(Cin_a=24), _EINVAL),
+    ("pwc_conv3x3_h2_ex_f32", dict(Cin_a=64), _EINVAL), ("pwc_conv3x3_h2_ex_f32", dict(x2_cs=34), _EALIGN), ("pwc_conv3x3_h2_ex_f32", dict(Cout=48), _EUNSUP),
+    ("pwc_conv3x3_h2_ex_f32", dict(x2=None, x_cs=32), _EINVAL), ("pwc_conv3x3_h2_ex_f32", dict(x_cs=34), _EALIGN), ("pwc_conv3x3_h2_ex_f32", dict(Cin=72, x2_cs=40), _EUNSUP),
+    ("pwc_conv3x3_h2_ex3_f32", dict(x3=None), _EINVAL), ("pwc_conv3x3_h2_ex3_f32", dict(x_cs=80), _EINVAL), ("pwc_conv3x3_h2_ex3_f32", dict(x3_cs=16), _EINVAL),
+    ("pwc_conv3x3_h2_ex3_f32", dict(Cin_b=24), _EINVAL), ("pwc_conv3x3_h2_ex3_f32", dict(x3=_MIS, Cout=48), _EALIGN), ("pwc_conv3x3_h2_ex3_f32", dict(Cout=48), _EUNSUP),
+    ("pwc_conv3x3_h2_ex3_f32", dict(x_cs=86), _EALIGN),
+    ("pwc_conv3x3_h2_stride2_f32", dict(H=15), _EUNSUP), ("pwc_conv3x3_h2_stride2_f32", dict(Cout=48, y_cs=48), _EUNSUP),
+    ("pwc_conv3x3_h2_stride2_f32", dict(H=15, x_cs=12), _EUNSUP), ("pwc_conv3x3_h2_stride2_f32", dict(x_cs=12), _EINVAL),
+    ("pwc_conv3x3_sk_f32", dict(bias=None), _EINVAL), ("pwc_conv3x3_sk_f32", dict(stride=3), _EINVAL), ("pwc_conv3x3_sk_f32", dict(dil=0), _EINVAL),
+    ("pwc_conv3x3_sk_f32", dict(x_cs=32), _EINVAL), ("pwc_conv3x3_sk_f32", dict(x=_MIS), _EALIGN), ("pwc_conv3x3_sk_f32", dict(x_cs=66), _EALIGN),
+    ("pwc_conv3x3_sk_f32", dict(Cin=48), _EUNSUP), ("pwc_conv3x3_sk_f32", dict(Cout=24), _EUNSUP), ("pwc_conv3x3_sk_f32", dict(Cin=-5), _EINVAL),
+    ("pwc_conv3x3_sk_f32", dict(N=8, H=1024, W=1024), _ERANGE), ("pwc_conv3x3_sk_f32", dict(Cin=48, x_cs=32), _EUNSUP),
+    ("pwc_conv3x3_sk_f32", dict(stride=3, Cin=48), _EINVAL), ("pwc_conv3x3_sk_f32", dict(N=8, H=1024, W=1024, bias=_MIS), _EALIGN),
+    ("pwc_conv3x3_t32_f32", dict(stride=0), _EINVAL), ("pwc_conv3x3_t32_f32", dict(Cin=24, x_cs=32), _EUNSUP), ("pwc_conv3x3_t32_f32", dict(Cout=64, y_cs=64), _EUNSUP),
+    ("pwc_conv3x3_t32_f32", dict(Cin=32, x_cs=32, stride=2), _EUNSUP), ("pwc_conv3x3_t32_f32", dict(stride=3, Cin=24), _EINVAL),
+    ("pwc_conv3x3_t32_f32", dict(Cin=32, x_cs=16), _EINVAL), ("pwc_conv3x3_t32_f32", dict(x=_MIS), _EALIGN), ("pwc_conv3x3_t32_f32", dict(x_cs=18), _EALIGN),
+    ("pwc_conv3x3_t32_f32", dict(N=32, H=1024, W=1024), _ERANGE), ("pwc_conv3x3_t32_f32", dict(N=16, H=1024, W=1024), _ERANGE),       # (the input's range, the output's)
+    ("pwc_conv3x3_t32_f32", dict(N=16, H=1024, W=1024, bias=_MIS), _EALIGN),
+    ("pwc_conv3x3_w32_f32", dict(Cin=16), _EUNSUP), ("pwc_conv3x3_w32_f32", dict(Cout=64, y_cs=64), _EUNSUP), ("pwc_conv3x3_w32_f32", dict(Cin=16, x=_MIS), _EUNSUP),
+    ("pwc_conv3x3_w32_f32", dict(Cin=64), _EINVAL), ("pwc_conv3x3_w32_f32", dict(x_cs=34), _EALIGN), ("pwc_conv3x3_w32_f32", dict(N=16, H=1024, W=1024), _ERANGE),
+    ("pwc_conv3x3_w32_f32", dict(N=8, H=1024, W=1024, y_cs=64), _ERANGE), ("pwc_conv3x3_w32_f32", dict(Cin=0), _EINVAL),
+    ("pwc_conv3x3_c16pair_f32", dict(b2=None), _EINVAL), ("pwc_conv3x3_c16pair_f32", dict(b2=None, x=_MIS), _EINVAL), ("pwc_conv3x3_c16pair_f32", dict(b2=_MIS), _EALIGN),
+    ("pwc_conv3x3_c16pair_f32", dict(_BIG, b2=_MIS), _EALIGN), ("pwc_conv3x3_c16pair_f32", dict(x_cs=12), _EINVAL), ("pwc_conv3x3_c16pair_f32", dict(x_cs=12, y=_MIS), _EINVAL),
+    ("pwc_conv3x3_c16pair_f32", dict(x_cs=18), _EALIGN),
+    ("pwc_conv3x3_c3c16pair_f32", dict(W=62), _EUNSUP), ("pwc_conv3x3_c3c16pair_f32", dict(N_b=1), _EINVAL), ("pwc_conv3x3_c3c16pair_f32", dict(N_b=-1), _EINVAL),
+    ("pwc_conv3x3_c3c16pair_f32", dict(W=62, y=_MIS), _EUNSUP), ("pwc_conv3x3_c3c16pair_f32", dict(W=62, y_cs=12), _EINVAL), ("pwc_conv3x3_c3c16pair_f32", dict(b0=_MIS), _EALIGN),
+]
+
+
+def test_f16_conv_entry_points_report_the_same_codes():
+    """The argument checks of the F16-matrix-pipe conv entry points (conv3x3_h2 / sk / t32 / w32 / c16pair) go through one shared
+    checker (pwc_conv_io_check, pwc_common.h); every family keeps the checks that are its own.  This table pins which code each
+    entry point returns for a bad call -- one fault at a time, then two at once (which one wins) -- as recorded from the
+    library before the checks were shared.  Every row fails a check: nothing is launched, no GPU is needed."""
+    L = _lib.lib()
+    assert all(code != 0 for _, _, code in _F16_CONV_FAULTS)
+    got = []
+    for name, bad, code in _F16_CONV_FAULTS:
+        names, good = _F16_CONV_CALLS[name]
+        assert set(bad) <= set(good), (name, bad)
+        args = dict(good, **bad)
+        rc = getattr(L, name)(*[args[k] for k in names.split()])
+        if rc != code:
+            got.append((name, bad, code, rc))
+    assert not got, got
+
+
 def test_round5_routing_rules_are_host_logic():
     """Which kernel takes which launch is decided by pure host functions of the library (no GPU needed): the small-launch conv
     (up to 1e8 multiply-adds and 4096 output pixels; stride-2 / thin layers beyond), the weights-stationary thin-input conv
