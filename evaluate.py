@@ -5,8 +5,13 @@ train.py:124-131 as a stand-alone tool).
     python evaluate.py --list pairs.txt [--resume model_600.ckpt] [--batch 8] [--save_dir out]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --list ...
 
-pairs.txt: one pair per line, `image_0 image_1 flow_gt.flo`.  Images are cropped to multiples
-of 64 (reference test.py:13-17), scaled to [0,1]; the ground truth is cropped the same way.
+pairs.txt: one pair per line, `image_0 image_1 flow_gt.flo [mask.png]`.  Images are cropped to multiples
+of 64 (reference test.py:13-17), scaled to [0,1]; the ground truth and the mask are cropped the same way.
+Sparse ground truth: pixels whose .flo value is the "unknown" sentinel (|u| or |v| above 1e9, or not finite) are
+left out of every number; the optional fourth column names an 8-bit mask image, non-zero = valid
+(`--mask_is_invalid`: non-zero = INVALID, Sintel's invalid/ images).  The JSON line carries the masked EPE, KITTI's
+Fl-all, the 1/3/5-px error rates and the EPE by motion magnitude (pwcnet_amd.losses.summarize_metrics).  KITTI's
+16-bit flow PNGs are not read here: convert them to .flo plus a mask image first.
 Pairs are sharded contiguously over the ranks (one process per GPU, RCCL only for the final
 all-gather of the statistics / flows); rank 0 prints one JSON line.
 """
@@ -25,6 +30,8 @@ def main():
     ap.add_argument("--resume", default=None)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--save_dir", default=None, help="write every predicted flow as <index>.flo (rank 0, after the gather)")
+    ap.add_argument("--mask_is_invalid", action="store_true",
+                    help="the mask column's images mark INVALID pixels with non-zero values (Sintel's invalid/)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -47,20 +54,29 @@ def main():
         model.load_weights(ckpt.load_weights(args.resume))
 
     def load_pair(i):
-        p0, p1, pf = pairs[i]
+        p0, p1, pf = pairs[i][:3]
         im0 = flow_io.factor_crop(np.asarray(Image.open(p0).convert("RGB")))
         im1 = flow_io.factor_crop(np.asarray(Image.open(p1).convert("RGB")))
-        gt = flow_io.factor_crop(flow_io.read_flo(pf))
+        raw = flow_io.read_flo(pf)
+        gt = flow_io.factor_crop(raw)
+        valid = flow_io.flow_valid(gt)                        # the .flo sentinel
+        if len(pairs[i]) > 3:
+            mask = np.asarray(Image.open(pairs[i][3]).convert("L")) != 0
+            if mask.shape != raw.shape[:2]:
+                raise SystemExit(f"evaluate.py: mask {pairs[i][3]} is {mask.shape}, its flow {raw.shape[:2]}")
+            valid &= flow_io.factor_crop((~mask if args.mask_is_invalid else mask)[..., None])[..., 0]
         return (torch.from_numpy(np.ascontiguousarray(im0, np.float32) / 255.0),
                 torch.from_numpy(np.ascontiguousarray(im1, np.float32) / 255.0),
-                torch.from_numpy(np.ascontiguousarray(gt, np.float32)))
+                torch.from_numpy(np.ascontiguousarray(gt, np.float32)),
+                torch.from_numpy(np.ascontiguousarray(valid)))
 
     def forward(im0, im1):
         return model(im0, im1)[0]
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = sharding.evaluate_pairs(forward, load_pair, len(pairs), args.batch, dist, dev, gather=args.save_dir is not None)
+    res = sharding.evaluate_pairs(forward, load_pair, len(pairs), args.batch, dist, dev, gather=args.save_dir is not None,
+                                  metrics=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if dist is None or dist.get_rank() == 0:
@@ -68,8 +84,10 @@ def main():
             os.makedirs(args.save_dir, exist_ok=True)
             for i, f in enumerate(res["flows"].cpu().numpy()):
                 flow_io.write_flo(os.path.join(args.save_dir, f"{i:06d}.flo"), f)
-        print(json.dumps({"epe": res["epe"], "pairs": res["pairs"], "seconds": dt, "n_gpus": world,
-                          "per_pair_epe": res["per_pair_epe"]}))
+        out = {"epe": res["epe"], "pairs": res["pairs"], "seconds": dt, "n_gpus": world}
+        out.update({k: res[k] for k in ("fl_all", "px1", "px3", "px5", "epe_s0_10", "epe_s10_40", "epe_s40", "valid_px")})
+        out["per_pair_epe"] = res["per_pair_epe"]
+        print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
 

@@ -567,6 +567,39 @@ int pwc_conv3x3_wgrad_f32(const float* x, int x_cs, const float* dy, int dy_cs, 
 int pwc_conv3x3_dgrad_s2_narrow_f32(const float* dy, int dy_cs, const float* w_hwio, float* dx, int dx_cs, int N, int H,
                                     int W, int Cx, int Cy, int accumulate, pwc_stream_t stream);
 
+/* ==== sparse ground truth: the losses, their gradient and the flow metrics under a validity mask ====
+ * `valid` is one byte per pixel of the GROUND TRUTH, uint8_t[N][GH][GW], dense, non-zero = valid; no alignment is asked of
+ * it (byte loads).  It is read at the nearest-neighbour index the ground truth is read at -- floor(y * GH / H), the rounded
+ * fp32 product, clipped: tf.image.resize_nearest_neighbor applied to the mask.  Invalid pixels are SELECTED out: neither pred
+ * nor gt is read there, an invalid pixel adds exactly 0.0f to every sum and exactly 0 to every gradient whatever the two hold
+ * (NaN, Inf, the .flo sentinel 1e10).  Every check precedes the launches: null pointers, sizes <= 0, channel strides < 2,
+ * gt_div == 0, a workspace that is too small: PWC_EINVAL; ord outside {1, 2}: PWC_EUNSUPPORTED; H * W >= 2^31 or N > 65535
+ * (sums and metrics): PWC_ERANGE. */
+
+/* pwc_flow_norm_sums_f32 over the valid pixels: out_sums[n] as there, out_counts[n] = the number of valid pixels of image n
+ * at pred's resolution (exact; an image without valid pixels gives sum 0, count 0).  Deterministic, with the partition and
+ * the order of additions of the unmasked call: an all-ones mask returns its bits. */
+size_t pwc_flow_norm_masked_workspace_floats(int N, int H, int W);
+int pwc_flow_norm_masked_sums_f32(const float* pred, int pred_cs, const float* gt, int gt_cs, const uint8_t* valid,
+                                  int N, int H, int W, int GH, int GW, float gt_div, int ord,
+                                  float* workspace, size_t workspace_floats, float* out_sums, int32_t* out_counts,
+                                  pwc_stream_t stream);
+/* pwc_flow_norm_grad_f32 at the valid pixels (an all-ones mask returns its bits); an invalid pixel's two floats are written
+ * as 0 (accumulate == 0) or left untouched (accumulate != 0).  Channels outside dpred's two floats are never written. */
+int pwc_flow_norm_masked_grad_f32(const float* pred, int pred_cs, const float* gt, int gt_cs, const uint8_t* valid,
+                                  int N, int H, int W, int GH, int GW, float gt_div, int ord, float scale,
+                                  float* dpred, int dpred_cs, int accumulate, pwc_stream_t stream);
+/* Flow metrics of pred against gt, both N x H x W in pixels (flows_final against the ground truth); valid == NULL: every
+ * pixel.  With e = ||pred - gt||_2 and g = ||gt||_2 at a valid pixel, out[n][0..11] =
+ *   n_valid, sum e, n(e > 3 && e > 0.05 g)  [KITTI's outlier rule, Fl], n(e > 1), n(e > 3), n(e > 5),
+ *   n(g < 10), sum e (g < 10), n(10 <= g < 40), sum e (10 <= g < 40), n(g >= 40), sum e (g >= 40).
+ * Counts are added as integers (exact); sums are fp32 block partials added in index order in double: two calls give the
+ * same bits.  One pass over the data; workspace: at least the floats the workspace function names. */
+size_t pwc_flow_metrics_workspace_floats(int N, int H, int W);
+int pwc_flow_metrics_f32(const float* pred, int pred_cs, const float* gt, int gt_cs, const uint8_t* valid,
+                         int N, int H, int W, float* workspace, size_t workspace_floats, double* out,
+                         pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

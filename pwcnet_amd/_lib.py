@@ -21,7 +21,8 @@ LIB_PATH = os.path.join(CSRC, "libpwc_hip_harness.so" if HARNESS else "libpwc_hi
 HARNESS_SIGNATURES_NAMES = ("pwc_debug_cost_volume_blk_rows", "pwc_debug_conv3x3_sk_tile", "pwc_debug_conv3x3_t32",
                             "pwc_debug_h2_reserve_cus")
 SOURCES = ["conv3x3_mfma.hip", "conv3x3_wino.hip", "conv3x3_direct.hip", "cost_volume.hip", "pwc_ops.hip",
-           "pwc_backward.hip", "conv3x3_wgrad.hip", "conv3x3_h2.hip", "conv3x3_c16pair.hip", "conv3x3_sk.hip", "conv3x3_t32.hip", "conv3x3_w32.hip"]
+           "pwc_backward.hip", "conv3x3_wgrad.hip", "conv3x3_h2.hip", "conv3x3_c16pair.hip", "conv3x3_sk.hip", "conv3x3_t32.hip", "conv3x3_w32.hip",
+           "pwc_masked.hip"]
 HEADERS = ["pwc_common.h", "cost_volume_roll.hip", "cost_volume_mfma.hip", "cost_volume_h2.hip", "cost_volume_blk.hip", "conv3x3_wino4.hip", os.path.join("..", "..", "include", "pwc_hip.h")]
 
 _vp, _i, _f, _l, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long, ctypes.c_size_t
@@ -120,6 +121,11 @@ SIGNATURES = {
     "pwc_flow_norm_workspace_floats": (_sz, [_i, _i, _i]),
     "pwc_flow_norm_sums_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp]),
     "pwc_conv3x3_dgrad_s2_narrow_f32": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "pwc_flow_norm_masked_workspace_floats": (_sz, [_i, _i, _i]),
+    "pwc_flow_norm_masked_sums_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp, _vp]),
+    "pwc_flow_norm_masked_grad_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _i, _i, _vp]),
+    "pwc_flow_metrics_workspace_floats": (_sz, [_i, _i, _i]),
+    "pwc_flow_metrics_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
 }
 
 if HARNESS:

@@ -33,6 +33,19 @@ def read_flo(path):
     return data.reshape(h, w, 2)
 
 
+UNKNOWN_FLOW_THRESH = 1e9
+
+
+def flow_valid(flow):
+    """(..., 2) flow -> (...) bool mask of the pixels that carry a measurement, by the .flo convention (reference
+    flow_utils.py:120-135; Middlebury writes 1e10): both components finite and |u|, |v| <= 1e9."""
+    flow = np.asarray(flow)
+    if flow.shape[-1] != 2:
+        raise ValueError(f"flow must be (..., 2), got {flow.shape}")
+    with np.errstate(invalid="ignore"):
+        return np.all(np.isfinite(flow) & (np.abs(flow) <= UNKNOWN_FLOW_THRESH), axis=-1)
+
+
 def color_wheel():
     """(55, 3) RGB in 0..255."""
     segments = [(15, (255, 0, 0), (0, 1, 0)), (6, (255, 255, 0), (-1, 0, 0)), (4, (0, 255, 0), (0, 0, 1)),
@@ -49,7 +62,7 @@ def flow_to_color(flow, max_rad=None):
     (default: the largest magnitude in the field, as reference vis_flow does)."""
     flow = np.asarray(flow, np.float64)
     u, v = flow[..., 0].copy(), flow[..., 1].copy()
-    bad = ~np.isfinite(u) | ~np.isfinite(v) | (np.abs(u) > 1e9) | (np.abs(v) > 1e9)
+    bad = ~flow_valid(flow)
     u[bad] = 0
     v[bad] = 0
     rad = np.sqrt(u * u + v * v)

@@ -148,11 +148,34 @@ def cost_volume_grad(f0, f1w, cv, dcv, df0=None, df1w=None, accumulate=False, se
         1 if accumulate else 0, f0.N, f0.H, f0.W, f0.C, int(search_range), float(slope), _s()), "cost_volume_grad")
 
 
-def flow_norm_grad(pred, gt, dpred, gt_div=1.0, ord=2, scale=1.0, accumulate=False):
-    """dpred (+)= scale * d/dpred sum_p ||pred - nearest_downsample(gt) / gt_div||_ord."""
-    _lib.check(_L().pwc_flow_norm_grad_f32(_p(pred.ptr), pred.cs, _p(gt.ptr), gt.cs, pred.N, pred.H, pred.W, gt.H, gt.W,
-                                           float(gt_div), int(ord), float(scale), _p(dpred.ptr), dpred.cs,
-                                           1 if accumulate else 0, _s()), "flow_norm_grad")
+def mask_ptr(valid, N, GH, GW, device=None):
+    """Address of a validity mask for the masked kernels: a torch.bool or torch.uint8 tensor of shape (N, GH, GW), one
+    byte per ground-truth pixel, non-zero = valid; contiguous and on the GPU (`device`: the flows').  TypeError for another
+    dtype, ValueError for another shape, layout or device -- raised here, before the library is called."""
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"valid: expected a torch.bool or torch.uint8 tensor, got "
+                        f"{valid.dtype if isinstance(valid, torch.Tensor) else type(valid)}")
+    if tuple(valid.shape) != (N, GH, GW):
+        raise ValueError(f"valid: expected shape {(N, GH, GW)} (the ground truth's N, H, W), got {tuple(valid.shape)}")
+    if not valid.is_contiguous():
+        raise ValueError("valid: the mask must be contiguous")
+    if not valid.is_cuda or (device is not None and valid.device != device):
+        raise ValueError(f"valid: the mask is on {valid.device}, the flows are on {device if device is not None else 'the GPU'}")
+    return _p(valid.data_ptr())
+
+
+def flow_norm_grad(pred, gt, dpred, gt_div=1.0, ord=2, scale=1.0, accumulate=False, valid=None):
+    """dpred (+)= scale * d/dpred sum_p ||pred - nearest_downsample(gt) / gt_div||_ord.  valid (mask_ptr's format, at gt's
+    resolution): the sum runs over the valid pixels only; an invalid pixel's gradient is 0 (accumulate: it is left alone)."""
+    if valid is None:
+        _lib.check(_L().pwc_flow_norm_grad_f32(_p(pred.ptr), pred.cs, _p(gt.ptr), gt.cs, pred.N, pred.H, pred.W, gt.H, gt.W,
+                                               float(gt_div), int(ord), float(scale), _p(dpred.ptr), dpred.cs,
+                                               1 if accumulate else 0, _s()), "flow_norm_grad")
+        return
+    vp = mask_ptr(valid, gt.N, gt.H, gt.W)
+    _lib.check(_L().pwc_flow_norm_masked_grad_f32(_p(pred.ptr), pred.cs, _p(gt.ptr), gt.cs, vp, pred.N, pred.H, pred.W, gt.H,
+                                                  gt.W, float(gt_div), int(ord), float(scale), _p(dpred.ptr), dpred.cs,
+                                                  1 if accumulate else 0, _s()), "flow_norm_masked_grad")
 
 
 def adam_step_(params, grads, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, l2_gamma=0.0, grad_scale=1.0):

@@ -87,18 +87,25 @@ def gather_flows(flows, n_total, dist=None):
     return torch.cat([p[:s] for p, s in zip(parts, sizes)], dim=0)
 
 
-def evaluate_pairs(forward, load_pair, n_pairs, batch=8, dist=None, device="cpu", gather=False):
+def evaluate_pairs(forward, load_pair, n_pairs, batch=8, dist=None, device="cpu", gather=False, metrics=False):
     """Sharded evaluation loop (counterpart of the validation block of reference
     train.py:124-131 without TensorFlow): every rank runs `forward(images_0, images_1) ->
     flows_final` on its shard_range slice of the pairs, `load_pair(i) -> (image_0, image_1,
     flow_gt)` as (h,w,3),(h,w,3),(h,w,2) float tensors.  Returns a dict with the global
     pixel-weighted EPE, the per-pair EPEs in pair order and, if `gather`, all predicted flows
-    (all pairs must then have one size)."""
+    (all pairs must then have one size).
+
+    Sparse ground truth: `load_pair` may return a fourth item, `valid` (h,w) torch.bool / torch.uint8 (non-zero = the
+    pixel carries a label; None for a dense pair).  `epe` and `per_pair_epe` are then masked -- weighted by the valid
+    pixels, whatever the ground truth holds elsewhere; a pair without a valid pixel counts 0.0 and weighs nothing.
+    `metrics`: also sum losses.flow_metrics over the pairs (the twelve sums ride in the same all-gather as the other
+    statistics) and add the keys of losses.summarize_metrics (fl_all, px1/3/5, epe_s0_10/s10_40/s40, valid_px)."""
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     lo, hi = shard_range(n_pairs, world, rank)
     per_pair, flows_out = [], []
     err_sum, px_sum = 0.0, 0.0
+    msum = [0.0] * 12
     i = lo
     while i < hi:
         items = [load_pair(j) for j in range(i, min(i + batch, hi))]
@@ -110,17 +117,44 @@ def evaluate_pairs(forward, load_pair, n_pairs, batch=8, dist=None, device="cpu"
         im0 = torch.stack([it[0] for it in items]).to(device)
         im1 = torch.stack([it[1] for it in items]).to(device)
         gt = torch.stack([it[2] for it in items]).to(device)
+        masks = [it[3] if len(it) > 3 else None for it in items]
+        valid = None
+        if any(m is not None for m in masks):
+            valid = torch.stack([torch.ones(gt.shape[1:3], dtype=torch.bool) if m is None else torch.as_tensor(m).bool()
+                                 for m in masks]).to(device)
         flows = forward(im0, im1)
-        norms = torch.linalg.vector_norm(gt - flows, ord=2, dim=3)          # (k, h, w)
-        per_pair.extend(norms.mean(dim=(1, 2)).double().cpu().tolist())
-        err_sum += float(norms.double().sum())
-        px_sum += float(norms.numel())
+        if metrics:
+            from . import losses
+            m = losses.flow_metrics(gt, flows.contiguous(), valid).cpu()                    # (k, 12) float64
+            per_pair.extend(torch.where(m[:, 0] > 0, m[:, 1] / m[:, 0].clamp(min=1.0), torch.zeros_like(m[:, 1])).tolist())
+            err_sum += float(m[:, 1].sum())
+            px_sum += float(m[:, 0].sum())
+            msum = [a + b for a, b in zip(msum, m.sum(0).tolist())]
+        elif valid is not None:
+            diff = torch.where(valid.unsqueeze(3), gt - flows, torch.zeros((), dtype=flows.dtype, device=flows.device))
+            norms = torch.linalg.vector_norm(diff, ord=2, dim=3).double()                   # 0 at the invalid pixels
+            cnt = valid.reshape(k, -1).sum(1).double()
+            per_pair.extend((norms.reshape(k, -1).sum(1) / cnt.clamp(min=1.0)).cpu().tolist())
+            err_sum += float(norms.sum())
+            px_sum += float(cnt.sum())
+        else:
+            norms = torch.linalg.vector_norm(gt - flows, ord=2, dim=3)          # (k, h, w)
+            per_pair.extend(norms.mean(dim=(1, 2)).double().cpu().tolist())
+            err_sum += float(norms.double().sum())
+            px_sum += float(norms.numel())
         if gather:
             flows_out.append(flows.clone())
         i += k
-    stats = gather_stats({"err": err_sum, "px": px_sum, "n": float(hi - lo)}, dist if world > 1 else None, device)
+    mine = {"err": err_sum, "px": px_sum, "n": float(hi - lo)}
+    if metrics:
+        mine.update({f"m{j:02d}": v for j, v in enumerate(msum)})
+    stats = gather_stats(mine, dist if world > 1 else None, device)
     res = {"epe": sum(s["err"] for s in stats) / max(sum(s["px"] for s in stats), 1.0),
            "pairs": int(sum(s["n"] for s in stats))}
+    if metrics:
+        from . import losses
+        res.update(losses.summarize_metrics(torch.tensor([sum(s[f"m{j:02d}"] for s in stats) for j in range(12)],
+                                                         dtype=torch.float64)))
     mine = torch.tensor(per_pair, dtype=torch.float64, device=device).reshape(-1, 1, 1, 1)
     res["per_pair_epe"] = gather_flows(mine, n_pairs, dist if world > 1 else None).reshape(-1).cpu().tolist()
     if gather:

@@ -407,41 +407,46 @@ class Trainer(_Net):
         self._tape = self._forward(images_0, images_1)
         return self._tape.flows_pyramid
 
-    def _level_loss_scale(self, l, flows_gt):
-        """(ord, scale) of level l's loss term for flow_norm_grad: d/dpred of scale * sum_p ||pred - gt||_ord."""
+    def _level_loss_scale(self, l, flows_gt, valid=None):
+        """(ord, scale) of level l's loss term for flow_norm_grad: d/dpred of scale * sum_p ||pred - gt||_ord (with a mask:
+        the sum over the valid pixels, and the robust loss's L1 is the masked one)."""
         N = flows_gt.shape[0]
         wl = self.loss_weights[l]
         if self.loss == "multiscale":
             return 2, wl / N                                               # weight * mean_n sum_p ||.||_2
         from . import losses
-        l1 = float(losses._norm_sums(self.flows_pyramid[l], flows_gt, 1, gt_div=20.0)[0].mean())   # L1loss(gt_down, fs)
+        l1 = float(losses._norm_sums(self.flows_pyramid[l], flows_gt, 1, gt_div=20.0, valid=valid)[0].mean())   # L1loss(gt_down, fs)
         return 1, wl * self.q * (l1 + self.epsilon) ** (self.q - 1.0) / N
 
-    def backward(self, flows_gt):
+    def backward(self, flows_gt, valid=None):
         """Gradients of the level losses (losses.py:15-32 / :34-48) w.r.t. every variable, into self.grads (the
-        gamma * l2_loss term is applied by the optimiser kernel)."""
+        gamma * l2_loss term is applied by the optimiser kernel).  valid: (N,H,W) torch.bool / torch.uint8 mask of the
+        ground truth's labelled pixels (None: all of them, the path without a mask): the five level gradients are seeded by
+        the masked kernel -- 0 at every invalid pixel, whatever flows_gt holds there -- and the rest is the same backward."""
         G.F16X2, G.F16X2_DGRAD = self.f16x2, self.f16x2_dgrad
         dev = self.device
         N = flows_gt.shape[0]
         gt = View(flows_gt.data_ptr(), 2, N, flows_gt.shape[1], flows_gt.shape[2], 2)
+        masked = {} if valid is None else {"valid": valid}
         self.grads.zero_()
         # loss gradient of every pyramid flow
         dflows = []
         for l, L in enumerate(self.levels):
             fl = self.flows_pyramid[l]
             d = torch.empty_like(fl)
-            order, scale = self._level_loss_scale(l, flows_gt)
+            order, scale = self._level_loss_scale(l, flows_gt, valid)
             G.flow_norm_grad(View(fl.data_ptr(), 2, N, fl.shape[1], fl.shape[2], 2), gt,
-                             View(d.data_ptr(), 2, N, fl.shape[1], fl.shape[2], 2), gt_div=20.0, ord=order, scale=scale)
+                             View(d.data_ptr(), 2, N, fl.shape[1], fl.shape[2], 2), gt_div=20.0, ord=order, scale=scale,
+                             **masked)
             dflows.append(d)
         self._backward_from(self._tape, dflows, self.grads)
 
     # ------------------------------------------------------------------ step
-    def loss_value(self, flows_gt):
+    def loss_value(self, flows_gt, valid=None):
         from . import losses
         if self.loss == "robust":
-            return losses.multirobust_loss(flows_gt, self.flows_pyramid, self.loss_weights, self.epsilon, self.q)
-        return losses.multiscale_loss(flows_gt, self.flows_pyramid, self.loss_weights)
+            return losses.multirobust_loss(flows_gt, self.flows_pyramid, self.loss_weights, self.epsilon, self.q, valid=valid)
+        return losses.multiscale_loss(flows_gt, self.flows_pyramid, self.loss_weights, valid=valid)
 
     def status(self):
         """Status words of the training path's F16-pipe launches since the last call (synchronises): 0, or
@@ -449,11 +454,12 @@ class Trainer(_Net):
         workspaces have been refilled: repeat the step)."""
         return G.read_status()
 
-    def step(self, images_0, images_1, flows_gt):
-        """One optimisation step (reference train.py:66-92, 114-118).  Returns the data loss (without the L2 term)."""
+    def step(self, images_0, images_1, flows_gt, valid=None):
+        """One optimisation step (reference train.py:66-92, 114-118).  Returns the data loss (without the L2 term).
+        valid: the mask of backward() for sparse ground truth; None is the dense step."""
         self.forward(images_0, images_1)
-        loss = self.loss_value(flows_gt)
-        self.backward(flows_gt)
+        loss = self.loss_value(flows_gt, valid)
+        self.backward(flows_gt, valid)
         world = allreduce_sum_(self.grads, self.dist)         # RCCL: one 20 MB collective per step
         self.global_step += 1
         t = self.global_step

@@ -14,6 +14,12 @@ Dataset: the reference's loaders live in its empty `datahandler` submodule; here
 MPI-Sintel-style pairs  <dir>/<pass>/<seq>/frame_NNNN.png  with  <dir>/flow/<seq>/frame_NNNN.flo , or, with
 `--dataset synthetic`, random translating textures with known flow are generated (no files needed).
 Both use_dc settings and both losses (multiscale, robust) are implemented (Trainer docstring).
+
+Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
+and-ed with <dir>/invalid/<seq>/frame_NNNN.png (non-zero = invalid, MPI-Sintel's layout) where that file exists -- and
+the step's loss and gradient and the validation numbers (masked EPE, KITTI's Fl-all) leave the invalid pixels out.
+`--synthetic_invalid F` knocks a random fraction F of the synthetic ground truth out and writes 1e10 there.  KITTI's
+16-bit flow PNGs are not read: convert them to .flo (sentinel at the unlabelled pixels) first.
 """
 import argparse
 import glob
@@ -36,10 +42,12 @@ def sintel_pairs(root, render="clean"):
 
 
 class SyntheticPairs:
-    """Random smooth textures translated by a per-pair integer shift; ground truth = that shift."""
+    """Random smooth textures translated by a per-pair integer shift; ground truth = that shift.  invalid: the fraction of
+    the pixels (a seeded random set per pair) whose label is knocked out: mask False and ground truth 1e10, the .flo
+    sentinel, so that a consumer that ignored the mask would show it at once."""
 
-    def __init__(self, n, shape, seed=0):
-        self.n, self.shape, self.seed = n, shape, seed
+    def __init__(self, n, shape, seed=0, invalid=0.0):
+        self.n, self.shape, self.seed, self.invalid = n, shape, seed, float(invalid)
 
     def __len__(self):
         return self.n
@@ -54,7 +62,11 @@ class SyntheticPairs:
         im1 = big[16 - sy:16 - sy + h, 16 - sx:16 - sx + w]       # im1(p) = im0(p - s): content moves by +s
         flow = np.empty((h, w, 2), np.float32)
         flow[..., 0], flow[..., 1] = sx, sy
-        return np.ascontiguousarray(im0), np.ascontiguousarray(im1), flow
+        valid = np.ones((h, w), bool)
+        if self.invalid > 0:
+            valid = np.random.RandomState(self.seed + 7919 * (i + 1)).uniform(size=(h, w)) >= self.invalid
+            flow[~valid] = 1e10
+        return np.ascontiguousarray(im0), np.ascontiguousarray(im1), flow, valid
 
 
 class FilePairs:
@@ -71,18 +83,24 @@ class FilePairs:
         a, b, f = self.pairs[i]
         im0, im1 = (np.asarray(Image.open(p).convert("RGB"), np.float32) for p in (a, b))
         flow = flow_io.read_flo(f)
+        valid = flow_io.flow_valid(flow)
+        inv = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(f))), "invalid",
+                           os.path.basename(os.path.dirname(f)), os.path.basename(f).replace(".flo", ".png"))
+        if os.path.exists(inv):
+            valid &= np.asarray(Image.open(inv).convert("L")) == 0
         ch, cw = self.crop
         H, W = im0.shape[:2]
         y0 = self.rng.randint(0, H - ch + 1) if self.crop_type == "random" else (H - ch) // 2
         x0 = self.rng.randint(0, W - cw + 1) if self.crop_type == "random" else (W - cw) // 2
         sl = (slice(y0, y0 + ch), slice(x0, x0 + cw))
-        return np.ascontiguousarray(im0[sl]), np.ascontiguousarray(im1[sl]), np.ascontiguousarray(flow[sl])
+        return (np.ascontiguousarray(im0[sl]), np.ascontiguousarray(im1[sl]), np.ascontiguousarray(flow[sl]),
+                np.ascontiguousarray(valid[sl]))
 
 
 def batches(ds, idx, bs):
     for i in range(0, len(idx) - bs + 1, bs):                       # drop_last, like the reference's loader
         items = [ds[j] for j in idx[i:i + bs]]
-        yield tuple(torch.from_numpy(np.stack([it[k] for it in items])) for k in range(3))
+        yield tuple(torch.from_numpy(np.stack([it[k] for it in items])) for k in range(4))
 
 
 def main():
@@ -111,6 +129,8 @@ def main():
     ap.add_argument("--gamma", type=float, default=0.0004, help="Coefficient for weight decay [4e-4]")
     ap.add_argument("-r", "--resume", type=str, default=None, help="Learned parameter checkpoint prefix [None]")
     ap.add_argument("--synthetic_pairs", type=int, default=64, help="pairs per epoch with --dataset synthetic")
+    ap.add_argument("--synthetic_invalid", type=float, default=0.0,
+                    help="fraction of the synthetic ground truth knocked out (mask False, flow 1e10) [0]")
     ap.add_argument("--val_fraction", type=float, default=0.1)
     ap.add_argument("--model_dir", type=str, default="./model")
     args = ap.parse_args()
@@ -121,6 +141,8 @@ def main():
         ap.error("training supports --num_levels 6 --search_range 4 (the reference's scales and *20 hard-code 6 levels)")
     if not 0 <= args.output_level < args.num_levels:
         ap.error("--output_level must be in [0, num_levels)")
+    if not 0.0 <= args.synthetic_invalid < 1.0:
+        ap.error("--synthetic_invalid must be in [0, 1)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -139,7 +161,7 @@ def main():
     from pwcnet_amd.train import Trainer
 
     if args.dataset == "synthetic":
-        ds = SyntheticPairs(args.synthetic_pairs, tuple(args.crop_shape))
+        ds = SyntheticPairs(args.synthetic_pairs, tuple(args.crop_shape), invalid=args.synthetic_invalid)
     else:
         if not args.dataset_dir:
             raise SystemExit("train.py: --dataset_dir is required for file datasets")
@@ -168,8 +190,10 @@ def main():
             dist.all_reduce(st, op=dist.ReduceOp.MIN)
             steps = int(st.item())
         t0, loss_sum, n_steps = time.time(), 0.0, 0
-        for images_0, images_1, flows_gt in batches(ds, order[lo:lo + steps * args.batch_size], args.batch_size):
-            loss = trainer.step((images_0 / 255.0).cuda(), (images_1 / 255.0).cuda(), flows_gt.cuda())
+        for images_0, images_1, flows_gt, valid in batches(ds, order[lo:lo + steps * args.batch_size], args.batch_size):
+            # a dense batch takes the step without a mask (the same kernels as before masks existed)
+            loss = trainer.step((images_0 / 255.0).cuda(), (images_1 / 255.0).cuda(), flows_gt.cuda(),
+                                None if bool(valid.all()) else valid.cuda())
             loss_sum += float(loss)
             n_steps += 1
         # validation: EPE of flows_final (reference train.py:77,124-131), sharded over the ranks
@@ -179,10 +203,11 @@ def main():
         net.load_weights(trainer.state_dict())
         res = sharding.evaluate_pairs(lambda a, b: net(a / 255.0, b / 255.0)[0],
                                       lambda i: tuple(torch.from_numpy(x) for x in ds[val_idx[i]]),
-                                      len(val_idx), batch=args.batch_size, dist=dist, device="cuda")
+                                      len(val_idx), batch=args.batch_size, dist=dist, device="cuda", metrics=True)
         if rank == 0:
             dt = time.time() - t0
             print(f"epoch {e + 1}: loss/pwc {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
+                  f"Fl-all/val {res['fl_all']:.4f}  "
                   f"global_step {trainer.global_step}  {n_steps * args.batch_size * world / max(dt, 1e-9):.1f} pairs/s")
             os.makedirs(args.model_dir, exist_ok=True)
             ckpt.save_weights(os.path.join(args.model_dir, f"model_{e + 1}.ckpt"), trainer.state_dict())
