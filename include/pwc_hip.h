@@ -600,6 +600,49 @@ int pwc_flow_metrics_f32(const float* pred, int pred_cs, const float* gt, int gt
                          int N, int H, int W, float* workspace, size_t workspace_floats, double* out,
                          pwc_stream_t stream);
 
+/* ==== self-supervised losses: the photometric warp term and the edge-aware smoothness of the flow ====
+ * Two loss terms that need no ground truth, each as per-image sums (a deterministic two-stage reduction: workgroup partials in
+ * `workspace`, added in index order) and as the gradient of those sums with respect to the flow (a gather, one lane per pixel,
+ * no atomics: deterministic).  All tensors NHWC fp32, pointer + channel stride; images have C = 1..4 channels and no alignment
+ * is asked of anything (scalar loads).  The images are constants: no gradient reaches them.
+ *   rho(d) = (d^2 + eps^2)^q  (generalised Charbonnier),  rho'(d) = 2 q d (d^2 + eps^2)^(q - 1).
+ * Every check precedes the launches: null pointers other than the optional ones, sizes <= 0, a channel stride below the
+ * channel count, eps <= 0, q outside (0, 1], alpha < 0, a workspace that is too small: PWC_EINVAL; C outside 1..4:
+ * PWC_EUNSUPPORTED; H * W >= 2^31 or N > 65535: PWC_ERANGE. */
+
+/* Photometric term.  Pixel p = (n, y, x) samples images_1[n] at (py, px) = (y + flow_scale * flow[p,1], x + flow_scale *
+ * flow[p,0]) and CONTRIBUTES iff (valid == NULL or valid[p] != 0, uint8_t[N][H][W]) and 0 <= px <= W - 1 and 0 <= py <= H - 1
+ * (a NaN or Inf flow fails the test).  Other pixels are selected out: no image is read for them and, where the mask rules them
+ * out, no flow either.  The sample is the bilinear warp's: x0 = floor(px), x1 = min(x0 + 1, W - 1), weight px - x0 on x1, the
+ * same in y.  out_sums[n] = sum over the contributing pixels of sum_c rho(images_0[p,c] - sample[c]); out_counts[n] = their
+ * number (exact).  The sample point, the weights and the difference are computed in double and the difference is rounded to
+ * fp32 once, so that rho' does not magnify a rounding error of the interpolation by 1 / eps. */
+size_t pwc_photometric_workspace_floats(int N, int H, int W);
+int pwc_photometric_sums_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
+                             float flow_scale, const uint8_t* valid, int N, int H, int W, int C, float eps, float q,
+                             float* workspace, size_t workspace_floats, float* out_sums, int32_t* out_counts,
+                             pwc_stream_t stream);
+/* dflow[p,0] (+)= dsums[n] * flow_scale * sum_c rho'(d_c) * (-d sample_c / d px), dflow[p,1] likewise along y (floor and clip
+ * carry no gradient, as in the warp's own gradient).  dsums: N floats ON THE DEVICE, the upstream gradient of out_sums (no host
+ * synchronisation).  A pixel that does not contribute gets 0 (accumulate == 0) or is left untouched (accumulate != 0). */
+int pwc_photometric_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
+                             float flow_scale, const uint8_t* valid, int N, int H, int W, int C, float eps, float q,
+                             const float* dsums, float* dflow, int dflow_cs, int accumulate, pwc_stream_t stream);
+
+/* Smoothness term, first order, forward differences: out_sums[n] = sum over the pixels with x < W - 1 of
+ * wx(p) * sum_k rho(flow[n,y,x+1,k] - flow[n,y,x,k]), wx(p) = exp(-alpha * mean_c |image[n,y,x+1,c] - image[n,y,x,c]|), plus
+ * the same along y for y < H - 1.  image: at the flow's resolution, C channels; NULL: every weight is 1 (C and image_cs are
+ * then ignored; a constant image gives the same bits). */
+size_t pwc_flow_smoothness_workspace_floats(int N, int H, int W);
+int pwc_flow_smoothness_sums_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
+                                 float eps, float q, int N, int H, int W, float* workspace, size_t workspace_floats,
+                                 float* out_sums, pwc_stream_t stream);
+/* dflow (+)= dsums[n] * d out_sums[n] / d flow: every lane gathers the up to four differences its pixel takes part in (its
+ * own along x and y, its left and its upper neighbour's). */
+int pwc_flow_smoothness_grad_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
+                                 float eps, float q, int N, int H, int W, const float* dsums, float* dflow, int dflow_cs,
+                                 int accumulate, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

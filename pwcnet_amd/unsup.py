@@ -1,0 +1,212 @@
+"""Losses that need no ground-truth flow, on the HIP path: the photometric warp term and the edge-aware smoothness term.
+
+    photometric_sums(images_0, images_1, flows, ...)  -> (sums (N,), counts (N,) int32)
+    photometric_loss(...)                              -> sums.sum() / (C * counts.sum().clamp(min=1))
+    smoothness_sums(flows, images=None, ...)           -> sums (N,)
+    smoothness_loss(...)                               -> sums.sum() / (N * H * W)
+
+With rho(d) = (d^2 + eps^2)^q: the photometric term of a pixel is sum_c rho(images_0 - bilinear sample of images_1 at the pixel
+moved by flow_scale * flow), over the pixels that are valid (`valid`, grad_ops.mask_ptr's format, e.g. an occlusion mask of the
+caller's) and whose sample point lies inside the frame; the smoothness term is the sum of exp(-alpha * mean_c |d image|) *
+rho(d flow) over the forward differences along x and y (include/pwc_hip.h, "self-supervised losses").
+`sums` is differentiable with respect to `flows` (pwc_photometric_grad_f32 / pwc_flow_smoothness_grad_f32: gathers, bit
+reproducible), so the losses compose with PWCDCNetModule; the images are constants -- an image that requires grad is refused.
+No double backward.
+"""
+import torch
+
+from . import _lib
+from .grad_ops import mask_ptr
+from .modules import _p, _pixel_dense, as_view
+
+
+def _check_rho(eps, q, what):
+    eps, q = float(eps), float(q)
+    if not eps > 0.0:
+        raise ValueError(f"{what}: eps must be positive, got {eps}")
+    if not 0.0 < q <= 1.0:
+        raise ValueError(f"{what}: q must be in (0, 1], got {q}")
+    return eps, q
+
+
+def _check_nhwc(t, what, channels):
+    """dtype (TypeError) and shape (ValueError) of an NHWC float32 argument -- mask_ptr's exception types.  The device is checked
+    last of all (_check_gpu), so that every other fault of a call is reported whatever machine it is made on."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"{what}: expected a torch.float32 tensor, got {t.dtype if isinstance(t, torch.Tensor) else type(t)}")
+    if t.dim() != 4 or t.shape[3] not in channels:
+        raise ValueError(f"{what}: expected an NHWC tensor with {' or '.join(str(c) for c in channels)} channels, "
+                         f"got shape {tuple(t.shape)}")
+
+
+def _check_image(t, what, like):
+    _check_nhwc(t, what, (1, 2, 3, 4))
+    if tuple(t.shape[:3]) != tuple(like.shape[:3]):
+        raise ValueError(f"{what}: expected (N,H,W) {tuple(like.shape[:3])}, the flows', got {tuple(t.shape[:3])}")
+    if t.requires_grad:
+        raise ValueError(f"{what}: gradients with respect to the images are not implemented (the image requires grad); "
+                         "detach it")
+
+
+def _check_gpu(flows, **others):
+    for what, t in dict(flows=flows, **others).items():
+        if not t.is_cuda or t.device != flows.device:
+            raise ValueError(f"{what}: the tensor is on {t.device}; pwcnet_amd runs on the GPU only, all arguments on one device")
+
+
+def _dflow_view(dflow, fv, dev):
+    """The gradient's destination: a new dense tensor, or the caller's (N,H,W,2) tensor / channel slice of a wider buffer."""
+    if dflow is None:
+        dflow = torch.empty((fv.N, fv.H, fv.W, 2), dtype=torch.float32, device=dev)
+    _check_nhwc(dflow, "dflow", (2,))
+    _check_gpu(dflow)
+    if tuple(dflow.shape) != (fv.N, fv.H, fv.W, 2) or dflow.device != dev or not _pixel_dense(dflow):
+        raise ValueError(f"dflow: expected a pixel-dense {(fv.N, fv.H, fv.W, 2)} tensor on {dev}, got {tuple(dflow.shape)} "
+                         f"strides {dflow.stride()} on {dflow.device}")
+    return as_view(dflow, "dflow")[0], dflow
+
+
+def photometric_grad(images_0, images_1, flows, dsums, dflow=None, flow_scale=1.0, valid=None, eps=1e-3, q=0.5,
+                     accumulate=False):
+    """dflow (+)= the gradient of (dsums * photometric_sums(...)[0]).sum() w.r.t. flows (pwc_photometric_grad_f32); dsums:
+    (N,) on the GPU.  dflow None: a new tensor; accumulate: added onto dflow, pixels that do not contribute are left alone
+    (without it they get 0).  Returns dflow.  What the autograd backward of photometric_sums calls."""
+    vp = None if valid is None else mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+    fv, flows = as_view(flows, "flows")
+    v0, images_0 = as_view(images_0, "images_0")
+    v1, images_1 = as_view(images_1, "images_1")
+    up = torch.empty((fv.N,), dtype=torch.float32, device=flows.device).copy_(dsums)       # contiguous float32, its own
+    dv, dflow = _dflow_view(dflow, fv, flows.device)
+    _lib.check(_lib.lib().pwc_photometric_grad_f32(_p(v0.ptr), v0.cs, _p(v1.ptr), v1.cs, _p(fv.ptr), fv.cs, float(flow_scale),
+                                                   vp, fv.N, fv.H, fv.W, v0.C, float(eps), float(q), _p(up.data_ptr()),
+                                                   _p(dv.ptr), dv.cs, 1 if accumulate else 0, _lib.current_stream()),
+               "photometric grad")
+    return dflow
+
+
+def smoothness_grad(flows, dsums, dflow=None, images=None, alpha=10.0, eps=1e-3, q=0.5, accumulate=False):
+    """dflow (+)= the gradient of (dsums * smoothness_sums(...)).sum() w.r.t. flows (pwc_flow_smoothness_grad_f32)."""
+    fv, flows = as_view(flows, "flows")
+    iv = None
+    if images is not None:
+        iv, images = as_view(images, "images")
+    up = torch.empty((fv.N,), dtype=torch.float32, device=flows.device).copy_(dsums)
+    dv, dflow = _dflow_view(dflow, fv, flows.device)
+    _lib.check(_lib.lib().pwc_flow_smoothness_grad_f32(_p(fv.ptr), fv.cs, _p(iv.ptr) if iv is not None else None,
+                                                       iv.cs if iv is not None else 0, iv.C if iv is not None else 0,
+                                                       float(alpha), float(eps), float(q), fv.N, fv.H, fv.W,
+                                                       _p(up.data_ptr()), _p(dv.ptr), dv.cs, 1 if accumulate else 0,
+                                                       _lib.current_stream()), "flow smoothness grad")
+    return dflow
+
+
+class _PhotometricSums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, images_0, images_1, flow_scale, valid, eps, q):
+        ctx.set_materialize_grads(False)
+        vp = None if valid is None else mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+        fv, flows = as_view(flows, "flows")
+        v0, images_0 = as_view(images_0, "images_0")
+        v1, images_1 = as_view(images_1, "images_1")
+        L = _lib.lib()
+        dev = flows.device
+        sums = torch.empty((fv.N,), dtype=torch.float32, device=dev)
+        counts = torch.empty((fv.N,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(L.pwc_photometric_workspace_floats(fv.N, fv.H, fv.W), 1),), dtype=torch.float32, device=dev)
+        _lib.check(L.pwc_photometric_sums_f32(_p(v0.ptr), v0.cs, _p(v1.ptr), v1.cs, _p(fv.ptr), fv.cs, flow_scale, vp,
+                                              fv.N, fv.H, fv.W, v0.C, eps, q, _p(ws.data_ptr()), ws.numel(),
+                                              _p(sums.data_ptr()), _p(counts.data_ptr()), _lib.current_stream()),
+                   "photometric sums")
+        ctx.save_for_backward(flows, images_0, images_1)
+        ctx.valid, ctx.consts = valid, (flow_scale, eps, q)
+        ctx.mark_non_differentiable(counts)
+        return sums, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dsums, _dcounts):
+        if dsums is None or not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        flows, images_0, images_1 = ctx.saved_tensors
+        flow_scale, eps, q = ctx.consts
+        dflow = photometric_grad(images_0, images_1, flows, dsums, None, flow_scale, ctx.valid, eps, q)
+        return dflow, None, None, None, None, None, None
+
+
+class _SmoothnessSums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, images, alpha, eps, q):
+        ctx.set_materialize_grads(False)
+        fv, flows = as_view(flows, "flows")
+        iv = None
+        if images is not None:
+            iv, images = as_view(images, "images")
+        L = _lib.lib()
+        dev = flows.device
+        sums = torch.empty((fv.N,), dtype=torch.float32, device=dev)
+        ws = torch.empty((max(L.pwc_flow_smoothness_workspace_floats(fv.N, fv.H, fv.W), 1),), dtype=torch.float32, device=dev)
+        _lib.check(L.pwc_flow_smoothness_sums_f32(_p(fv.ptr), fv.cs, _p(iv.ptr) if iv is not None else None,
+                                                  iv.cs if iv is not None else 0, iv.C if iv is not None else 0, alpha, eps, q,
+                                                  fv.N, fv.H, fv.W, _p(ws.data_ptr()), ws.numel(), _p(sums.data_ptr()),
+                                                  _lib.current_stream()), "flow smoothness sums")
+        if images is None:
+            ctx.save_for_backward(flows)
+        else:
+            ctx.save_for_backward(flows, images)
+        ctx.consts = (alpha, eps, q)
+        return sums
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dsums):
+        if dsums is None or not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        flows, *images = ctx.saved_tensors
+        alpha, eps, q = ctx.consts
+        return smoothness_grad(flows, dsums, None, images[0] if images else None, alpha, eps, q), None, None, None, None
+
+
+def photometric_sums(images_0, images_1, flows, flow_scale=1.0, valid=None, eps=1e-3, q=0.5):
+    """(sums (N,) float32, counts (N,) int32): per image, the sum over the contributing pixels of sum_c rho(images_0 -
+    images_1 sampled at the pixel moved by flow_scale * flows), rho(d) = (d^2 + eps^2)^q, and the number of contributing
+    pixels -- valid ones (valid: (N,H,W) torch.bool / torch.uint8, None = all) whose sample point is inside the frame.
+    images: (N,H,W,C), C = 1..4, at the flows' resolution; flows: (N,H,W,2).  flow_scale: 20 / 2^level takes the pyramid
+    flows (px / 20 at the level's size) with images the caller has downsampled.  sums is differentiable w.r.t. flows."""
+    eps, q = _check_rho(eps, q, "photometric_sums")
+    _check_nhwc(flows, "flows", (2,))
+    _check_image(images_0, "images_0", flows)
+    _check_image(images_1, "images_1", flows)
+    if images_0.shape[3] != images_1.shape[3]:
+        raise ValueError(f"images_0 has {images_0.shape[3]} channels, images_1 {images_1.shape[3]}")
+    if valid is not None:
+        mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+    _check_gpu(flows, images_0=images_0, images_1=images_1)
+    return _PhotometricSums.apply(flows, images_0, images_1, float(flow_scale), valid, eps, q)
+
+
+def photometric_loss(images_0, images_1, flows, flow_scale=1.0, valid=None, eps=1e-3, q=0.5):
+    """0-dim: the mean of rho over the contributing pixels and the channels; 0 when no pixel contributes."""
+    sums, counts = photometric_sums(images_0, images_1, flows, flow_scale, valid, eps, q)
+    return sums.sum() / (images_0.shape[3] * counts.sum().clamp(min=1)).to(torch.float32)
+
+
+def smoothness_sums(flows, images=None, alpha=10.0, eps=1e-3, q=0.5):
+    """sums (N,) float32: per image, sum over x < W - 1 of exp(-alpha * mean_c |images[y,x+1] - images[y,x]|) * sum_k
+    rho(flows[y,x+1,k] - flows[y,x,k]) plus the same along y.  images: (N,H,W,C), C = 1..4, at the flows' resolution, a
+    constant; None: every weight is 1.  Differentiable w.r.t. flows."""
+    eps, q = _check_rho(eps, q, "smoothness_sums")
+    alpha = float(alpha)
+    if not alpha >= 0.0:
+        raise ValueError(f"smoothness_sums: alpha must be non-negative, got {alpha}")
+    _check_nhwc(flows, "flows", (2,))
+    if images is not None:
+        _check_image(images, "images", flows)
+        _check_gpu(flows, images=images)
+    _check_gpu(flows)
+    return _SmoothnessSums.apply(flows, images, alpha, eps, q)
+
+
+def smoothness_loss(flows, images=None, alpha=10.0, eps=1e-3, q=0.5):
+    """0-dim: smoothness_sums(...).sum() / (N * H * W)."""
+    sums = smoothness_sums(flows, images, alpha, eps, q)
+    return sums.sum() / float(flows.shape[0] * flows.shape[1] * flows.shape[2])

@@ -15,6 +15,11 @@ MPI-Sintel-style pairs  <dir>/<pass>/<seq>/frame_NNNN.png  with  <dir>/flow/<seq
 `--dataset synthetic`, random translating textures with known flow are generated (no files needed).
 Both use_dc settings and both losses (multiscale, robust) are implemented (Trainer docstring).
 
+`--loss unsup` trains without labels: PWCDCNetModule under torch.optim.Adam on photometric_loss(flows_final) + --smooth_weight *
+smoothness_loss(flows_final, images_0) (pwcnet_amd/unsup.py: images_1 warped by the predicted flow against images_0, and an
+edge-aware first-order smoothness of the flow).  Ground truth, where the data set has it, is used for the validation line only.
+Single process, constant learning rate; --gamma is Adam's weight_decay (the same gamma * l2_loss gradient).
+
 Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
 and-ed with <dir>/invalid/<seq>/frame_NNNN.png (non-zero = invalid, MPI-Sintel's layout) where that file exists -- and
 the step's loss and gradient and the validation numbers (masked EPE, KITTI's Fl-all) leave the invalid pixels out.
@@ -103,6 +108,54 @@ def batches(ds, idx, bs):
         yield tuple(torch.from_numpy(np.stack([it[k] for it in items])) for k in range(4))
 
 
+def validate(args, weights, ds, val_idx, dist=None):
+    """EPE / Fl-all of flows_final over the validation pairs (reference train.py:77,124-131), sharded over the ranks."""
+    from pwcnet_amd import PWCDCNet, sharding
+    net = PWCDCNet(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
+                   use_dc=args.use_dc, output_level=args.output_level)
+    net.load_weights(weights)
+    return sharding.evaluate_pairs(lambda a, b: net(a / 255.0, b / 255.0)[0],
+                                   lambda i: tuple(torch.from_numpy(x) for x in ds[val_idx[i]]),
+                                   len(val_idx), batch=args.batch_size, dist=dist, device="cuda", metrics=True)
+
+
+def train_unsup(args, ds, train_idx, val_idx):
+    """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet."""
+    from pwcnet_amd import PWCDCNetModule, ckpt
+    from pwcnet_amd.unsup import photometric_loss, smoothness_loss
+    model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
+                           use_dc=args.use_dc, output_level=args.output_level)
+    if args.resume is not None:
+        print(f"Loading learned model from checkpoint {args.resume}")
+        model.load_weights(ckpt.load_weights(args.resume))
+    opt = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.gamma)
+    global_step = 0
+    for e in range(args.num_epochs):
+        order = np.random.RandomState(1000 + e).permutation(train_idx)
+        steps = len(order) // args.batch_size
+        t0, loss_sum, n_steps = time.time(), 0.0, 0
+        for images_0, images_1, _, _ in batches(ds, order[:steps * args.batch_size], args.batch_size):
+            images_0, images_1 = (images_0 / 255.0).cuda(), (images_1 / 255.0).cuda()
+            opt.zero_grad(set_to_none=True)
+            flows_final, _ = model(images_0, images_1)
+            photo = photometric_loss(images_0, images_1, flows_final, eps=args.photo_eps, q=args.photo_q)
+            smooth = smoothness_loss(flows_final, images_0, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q)
+            loss = photo + args.smooth_weight * smooth
+            loss.backward()
+            opt.step()
+            global_step += 1
+            n_steps += 1
+            loss_sum += float(loss)
+            print(f"step {global_step}: loss/unsup {float(loss):.6f}  photometric {float(photo):.6f}  smoothness {float(smooth):.6f}")
+        res = validate(args, model.tf_state_dict(), ds, val_idx)
+        dt = time.time() - t0
+        print(f"epoch {e + 1}: loss/unsup {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
+              f"Fl-all/val {res['fl_all']:.4f}  "
+              f"global_step {global_step}  {n_steps * args.batch_size / max(dt, 1e-9):.1f} pairs/s")
+        os.makedirs(args.model_dir, exist_ok=True)
+        ckpt.save_weights(os.path.join(args.model_dir, f"model_{e + 1}.ckpt"), model.tf_state_dict())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-d", "--dataset", type=str, default="SintelClean", help="SintelClean | SintelFinal | synthetic")
@@ -118,7 +171,13 @@ def main():
     ap.add_argument("--no-dc", dest="use_dc", action="store_false")
     ap.set_defaults(use_dc=False)
     ap.add_argument("--output_level", type=int, default=4)
-    ap.add_argument("--loss", default="multiscale", choices=["multiscale", "robust"])
+    ap.add_argument("--loss", default="multiscale", choices=["multiscale", "robust", "unsup"],
+                    help="multiscale | robust: supervised (Trainer); unsup: photometric + smoothness, no labels [multiscale]")
+    ap.add_argument("--smooth_weight", type=float, default=0.1, help="--loss unsup: weight of the smoothness term [0.1]")
+    ap.add_argument("--photo_eps", type=float, default=1e-3, help="--loss unsup: Charbonnier epsilon of both terms [1e-3]")
+    ap.add_argument("--photo_q", type=float, default=0.5, help="--loss unsup: Charbonnier exponent of both terms [0.5]")
+    ap.add_argument("--edge_alpha", type=float, default=10.0,
+                    help="--loss unsup: edge weight exp(-alpha * mean |image difference|) of the smoothness term [10]")
     ap.add_argument("--lr", type=float, default=1e-4, help="Learning rate [1e-4]")
     ap.add_argument("--lr_scheduling", dest="lr_scheduling", action="store_true")
     ap.add_argument("--no-lr_scheduling", dest="lr_scheduling", action="store_false")
@@ -147,6 +206,14 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.loss == "unsup":
+        if world > 1:
+            raise SystemExit("train.py: --loss unsup runs in a single process (no multi-GPU label-free training): "
+                             f"launched with WORLD_SIZE={world}")
+        if args.output_level not in (4, 5):
+            ap.error("--loss unsup: --output_level 4 or 5 (PWCDCNetModule's gradient of the final resize)")
+        if not (args.photo_eps > 0 and 0 < args.photo_q <= 1 and args.edge_alpha >= 0):
+            ap.error("--photo_eps must be positive, --photo_q in (0, 1], --edge_alpha non-negative")
     torch.cuda.set_device(local_rank)
     dist = None
     if world > 1:
@@ -172,6 +239,8 @@ def main():
     n_val = max(1, int(len(ds) * args.val_fraction))
     perm = np.random.RandomState(0).permutation(len(ds))
     val_idx, train_idx = perm[:n_val], perm[n_val:]
+    if args.loss == "unsup":
+        return train_unsup(args, ds, train_idx, val_idx)
 
     trainer = Trainer(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                       use_dc=args.use_dc, output_level=args.output_level, weights=args.weights, gamma=args.gamma,
@@ -196,14 +265,7 @@ def main():
                                 None if bool(valid.all()) else valid.cuda())
             loss_sum += float(loss)
             n_steps += 1
-        # validation: EPE of flows_final (reference train.py:77,124-131), sharded over the ranks
-        from pwcnet_amd import PWCDCNet
-        net = PWCDCNet(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
-                       use_dc=args.use_dc, output_level=args.output_level)
-        net.load_weights(trainer.state_dict())
-        res = sharding.evaluate_pairs(lambda a, b: net(a / 255.0, b / 255.0)[0],
-                                      lambda i: tuple(torch.from_numpy(x) for x in ds[val_idx[i]]),
-                                      len(val_idx), batch=args.batch_size, dist=dist, device="cuda", metrics=True)
+        res = validate(args, trainer.state_dict(), ds, val_idx, dist)
         if rank == 0:
             dt = time.time() - t0
             print(f"epoch {e + 1}: loss/pwc {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
