@@ -47,22 +47,13 @@ constexpr int CV_TH = 4, CV_TW = 64, CV_CK = 16, CV_HW = CV_TW + 8;
 
 __device__ __forceinline__ f32x4 cv_warp_gather(const float* f1n, int f1_cs, int c, int H, int W,
                                                 int y, int x, float fx, float fy) {
-    // bilinear_warp, modules.py:107-137: un-clipped floors give the weights, the four
-    // corner indices are clipped independently.
-    const float fx0 = floorf(fx), fy0 = floorf(fy);
-    const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
-    const float hl = (float)(H - 1), wl = (float)(W - 1);
-    const int y0 = (int)fminf(fmaxf((float)y + fy0, 0.f), hl);
-    const int y1 = (int)fminf(fmaxf((float)y + fy1, 0.f), hl);
-    const int x0 = (int)fminf(fmaxf((float)x + fx0, 0.f), wl);
-    const int x1 = (int)fminf(fmaxf((float)x + fx1, 0.f), wl);
-    const float c00 = (fy1 - fy) * (fx1 - fx), c01 = (fy1 - fy) * (fx - fx0);
-    const float c10 = (fy - fy0) * (fx1 - fx), c11 = (fy - fy0) * (fx - fx0);
-    const f32x4 v00 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)y0 * W + x0) * f1_cs + c);
-    const f32x4 v01 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)y0 * W + x1) * f1_cs + c);
-    const f32x4 v10 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)y1 * W + x0) * f1_cs + c);
-    const f32x4 v11 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)y1 * W + x1) * f1_cs + c);
-    return c00 * v00 + c01 * v01 + c10 * v10 + c11 * v11;
+    const PwcCorners k = pwc_bilinear_corners(y, x, fx, fy, H, W);
+    const f32x4 w = k.w;
+    const f32x4 v00 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)k.y0 * W + k.x0) * f1_cs + c);
+    const f32x4 v01 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)k.y0 * W + k.x1) * f1_cs + c);
+    const f32x4 v10 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)k.y1 * W + k.x0) * f1_cs + c);
+    const f32x4 v11 = *reinterpret_cast<const f32x4*>(f1n + ((size_t)k.y1 * W + k.x1) * f1_cs + c);
+    return w[0] * v00 + w[1] * v01 + w[2] * v10 + w[3] * v11;
 }
 
 constexpr int CV_RS = 20;   // LDS row stride in floats (16 channels + 4 padding)
@@ -497,11 +488,7 @@ template <int R>
 static int cv_launch_dma(const CvArgs& a, hipStream_t s) {
     using G = CvPGeom<R>;
     const size_t lds = (size_t)2 * G::BUF * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_volume_dma_kernel<R, 0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&cost_volume_dma_kernel<R, 0>>((int)lds);
     const long ntiles = (long)a.tiles_x * a.tiles_y * a.N;
     // one persistent workgroup per CU; smaller LDS footprints (R < 4) may co-reside
     const int per_cu = (int)((size_t)160 * 1024 / lds);
@@ -515,11 +502,7 @@ template <int R, bool FUSED>
 static int cv_launch(const CvArgs& a, hipStream_t s) {
     using G = CvGeom<R>;
     const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_volume_kernel<R, FUSED>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&cost_volume_kernel<R, FUSED>>((int)lds);
     const unsigned nb = (unsigned)(a.tiles_x * a.tiles_y * a.N);
     hipLaunchKernelGGL((cost_volume_kernel<R, FUSED>), dim3(nb), dim3(G::T), lds, s, a);
     return pwc_launch_status();
@@ -609,19 +592,13 @@ __global__ __launch_bounds__(256, 3) void cost_volume_coarse_kernel(const CvCoar
     float c00 = 1.f, c01 = 0.f, c10 = 0.f, c11 = 0.f;
     if (pin) {
         if (WARP) {
-            // bilinear_warp, modules.py:107-137: un-clipped floors give the weights, the four corner
-            // indices are clipped independently
             const float* fl = a.flow + (((size_t)n * a.H + yy) * a.W + xx) * a.flow_cs;
             const float fx = pwc_mul_rounded(fl[0], a.flow_scale), fy = pwc_mul_rounded(fl[1], a.flow_scale);   // rounded product (see warp_kernel)
-            const float fx0 = floorf(fx), fy0 = floorf(fy);
-            const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
-            const float hl = (float)(a.H - 1), wl = (float)(a.W - 1);
-            const int iy0 = (int)fminf(fmaxf((float)yy + fy0, 0.f), hl), iy1 = (int)fminf(fmaxf((float)yy + fy1, 0.f), hl);
-            const int ix0 = (int)fminf(fmaxf((float)xx + fx0, 0.f), wl), ix1 = (int)fminf(fmaxf((float)xx + fx1, 0.f), wl);
-            c00 = (fy1 - fy) * (fx1 - fx); c01 = (fy1 - fy) * (fx - fx0);
-            c10 = (fy - fy0) * (fx1 - fx); c11 = (fy - fy0) * (fx - fx0);
-            o00 = (iy0 * a.W + ix0) * a.f1_cs; o01 = (iy0 * a.W + ix1) * a.f1_cs;
-            o10 = (iy1 * a.W + ix0) * a.f1_cs; o11 = (iy1 * a.W + ix1) * a.f1_cs;
+            const PwcCorners k = pwc_bilinear_corners(yy, xx, fx, fy, a.H, a.W);
+            const f32x4 w = k.w;
+            c00 = w[0]; c01 = w[1]; c10 = w[2]; c11 = w[3];
+            o00 = (k.y0 * a.W + k.x0) * a.f1_cs; o01 = (k.y0 * a.W + k.x1) * a.f1_cs;
+            o10 = (k.y1 * a.W + k.x0) * a.f1_cs; o11 = (k.y1 * a.W + k.x1) * a.f1_cs;
         } else {
             o00 = (yy * a.W + xx) * a.f1_cs;
         }
@@ -720,11 +697,9 @@ extern "C" int pwc_cost_volume_coarse_f32(const float* f0, int f0_cs, const floa
                                           int flow_cs, float flow_scale, float* out, int out_cs, float* f0_copy,
                                           int f0_copy_cs, int N, int H, int W, int C, int search_range, float slope,
                                           pwc_stream_t stream) {
-    if (!f0 || !f1 || !out) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return PWC_EINVAL;
-    if (search_range != 4) return PWC_EUNSUPPORTED;
-    if (f0_cs < C || f1_cs < C || out_cs < 81 || (flow && flow_cs < 2) || (f0_copy && f0_copy_cs < C)) return PWC_EINVAL;
-    if ((C & 3) || (f0_cs & 3) || (f1_cs & 3) || !pwc_aligned16(f0) || !pwc_aligned16(f1)) return PWC_EALIGN;
+    const int rc = cv_io_check(f0, f0_cs, f1, f1_cs, out, out_cs, N, H, W, C, search_range, 4,
+                               !(flow && flow_cs < 2) && !(f0_copy && f0_copy_cs < C));
+    if (rc) return rc;
     if (f0_copy && ((f0_copy_cs & 3) || !pwc_aligned16(f0_copy))) return PWC_EALIGN;
     if ((long)H * W * f0_cs >= (1L << 31) || (long)H * W * f1_cs >= (1L << 31)) return PWC_ERANGE;
     CvCoarseArgs a;
@@ -742,16 +717,6 @@ extern "C" int pwc_cost_volume_coarse_f32(const float* f0, int f0_cs, const floa
     return pwc_launch_status();
 }
 
-static int cv_check(const float* f0, int f0_cs, const float* f1, int f1_cs, float* out, int out_cs, int N,
-                    int H, int W, int C, int R) {
-    if (!f0 || !f1 || !out) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return PWC_EINVAL;
-    if (R < 1 || R > 4) return PWC_EUNSUPPORTED;
-    if (f0_cs < C || f1_cs < C || out_cs < (2 * R + 1) * (2 * R + 1)) return PWC_EINVAL;
-    if ((C & 3) || (f0_cs & 3) || (f1_cs & 3) || !pwc_aligned16(f0) || !pwc_aligned16(f1)) return PWC_EALIGN;
-    return PWC_OK;
-}
-
 extern "C" int pwc_cost_volume_uses_rolling_kernel(int H, int W, int C, int search_range, int f0_cs, int f1_cs, int out_cs) {
     // pointers are taken as 16-byte aligned (what pwc_cost_volume_f32 checks at run time)
     const float* al = reinterpret_cast<const float*>(16);
@@ -761,7 +726,7 @@ extern "C" int pwc_cost_volume_uses_rolling_kernel(int H, int W, int C, int sear
 extern "C" int pwc_cost_volume_f32(const float* f0, int f0_cs, const float* f1w, int f1w_cs, float* out,
                                    int out_cs, int N, int H, int W, int C, int search_range, float slope,
                                    pwc_stream_t stream) {
-    int rc = cv_check(f0, f0_cs, f1w, f1w_cs, out, out_cs, N, H, W, C, search_range);
+    const int rc = cv_io_check(f0, f0_cs, f1w, f1w_cs, out, out_cs, N, H, W, C, search_range, 1);
     if (rc) return rc;
     if (cv_roll_eligible(f0, f0_cs, f1w, f1w_cs, out, out_cs, nullptr, 0, H, W, C, search_range))
         return cv_roll_launch(f0, f0_cs, f1w, f1w_cs, out, out_cs, nullptr, 0, N, H, W, slope, (hipStream_t)stream);
@@ -775,8 +740,8 @@ extern "C" int pwc_cost_volume_f32(const float* f0, int f0_cs, const float* f1w,
 extern "C" int pwc_warp_cost_volume_concat_supported(int H, int W, int C, int search_range, int f0_cs, int f1_cs,
                                                      int flow_cs, int out_cs, int f0_copy_cs) {
     const float* al = reinterpret_cast<const float*>(16);
-    return cvm_eligible(al, f0_cs, al, f1_cs, flow_cs ? al : nullptr, flow_cs, al, out_cs, f0_copy_cs ? al : nullptr,
-                        f0_copy_cs, H, W, C, search_range) ? 1 : 0;
+    return cv_rsrc_eligible(al, f0_cs, al, f1_cs, flow_cs ? al : nullptr, flow_cs, al, out_cs, f0_copy_cs ? al : nullptr,
+                            f0_copy_cs, H, W, C, search_range, cvm_channels) ? 1 : 0;
 }
 
 extern "C" int pwc_warp_cost_volume_concat_f32(const float* f0, int f0_cs, const float* f1, int f1_cs,
@@ -784,16 +749,12 @@ extern "C" int pwc_warp_cost_volume_concat_f32(const float* f0, int f0_cs, const
                                                int out_cs, int out_pad_writable, float* f0_copy, int f0_copy_cs,
                                                int N, int H, int W, int C, int search_range, float slope,
                                                pwc_stream_t stream) {
-    int rc = cv_check(f0, f0_cs, f1, f1_cs, out, out_cs, N, H, W, C, search_range);
+    const int rc = cv_concat_check(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, out_pad_writable, f0_copy, f0_copy_cs, N, H, W,
+                                   C, search_range, false, cvm_channels);
     if (rc) return rc;
-    if ((flow && flow_cs < 2) || (f0_copy && f0_copy_cs < C)) return PWC_EINVAL;
-    if (out_pad_writable && out_cs < 84) return PWC_EINVAL;
-    if (out_pad_writable == 2) return PWC_EUNSUPPORTED;      // (the flow in channels 81, 82: pwc_warp_cost_volume_concat_h2_f32 only)
-    if (search_range != 4 || !(C == 32 || C == 64 || C == 96)) return PWC_EUNSUPPORTED;
-    if (!cvm_eligible(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, f0_copy, f0_copy_cs, H, W, C, search_range))
-        return ((long)H * W * (long)(out_cs > f0_cs ? out_cs : f0_cs) * 4 >= (1L << 31)) ? PWC_ERANGE : PWC_EALIGN;
-    return cvm_launch(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs, out_pad_writable ? 1 : 0, f0_copy,
-                      f0_copy_cs, N, H, W, C, slope, (hipStream_t)stream);
+    CvmArgs a = cv_rsrc_args<CvmArgs>(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs, out_pad_writable ? 1 : 0, f0_copy,
+                                      f0_copy_cs, N, H, W, C, slope);
+    return cvm_launch(a, C, (hipStream_t)stream);
 }
 
 // Round 5: the same launch with the correlation on the F16 matrix pipe (two-term fp16 operand splits, fp32 accumulation;
@@ -803,18 +764,14 @@ extern "C" int pwc_warp_cost_volume_concat_h2_f32(const float* f0, int f0_cs, co
                                                   int out_cs, int out_pad_writable, float* f0_copy, int f0_copy_cs,
                                                   int N, int H, int W, int C, int search_range, float slope,
                                                   pwc_stream_t stream) {
-    int rc = cv_check(f0, f0_cs, f1, f1_cs, out, out_cs, N, H, W, C, search_range);
+    const int rc = cv_concat_check(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, out_pad_writable, f0_copy, f0_copy_cs, N, H, W,
+                                   C, search_range, true, cvm_channels);
     if (rc) return rc;
-    if ((flow && flow_cs < 2) || (f0_copy && f0_copy_cs < C)) return PWC_EINVAL;
-    if (out_pad_writable && out_cs < 84) return PWC_EINVAL;
-    if (search_range != 4 || !(C == 32 || C == 64 || C == 96)) return PWC_EUNSUPPORTED;
-    if (!cvm_eligible(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, f0_copy, f0_copy_cs, H, W, C, search_range))
-        return ((long)H * W * (long)(out_cs > f0_cs ? out_cs : f0_cs) * 4 >= (1L << 31)) ? PWC_ERANGE : PWC_EALIGN;
     // out_pad_writable == 2 (round 6): channels 81, 82 of every record receive the pixel's flow (cost_volume_h2.hip, FLOWPAD)
     if (out_pad_writable == 2 && !flow) return PWC_EINVAL;
-    return cvh_launch(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs,
-                      out_pad_writable == 2 ? 2 : (out_pad_writable ? 1 : 0), f0_copy, f0_copy_cs, N, H, W, C, slope,
-                      (hipStream_t)stream);
+    CvmArgs a = cv_rsrc_args<CvmArgs>(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs,
+                                      out_pad_writable == 2 ? 2 : (out_pad_writable ? 1 : 0), f0_copy, f0_copy_cs, N, H, W, C, slope);
+    return cvh_launch(a, C, (hipStream_t)stream);
 }
 
 // Round 5: the same operation for the small pyramid levels (C = 96 / 128 / 192): one 4 x 4 block per workgroup, the whole
@@ -822,8 +779,8 @@ extern "C" int pwc_warp_cost_volume_concat_h2_f32(const float* f0, int f0_cs, co
 extern "C" int pwc_warp_cost_volume_concat_blk_supported(int H, int W, int C, int search_range, int f0_cs, int f1_cs,
                                                          int flow_cs, int out_cs, int f0_copy_cs) {
     const float* al = reinterpret_cast<const float*>(16);
-    return cvb_eligible(al, f0_cs, al, f1_cs, flow_cs ? al : nullptr, flow_cs, al, out_cs, f0_copy_cs ? al : nullptr,
-                        f0_copy_cs, H, W, C, search_range) ? 1 : 0;
+    return cv_rsrc_eligible(al, f0_cs, al, f1_cs, flow_cs ? al : nullptr, flow_cs, al, out_cs, f0_copy_cs ? al : nullptr,
+                            f0_copy_cs, H, W, C, search_range, cvb_channels) ? 1 : 0;
 }
 
 #ifdef PWC_HARNESS
@@ -835,28 +792,25 @@ extern "C" int pwc_warp_cost_volume_concat_blk_f32(const float* f0, int f0_cs, c
                                                    int out_cs, int out_pad_writable, float* f0_copy, int f0_copy_cs,
                                                    int N, int H, int W, int C, int search_range, float slope,
                                                    pwc_stream_t stream) {
-    int rc = cv_check(f0, f0_cs, f1, f1_cs, out, out_cs, N, H, W, C, search_range);
+    const int rc = cv_concat_check(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, out_pad_writable, f0_copy, f0_copy_cs, N, H, W,
+                                   C, search_range, false, cvb_channels);
     if (rc) return rc;
-    if ((flow && flow_cs < 2) || (f0_copy && f0_copy_cs < C)) return PWC_EINVAL;
-    if (out_pad_writable && out_cs < 84) return PWC_EINVAL;
-    if (out_pad_writable == 2) return PWC_EUNSUPPORTED;      // (the flow in channels 81, 82: pwc_warp_cost_volume_concat_h2_f32 only)
-    if (search_range != 4 || !(C == 64 || C == 96 || C == 128 || C == 192)) return PWC_EUNSUPPORTED;
-    if (!cvb_eligible(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, f0_copy, f0_copy_cs, H, W, C, search_range))
-        return ((long)H * W * (long)(out_cs > f0_cs ? out_cs : f0_cs) * 4 >= (1L << 31)) ? PWC_ERANGE : PWC_EALIGN;
-    return cvb_launch(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs, out_pad_writable ? 1 : 0, f0_copy,
-                      f0_copy_cs, N, H, W, C, slope, (hipStream_t)stream);
+    CvbArgs a = cv_rsrc_args<CvbArgs>(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs, out_pad_writable ? 1 : 0, f0_copy,
+                                      f0_copy_cs, N, H, W, C, slope);
+    return cvb_launch(a, C, (hipStream_t)stream);
 }
 
 extern "C" int pwc_warp_cost_volume_f32(const float* f0, int f0_cs, const float* f1, int f1_cs,
                                         const float* flow, int flow_cs, float flow_scale, float* out,
                                         int out_cs, int N, int H, int W, int C, int search_range, float slope,
                                         pwc_stream_t stream) {
-    int rc = cv_check(f0, f0_cs, f1, f1_cs, out, out_cs, N, H, W, C, search_range);
+    const int rc = cv_io_check(f0, f0_cs, f1, f1_cs, out, out_cs, N, H, W, C, search_range, 1);
     if (rc) return rc;
     if (!flow || flow_cs < 2) return PWC_EINVAL;
-    if (cvm_eligible(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, nullptr, 0, H, W, C, search_range))
-        return cvm_launch(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs, 0, nullptr, 0, N, H, W, C, slope,
-                          (hipStream_t)stream);
+    if (cv_rsrc_eligible(f0, f0_cs, f1, f1_cs, flow, flow_cs, out, out_cs, nullptr, 0, H, W, C, search_range, cvm_channels)) {
+        CvmArgs m = cv_rsrc_args<CvmArgs>(f0, f0_cs, f1, f1_cs, flow, flow_cs, flow_scale, out, out_cs, 0, nullptr, 0, N, H, W, C, slope);
+        return cvm_launch(m, C, (hipStream_t)stream);
+    }
     CvArgs a;
     a.f0 = f0; a.f1 = f1; a.flow = flow; a.out = out;
     a.f0_cs = f0_cs; a.f1_cs = f1_cs; a.flow_cs = flow_cs; a.out_cs = out_cs;

@@ -80,6 +80,8 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
     const int n = blk / a.nby;
     const int y0 = 4 * by, x0 = 4 * bx;
 
+    // (the five resources stay spelled out in each of the three kernels: built by a shared forceinline helper -- a struct or five
+    // reference results -- every instantiation came out with another register allocation)
     const size_t npx = (size_t)a.H * a.W;
     const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.f0 + (size_t)n * npx * a.f0_cs), 0, (int)(npx * a.f0_cs * 4), 0x00020000);
@@ -117,7 +119,8 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
             const unsigned vo = ok ? (unsigned)((gy * a.W + gx) * a.flow_cs) * 4u : CVM_OOB;
             const float f0v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf, (int)vo, 0, 0));
             const float f1v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf, (int)vo, 4, 0));
-            // bilinear_warp, modules.py:107-137: the product flow * scale is rounded first (model.py:109 is an op of its own),
+            // pwc_bilinear_corners (pwc_common.h), spelled out: through the helper the 16 warping instantiations of this kernel
+            // came out with another register allocation.  bilinear_warp, modules.py:107-137: the product is rounded first,
             // weights from the un-clipped floors, the four corner indices clipped independently
             const float fx = pwc_mul_rounded(f0v, a.flow_scale), fy = pwc_mul_rounded(f1v, a.flow_scale);
             const float fx0 = floorf(fx), fy0 = floorf(fy);
@@ -134,7 +137,7 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
         *reinterpret_cast<cvm_u32x4*>(tab + t * 8) = off;
         *reinterpret_cast<f32x4*>(tab + t * 8 + 4) = w;
     }
-    cvm_barrier();
+    pwc_lds_barrier();
 
     // ---- the gather: item e = (window pixel e / NQ, channel quad e % NQ) -- the quads of a pixel in consecutive lanes, so one
     // instruction asks for whole lines of a corner pixel -- in rounds of R items per lane: requests, then blend + split -> image
@@ -160,11 +163,7 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
             f32x4 v = gv[i][0];
             if (WARP) {
                 const f32x4 w = *reinterpret_cast<const f32x4*>(tab + qp * 8 + 4);
-                // modules.py:132-135: c00*x00 + c01*x01 + c10*x10 + c11*x11, summed left to right
-                v = w[0] * gv[i][0];
-                v = __builtin_elementwise_fma(f32x4{w[1], w[1], w[1], w[1]}, gv[i][1], v);
-                v = __builtin_elementwise_fma(f32x4{w[2], w[2], w[2], w[2]}, gv[i][2], v);
-                v = __builtin_elementwise_fma(f32x4{w[3], w[3], w[3], w[3]}, gv[i][3], v);
+                v = pwc_blend_corners(w, gv[i][0], gv[i][1], gv[i][2], gv[i][3]);
             }
             pwc_f16x4 h, m;
             pwc_split4(v, h, m);
@@ -186,15 +185,8 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cvm_u32x4, A[g]), rc, (int)vo, g * 64, 0);
     }
     pwc_f16x8 AH[NP], AM[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        pwc_f16x4 h0, m0, h1, m1;
-        pwc_split4(A[2 * j], h0, m0);
-        pwc_split4(A[2 * j + 1], h1, m1);
-        AH[j] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-        AM[j] = __builtin_shufflevector(m0, m1, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-    cvm_barrier();
+    cv_split_rows<NP>(A, AH, AM);
+    pwc_lds_barrier();
 
     // ---- tiles: the window blocks (row qr4, column qbc) over the waves.  D fragment: lane holds P pixels (row kq, column r = 0..3)
     // x Q pixel (row mrow, column mcol); entry (v, h) = (4 (qbr0 + qr4 - 1) + mrow - kq, 4 (qbc - 1) + mcol - r) goes to
@@ -202,6 +194,7 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
     for (int qb = wave; qb < 3 * QR; qb += 4) {
         const int qr4 = qb / 3, qbc = qb - 3 * qr4;
         const char* base = img + (4 * qr4 + mrow) * RSB + (4 * qbc + mcol) * 64 + kq * 16;
+        // (the accumulate of cost_volume_h2.hip, one tile: see there why it is not shared)
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         f32x4 hh = zero, xx = zero;
 #pragma unroll
@@ -220,7 +213,7 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
             stg[ok ? ((kq * 4 + r) * ROWS + 4 * qr4 + mrow) * 9 + hx + 4 : 16 * ROWS * 9 + lane] = s[r];
         }
     }
-    cvm_barrier();
+    pwc_lds_barrier();
 
     // ---- copy-out: entry e = (pixel p, window row mr, h): channel (v + 4) * 9 + h + 4 with v = 4 (qbr0 - 1) + mr - (p >> 2), where
     // |v| <= 4 -- for a pixel a contiguous run of channels; mean = sum * (1/C) (reduce_mean, modules.py:181), leaky-relu
@@ -247,27 +240,12 @@ __global__ __launch_bounds__(256) void cost_volume_blk_kernel(const CvbArgs a) {
     }
 }
 
-static bool cvb_eligible(const float* f0, int f0_cs, const float* f1, int f1_cs, const float* flow, int flow_cs,
-                         const float* out, int out_cs, const float* f0_copy, int f0_copy_cs, int H, int W, int C, int R) {
-    if (R != 4 || !(C == 64 || C == 96 || C == 128 || C == 192)) return false;
-    if ((f0_cs & 3) || (f1_cs & 3) || (out_cs & 3) || !pwc_aligned16(f0) || !pwc_aligned16(f1) || !pwc_aligned16(out)) return false;
-    if (f0_copy && ((f0_copy_cs & 3) || !pwc_aligned16(f0_copy))) return false;
-    if (flow && (reinterpret_cast<uintptr_t>(flow) & 3u)) return false;
-    const long px = (long)H * W;
-    if (px * f0_cs * 4 >= (1L << 31) || px * f1_cs * 4 >= (1L << 31) || px * out_cs * 4 >= (1L << 31)) return false;
-    if (f0_copy && px * f0_copy_cs * 4 >= (1L << 31)) return false;
-    if (flow && px * flow_cs * 4 >= (1L << 31)) return false;
-    return true;
-}
+static bool cvb_channels(int C) { return C == 64 || C == 96 || C == 128 || C == 192; }
 
 template <int CG, bool WARP, bool PAD, int QR>
 static int cvb_launch_q(const CvbArgs& a, hipStream_t s) {
     using G = CvbGeom<CG, QR>;
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_volume_blk_kernel<CG, WARP, PAD, QR>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    }
+    pwc_allow_dynamic_lds<&cost_volume_blk_kernel<CG, WARP, PAD, QR>>(G::LDS);
     const long items = (long)a.N * a.nbx * a.nby * (QR == 1 ? 3 : 1);
     if (items >= (1L << 31)) return PWC_ERANGE;
     hipLaunchKernelGGL((cost_volume_blk_kernel<CG, WARP, PAD, QR>), dim3((unsigned)items), dim3(256), G::LDS, s, a);
@@ -288,25 +266,9 @@ static int cvb_launch_t(const CvbArgs& a, hipStream_t s) {
     return qr == 3 ? cvb_launch_q<CG, WARP, PAD, 3>(a, s) : cvb_launch_q<CG, WARP, PAD, 1>(a, s);
 }
 
-static int cvb_launch(const float* f0, int f0_cs, const float* f1, int f1_cs, const float* flow, int flow_cs,
-                      float flow_scale, float* out, int out_cs, int pad_ok, float* f0_copy, int f0_copy_cs, int N, int H,
-                      int W, int C, float slope, hipStream_t s) {
-    CvbArgs a;
-    a.f0 = f0; a.f1 = f1; a.flow = flow; a.out = out; a.f0_copy = f0_copy;
-    a.f0_cs = f0_cs; a.f1_cs = f1_cs; a.flow_cs = flow_cs; a.out_cs = out_cs; a.f0_copy_cs = f0_copy_cs;
-    a.N = N; a.H = H; a.W = W; a.flow_scale = flow_scale; a.slope = slope;
-    a.inv_c = 1.0f / (float)C;               // reduce_mean: x * (1/C), within 1 ulp of x / C
-    a.nbx = (W + 3) / 4; a.nby = (H + 3) / 4; a.pad_ok = pad_ok;
-#define CVB_CASE(CGV)                                                                          \
-    case CGV * 16:                                                                             \
-        return flow ? (pad_ok ? cvb_launch_t<CGV, true, true>(a, s) : cvb_launch_t<CGV, true, false>(a, s))         \
-                    : (pad_ok ? cvb_launch_t<CGV, false, true>(a, s) : cvb_launch_t<CGV, false, false>(a, s));
-    switch (C) {
-        CVB_CASE(4)
-        CVB_CASE(6)
-        CVB_CASE(8)
-        CVB_CASE(12)
-        default: return PWC_EUNSUPPORTED;
-    }
-#undef CVB_CASE
+static int cvb_launch(CvbArgs& a, int C, hipStream_t s) {
+    a.nbx = (a.W + 3) / 4; a.nby = (a.H + 3) / 4;
+    return cv_dispatch_cg<4, 6, 8, 12>(C, a.flow != nullptr, a.pad_ok != 0, [&](auto cg, auto warp, auto pad) {
+        return cvb_launch_t<decltype(cg)::value, decltype(warp)::value, decltype(pad)::value>(a, s);
+    });
 }

@@ -87,6 +87,8 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
     if (pb0 >= pb1) return;                                             // uniform
     const int qa = max(pb0 - 1, 0), qb = min(pb1, a.nbrows - 1);        // Q rows that hold image pixels
 
+    // (the five resources stay spelled out in each of the three kernels: built by a shared forceinline helper -- a struct or five
+    // reference results -- every instantiation came out with another register allocation)
     const size_t npx = (size_t)a.H * a.W;
     const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.f0 + (size_t)n * npx * a.f0_cs), 0, (int)(npx * a.f0_cs * 4), 0x00020000);
@@ -213,13 +215,9 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
             f32x4 v;
             if (WARP) {
                 const f32x4 w = *reinterpret_cast<const f32x4*>(tabf + ts * G::TAB + tab_d + 4);
-                // modules.py:132-135: c00*x00 + c01*x01 + c10*x10 + c11*x11, summed left to right.  (The 1/C of the mean is NOT
-                // folded into the weights here as the fp32 kernel does: a feature of 1e-3 over C = 64 would be split in fp16's
-                // subnormal range and lose bits; it multiplies the finished sum in the copy-out.)
-                v = w[0] * gv[i][0];
-                v = __builtin_elementwise_fma(f32x4{w[1], w[1], w[1], w[1]}, gv[i][1], v);
-                v = __builtin_elementwise_fma(f32x4{w[2], w[2], w[2], w[2]}, gv[i][2], v);
-                v = __builtin_elementwise_fma(f32x4{w[3], w[3], w[3], w[3]}, gv[i][3], v);
+                // (The 1/C of the mean is NOT folded into the weights here as the fp32 kernel does: a feature of 1e-3 over C = 64
+                // would be split in fp16's subnormal range and lose bits; it multiplies the finished sum in the copy-out.)
+                v = pwc_blend_corners(w, gv[i][0], gv[i][1], gv[i][2], gv[i][3]);
             } else {
                 v = gv[i][0];
             }
@@ -244,18 +242,12 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
         if (t < G::NPIX) {
             const int gy = 4 * qq + t_r, gx = x0 - 4 + t_xi;
             const bool ok = qq >= qa && qq <= qb && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-            // bilinear_warp, modules.py:107-137: the product flow * scale is rounded first (model.py:109 is an op of
-            // its own), weights from the un-clipped floors, the four corner indices clipped independently
             const float fx = pwc_mul_rounded(f0v, a.flow_scale), fy = pwc_mul_rounded(f1v, a.flow_scale);
-            const float fx0 = floorf(fx), fy0 = floorf(fy);
-            const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
-            const float hl = (float)(a.H - 1), wl = (float)(a.W - 1);
-            const int iy0 = (int)fminf(fmaxf((float)gy + fy0, 0.f), hl), iy1 = (int)fminf(fmaxf((float)gy + fy1, 0.f), hl);
-            const int ix0 = (int)fminf(fmaxf((float)gx + fx0, 0.f), wl), ix1 = (int)fminf(fmaxf((float)gx + fx1, 0.f), wl);
-            const f32x4 w = {(fy1 - fy) * (fx1 - fx), (fy1 - fy) * (fx - fx0), (fy - fy0) * (fx1 - fx), (fy - fy0) * (fx - fx0)};
+            const PwcCorners k = pwc_bilinear_corners(gy, gx, fx, fy, a.H, a.W);
+            const f32x4 w = k.w;
             const unsigned cs4 = (unsigned)a.f1_cs * 4u;
-            cvm_u32x4 off = {(unsigned)(iy0 * a.W + ix0) * cs4, (unsigned)(iy0 * a.W + ix1) * cs4,
-                             (unsigned)(iy1 * a.W + ix0) * cs4, (unsigned)(iy1 * a.W + ix1) * cs4};
+            cvm_u32x4 off = {(unsigned)(k.y0 * a.W + k.x0) * cs4, (unsigned)(k.y0 * a.W + k.x1) * cs4,
+                             (unsigned)(k.y1 * a.W + k.x0) * cs4, (unsigned)(k.y1 * a.W + k.x1) * cs4};
             if (!ok) off = cvm_u32x4{CVM_OOB, CVM_OOB, CVM_OOB, CVM_OOB};
             float* e = tabf + ts * G::TAB + t * 8;
             *reinterpret_cast<cvm_u32x4*>(e) = off;
@@ -280,14 +272,7 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
 #pragma unroll
         for (int g = 0; g < CG; ++g)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cvm_u32x4, A[g]), rc, (int)(ok ? vo : CVM_OOB), g * 64, CVM_COPY_AUX);
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            pwc_f16x4 h0, m0, h1, m1;
-            pwc_split4(A[2 * j], h0, m0);
-            pwc_split4(A[2 * j + 1], h1, m1);
-            AH[j] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-            AM[j] = __builtin_shufflevector(m0, m1, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
+        cv_split_rows<NP>(A, AH, AM);
     };
 
     // ---- the three tiles of one vertical block offset: per 32 channels cross = AH x BM' + AM' x BH, hh = AH x BH
@@ -315,6 +300,8 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
             for (int bx = 0; bx < 3; ++bx) acc[byi][bx] = zero;
             return;
         }
+        // (spelled out here and in cost_volume_blk.hip: as one forceinline helper over NT tiles, or as a three-instruction step per
+        // tile, this kernel's instantiations were scheduled differently)
         f32x4 hh[3], xx[3];
         cvm_for<NP>([&](auto j_c) {
             constexpr int j = decltype(j_c)::value;
@@ -354,17 +341,8 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
         if constexpr (!PAD) x80 = stg[(lane & 15) * G::SROW + 80];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            // mean = sum * (1/C) (reduce_mean, modules.py:181), then leaky-relu max(x, slope * x): ONE v_max_f32 per value (fmaxf
-            // costs a second one that quiets a possible signalling NaN)
-            const f32x4 mv = v[i] * a.inv_c;
-            const f32x4 sv = mv * a.slope;
-            f32x4 y;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float yk;
-                asm("v_max_f32 %0, %1, %2" : "=v"(yk) : "v"(mv[k]), "v"(sv[k]));
-                y[k] = yk;
-            }
+            // mean = sum * (1/C) (reduce_mean, modules.py:181), then leaky-relu
+            f32x4 y = cv_lrelu_quad(v[i] * a.inv_c, a.slope);
             if constexpr (FLOWPAD) {                                    // channels 81, 82 carry the flow as read: no mean, no activation
                 const bool f = (q20 >> i) & 1u;
                 y[1] = f ? v[i][1] : y[1];
@@ -416,7 +394,7 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
                 if constexpr (NP == 1) { reads(I1{}, s_0); reads(I2{}, s_p); }
             }
             stamp();
-            cvm_barrier();                                              // A: the image of Q row p-1 has been read
+            pwc_lds_barrier();                                          // A: the image of Q row p-1 has been read
             stamp();
             if (real) {
                 if constexpr (NP > 1) reads(I1{}, s_0);
@@ -436,12 +414,12 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
             // Always executed (rows outside the segment store nothing: out-of-range offsets)
             copy_out(p);
             stamp();
-            cvm_barrier();                                              // B: Q row p+2 and the table of row p+4 are complete
+            pwc_lds_barrier();                                          // B: Q row p+2 and the table of row p+4 are complete
             stamp();
             stamp();
             const int s_n = s_m; s_m = s_0; s_0 = s_p; s_p = s_n;      // (the freed image is Q row p+2's)
         };
-        cvm_barrier();                                                  // (the producers' first tables)
+        pwc_lds_barrier();                                              // (the producers' first tables)
         load_A(A2[1], pb0 - 2);                                         // (no such row: zeros)
         for (int p = pb0 - 3; p < pb1; p += 2) {
             cstep(I0{}, p);
@@ -457,15 +435,15 @@ __global__ __launch_bounds__(512, 1) void cost_volume_h2_kernel(const CvmArgs a)
             table_write(pb0 - 1, slot(pb0 - 1), fl0, fl1);
             table_write(pb0, slot(pb0), g0, g1);
         }
-        cvm_barrier();
+        pwc_lds_barrier();
         g_issue(pb0 - 1, slot(pb0 - 1));
         for (int p = pb0 - 3; p < pb1; ++p) {
             if (WARP) flow_issue(p + 4, fl0, fl1);
-            cvm_barrier();                                              // A
+            pwc_lds_barrier();                                          // A
             g_commit(slot(p + 2), slot(p - 1));                         // Q row p+2 (requested a step ago) -> the freed image
             g_issue(p + 3, slot(p + 3));
             if (WARP) table_write(p + 4, slot(p + 4), fl0, fl1);
-            cvm_barrier();                                              // B
+            pwc_lds_barrier();                                          // B
         }
     }
 }
@@ -474,11 +452,7 @@ template <int CG, bool WARP, bool PAD, bool FLOWPAD = false>
 static int cvh_launch_t(CvmArgs& a, hipStream_t s) {
     using GH = CvhGeom<CG>;
     const size_t lds = (size_t)GH::LDS_F * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_volume_h2_kernel<CG, WARP, PAD, 0, FLOWPAD>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&cost_volume_h2_kernel<CG, WARP, PAD, 0, FLOWPAD>>((int)lds);
     cvm_plan(a.N, a.H, a.W, 1, &a.nstrips, &a.nseg, &a.seg_brows);
     const long items = (long)a.N * a.nstrips * a.nseg;
     if (items >= (1L << 31)) return PWC_ERANGE;
@@ -486,26 +460,15 @@ static int cvh_launch_t(CvmArgs& a, hipStream_t s) {
     return pwc_launch_status();
 }
 
-static int cvh_launch(const float* f0, int f0_cs, const float* f1, int f1_cs, const float* flow, int flow_cs,
-                      float flow_scale, float* out, int out_cs, int pad_ok, float* f0_copy, int f0_copy_cs, int N, int H,
-                      int W, int C, float slope, hipStream_t s) {
-    CvmArgs a;
-    a.f0 = f0; a.f1 = f1; a.flow = flow; a.out = out; a.f0_copy = f0_copy;
-    a.f0_cs = f0_cs; a.f1_cs = f1_cs; a.flow_cs = flow_cs; a.out_cs = out_cs; a.f0_copy_cs = f0_copy_cs;
-    a.N = N; a.H = H; a.W = W; a.flow_scale = flow_scale; a.slope = slope;
-    a.inv_c = 1.0f / (float)C;               // reduce_mean: x * (1/C), within 1 ulp of x / C
-    a.nbrows = (H + 3) / 4;
-    a.pad_ok = pad_ok; a.dbg = nullptr;
-#define CVH_CASE(CGV)                                                                          \
-    case CGV * 16:                                                                             \
-        if (flow && pad_ok == 2) return cvh_launch_t<CGV, true, true, true>(a, s);                                  \
-        return flow ? (pad_ok ? cvh_launch_t<CGV, true, true>(a, s) : cvh_launch_t<CGV, true, false>(a, s))         \
-                    : (pad_ok ? cvh_launch_t<CGV, false, true>(a, s) : cvh_launch_t<CGV, false, false>(a, s));
-    switch (C) {
-        CVH_CASE(2)
-        CVH_CASE(4)
-        CVH_CASE(6)
-        default: return PWC_EUNSUPPORTED;
-    }
-#undef CVH_CASE
+// a.pad_ok == 2 (with a flow): the FLOWPAD form
+static int cvh_launch(CvmArgs& a, int C, hipStream_t s) {
+    a.nbrows = (a.H + 3) / 4;
+    a.dbg = nullptr;
+    return cv_dispatch_cg<2, 4, 6>(C, a.flow != nullptr, a.pad_ok != 0, [&](auto cg, auto warp, auto pad) {
+        constexpr int CG = decltype(cg)::value;
+        if constexpr (decltype(warp)::value && decltype(pad)::value) {
+            if (a.pad_ok == 2) return cvh_launch_t<CG, true, true, true>(a, s);
+        }
+        return cvh_launch_t<CG, decltype(warp)::value, decltype(pad)::value>(a, s);
+    });
 }

@@ -37,8 +37,7 @@
 //
 // Algorithmic bytes N*H*W*(2C+2+81)*4; HBM-bound (AI 8.9 flop/B at C = 32).
 #pragma once
-#include "pwc_common.h"
-#include <type_traits>
+#include "cost_volume_common.h"
 
 struct CvmArgs {
     const float* f0;
@@ -76,7 +75,6 @@ struct CvmGeom {
     static_assert(LDS_F * 4 <= 160 * 1024, "does not fit the LDS");
 };
 
-#define CVM_OOB 0x80000000u
 #ifndef CVM_ITEM_LINES
 #define CVM_ITEM_LINES 1
 #endif
@@ -101,29 +99,12 @@ struct CvmGeom {
 #else
 #define CVM_SCHED_BARRIER()
 #endif
-typedef unsigned int cvm_u32x4 __attribute__((ext_vector_type(4)));
 
-// Workgroup barrier that orders LDS traffic only (__syncthreads() would also drain vmcnt: the gathers in flight
-// and the copy-out stores)
-__device__ __forceinline__ void cvm_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 // LDS hand-over between the lanes of ONE wave (a wave's LDS instructions execute in order: compiler fence only)
 __device__ __forceinline__ void cvm_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-
-// f(std::integral_constant<int, i>{}) for i = 0 .. N-1
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void cvm_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        cvm_for<N, I + 1>(f);
-    }
 }
 
 // ABL (scripts/exp_cv3.hip only; 0 in the library): 1 = no MFMAs, 2 = no gather loads, 4 = no stores
@@ -156,6 +137,8 @@ __global__ __launch_bounds__(256, CvmGeom<CG>::WGPC) void cost_volume_mfma_kerne
     if (CVM_STAGGER > 0 && blockIdx.x >= 256 && ((blockIdx.x >> 8) & 1)) __builtin_amdgcn_s_sleep(CVM_STAGGER);
     const int qa = max(pb0 - 1, 0), qb = min(pb1, a.nbrows - 1);        // Q rows that hold image pixels
 
+    // (the five resources stay spelled out in each of the three kernels: built by a shared forceinline helper -- a struct or five
+    // reference results -- every instantiation came out with another register allocation)
     const size_t npx = (size_t)a.H * a.W;
     const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.f0 + (size_t)n * npx * a.f0_cs), 0, (int)(npx * a.f0_cs * 4), 0x00020000);
@@ -294,12 +277,8 @@ __global__ __launch_bounds__(256, CvmGeom<CG>::WGPC) void cost_volume_mfma_kerne
         f32x4 v;
         if (WARP) {
             const f32x4 w = *reinterpret_cast<const f32x4*>(tabf + (qq & 1) * G::TAB + tab_d + 4);
-            // modules.py:132-135: c00*x00 + c01*x01 + c10*x10 + c11*x11, summed left to right (the weights carry the
-            // 1/C of the mean: exact for C = 32, 64)
-            v = w[0] * gv[j][0];
-            v = __builtin_elementwise_fma(f32x4{w[1], w[1], w[1], w[1]}, gv[j][1], v);
-            v = __builtin_elementwise_fma(f32x4{w[2], w[2], w[2], w[2]}, gv[j][2], v);
-            v = __builtin_elementwise_fma(f32x4{w[3], w[3], w[3], w[3]}, gv[j][3], v);
+            // (the weights carry the 1/C of the mean: exact for C = 32, 64)
+            v = pwc_blend_corners(w, gv[j][0], gv[j][1], gv[j][2], gv[j][3]);
         } else {
             v = gv[j][0] * a.inv_c;
         }
@@ -321,19 +300,13 @@ __global__ __launch_bounds__(256, CvmGeom<CG>::WGPC) void cost_volume_mfma_kerne
         if (t < G::NPIX) {
             const int gy = 4 * qq + t_r, gx = x0 - 4 + t_xi;
             const bool ok = qq >= qa && qq <= qb && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-            // bilinear_warp, modules.py:107-137: the product flow * scale is rounded first (model.py:109 is an op of
-            // its own), weights from the un-clipped floors, the four corner indices clipped independently
             const float fx = pwc_mul_rounded(f0v, a.flow_scale), fy = pwc_mul_rounded(f1v, a.flow_scale);
-            const float fx0 = floorf(fx), fy0 = floorf(fy);
-            const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
-            const float hl = (float)(a.H - 1), wl = (float)(a.W - 1);
-            const int iy0 = (int)fminf(fmaxf((float)gy + fy0, 0.f), hl), iy1 = (int)fminf(fmaxf((float)gy + fy1, 0.f), hl);
-            const int ix0 = (int)fminf(fmaxf((float)gx + fx0, 0.f), wl), ix1 = (int)fminf(fmaxf((float)gx + fx1, 0.f), wl);
-            f32x4 w = {(fy1 - fy) * (fx1 - fx), (fy1 - fy) * (fx - fx0), (fy - fy0) * (fx1 - fx), (fy - fy0) * (fx - fx0)};
+            const PwcCorners k = pwc_bilinear_corners(gy, gx, fx, fy, a.H, a.W);
+            f32x4 w = k.w;
             w = w * a.inv_c;
             const unsigned cs4 = (unsigned)a.f1_cs * 4u;
-            cvm_u32x4 off = {(unsigned)(iy0 * a.W + ix0) * cs4, (unsigned)(iy0 * a.W + ix1) * cs4,
-                             (unsigned)(iy1 * a.W + ix0) * cs4, (unsigned)(iy1 * a.W + ix1) * cs4};
+            cvm_u32x4 off = {(unsigned)(k.y0 * a.W + k.x0) * cs4, (unsigned)(k.y0 * a.W + k.x1) * cs4,
+                             (unsigned)(k.y1 * a.W + k.x0) * cs4, (unsigned)(k.y1 * a.W + k.x1) * cs4};
             if (!ok) off = cvm_u32x4{CVM_OOB, CVM_OOB, CVM_OOB, CVM_OOB};
             float* e = tabf + (qq & 1) * G::TAB + t * 8;
             *reinterpret_cast<cvm_u32x4*>(e) = off;
@@ -376,16 +349,7 @@ __global__ __launch_bounds__(256, CvmGeom<CG>::WGPC) void cost_volume_mfma_kerne
         const unsigned base = (unsigned)((4 * pb * a.W + x0 + 4 * wave) * a.out_cs) * 4u;
         if constexpr (i < 6) {
             f32x4 v = *reinterpret_cast<const f32x4*>(stg + (i * 64 + lane < 16 * 21 ? (i * 64 + lane) * 4 : 0));
-            // leaky-relu max(x, slope * x): ONE v_max_f32 per value (fmaxf costs a second one that quiets a possible
-            // signalling NaN first; fmed3 with +inf is folded back into fmaxf).  The multiply in front is
-            // compiler-visible and reads the same registers.
-            const f32x4 sv = v * a.slope;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float y;
-                asm("v_max_f32 %0, %1, %2" : "=v"(y) : "v"(v[k]), "v"(sv[k]));
-                v[k] = y;
-            }
+            v = cv_lrelu_quad(v, a.slope);
             const bool ok = i * 64 + lane < 84 * ylim && !(ABL & 4);    // 84 items per block row
             const unsigned vo = ok ? base + co_rel[i] : CVM_OOB;        // out-of-range + base stays out of range
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cvm_u32x4, v), ro, (int)vo, 0, CVM_STORE_AUX);
@@ -508,7 +472,7 @@ __global__ __launch_bounds__(256, CvmGeom<CG>::WGPC) void cost_volume_mfma_kerne
         for (int j = 0; j < 3; ++j) gc_item(NB - 1, j, q + 1);
         if (WARP) table_write(q + 2, fl0, fl1);
         stamp();
-        cvm_barrier();
+        pwc_lds_barrier();
     };
     if (WARP) {
         // tables of the first two Q rows
@@ -518,7 +482,7 @@ __global__ __launch_bounds__(256, CvmGeom<CG>::WGPC) void cost_volume_mfma_kerne
         table_write(qa, fl0, fl1);
         table_write(qa + 1, g0, g1);
     }
-    cvm_barrier();
+    pwc_lds_barrier();
     {
         int q = qa - 1;
         for (;;) {
@@ -550,29 +514,13 @@ static void cvm_plan(int N, int H, int W, int wgpc, int* nstrips, int* nseg, int
     *nstrips = ns; *seg_brows = best_k; *nseg = (nb + best_k - 1) / best_k;
 }
 
-static bool cvm_eligible(const float* f0, int f0_cs, const float* f1, int f1_cs, const float* flow, int flow_cs,
-                         const float* out, int out_cs, const float* f0_copy, int f0_copy_cs, int H, int W, int C, int R) {
-    if (R != 4 || !(C == 32 || C == 64 || C == 96)) return false;
-    if ((f0_cs & 3) || (f1_cs & 3) || (out_cs & 3) || !pwc_aligned16(f0) || !pwc_aligned16(f1) || !pwc_aligned16(out)) return false;
-    if (f0_copy && ((f0_copy_cs & 3) || !pwc_aligned16(f0_copy))) return false;
-    if (flow && (reinterpret_cast<uintptr_t>(flow) & 3u)) return false;
-    // buffer resources are per image: byte extents must stay below 2^31 (the out-of-range marker)
-    const long px = (long)H * W;
-    if (px * f0_cs * 4 >= (1L << 31) || px * f1_cs * 4 >= (1L << 31) || px * out_cs * 4 >= (1L << 31)) return false;
-    if (f0_copy && px * f0_copy_cs * 4 >= (1L << 31)) return false;
-    if (flow && px * flow_cs * 4 >= (1L << 31)) return false;
-    return true;
-}
+static bool cvm_channels(int C) { return C == 32 || C == 64 || C == 96; }
 
 template <int CG, bool WARP, bool PAD>
 static int cvm_launch_t(CvmArgs& a, hipStream_t s) {
     using G = CvmGeom<CG>;
     const size_t lds = (size_t)G::LDS_F * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_volume_mfma_kernel<CG, WARP, PAD, 0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&cost_volume_mfma_kernel<CG, WARP, PAD, 0>>((int)lds);
     cvm_plan(a.N, a.H, a.W, G::WGPC, &a.nstrips, &a.nseg, &a.seg_brows);
     const long items = (long)a.N * a.nstrips * a.nseg;
     if (items >= (1L << 31)) return PWC_ERANGE;
@@ -580,25 +528,10 @@ static int cvm_launch_t(CvmArgs& a, hipStream_t s) {
     return pwc_launch_status();
 }
 
-static int cvm_launch(const float* f0, int f0_cs, const float* f1, int f1_cs, const float* flow, int flow_cs,
-                      float flow_scale, float* out, int out_cs, int pad_ok, float* f0_copy, int f0_copy_cs, int N, int H,
-                      int W, int C, float slope, hipStream_t s) {
-    CvmArgs a;
-    a.f0 = f0; a.f1 = f1; a.flow = flow; a.out = out; a.f0_copy = f0_copy;
-    a.f0_cs = f0_cs; a.f1_cs = f1_cs; a.flow_cs = flow_cs; a.out_cs = out_cs; a.f0_copy_cs = f0_copy_cs;
-    a.N = N; a.H = H; a.W = W; a.flow_scale = flow_scale; a.slope = slope;
-    a.inv_c = 1.0f / (float)C;               // reduce_mean: x * (1/C), within 1 ulp of x / C
-    a.nbrows = (H + 3) / 4;
-    a.pad_ok = pad_ok; a.dbg = nullptr;
-#define CVM_CASE(CGV)                                                                          \
-    case CGV * 16:                                                                             \
-        return flow ? (pad_ok ? cvm_launch_t<CGV, true, true>(a, s) : cvm_launch_t<CGV, true, false>(a, s))         \
-                    : (pad_ok ? cvm_launch_t<CGV, false, true>(a, s) : cvm_launch_t<CGV, false, false>(a, s));
-    switch (C) {
-        CVM_CASE(2)
-        CVM_CASE(4)
-        CVM_CASE(6)
-        default: return PWC_EUNSUPPORTED;
-    }
-#undef CVM_CASE
+static int cvm_launch(CvmArgs& a, int C, hipStream_t s) {
+    a.nbrows = (a.H + 3) / 4;
+    a.dbg = nullptr;
+    return cv_dispatch_cg<2, 4, 6>(C, a.flow != nullptr, a.pad_ok != 0, [&](auto cg, auto warp, auto pad) {
+        return cvm_launch_t<decltype(cg)::value, decltype(warp)::value, decltype(pad)::value>(a, s);
+    });
 }

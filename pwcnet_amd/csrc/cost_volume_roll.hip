@@ -109,14 +109,6 @@ __device__ __forceinline__ void cvr_swap32(float& a, float& b) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
 }
 
-// Workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt (its fence covers
-// global memory), which would wait for the prefetch DMA and for the copy-out stores at every barrier.
-__device__ __forceinline__ void cvr_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // ABL (scripts/exp_cv2.hip only; 0 in the library): 1 = no FMAs, 2 = no DMA, 4 = no stores, 8 = phase stamps
 template <int ABL = 0>
 __global__ __launch_bounds__(CvRollGeom::T) void cost_volume_roll_kernel(const CvRollArgs a) {
@@ -214,7 +206,7 @@ __global__ __launch_bounds__(CvRollGeom::T) void cost_volume_roll_kernel(const C
         issue_pieces(Y0 + 4, 8, 0, 0, false);
         CVR_WAIT_VM(0);
         stamp();
-        cvr_barrier();
+        pwc_lds_barrier();
         stamp();
 
         for (int s = 0; s < nsteps; ++s) {
@@ -310,7 +302,7 @@ __global__ __launch_bounds__(CvRollGeom::T) void cost_volume_roll_kernel(const C
                 (va < 8 ? stp9 : stpn)[offa] = pwc_lrelu(sum * inv_c, a.slope);
             }
             stamp();
-            cvr_barrier();
+            pwc_lds_barrier();
             stamp();
 
             // ---- copy-out: 21 items per pixel (20 quads + the last float), consecutive lanes =
@@ -365,7 +357,7 @@ __global__ __launch_bounds__(CvRollGeom::T) void cost_volume_roll_kernel(const C
                 else CVR_WAIT_VM(2 * G::NST_OUT);
             }
             stamp();
-            cvr_barrier();
+            pwc_lds_barrier();
             stamp();
         }
     }
@@ -413,11 +405,7 @@ static int cv_roll_launch(const float* f0, int f0_cs, const float* f1, int f1_cs
     const long items = (long)N * a.nstrips * a.nseg;
     if (items >= (1L << 31)) return PWC_ERANGE;
     const size_t lds = (size_t)G::LDS_F * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_volume_roll_kernel<0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&cost_volume_roll_kernel<0>>((int)lds);
     const unsigned nwg = (unsigned)(items < 256 ? items : 256);
     hipLaunchKernelGGL((cost_volume_roll_kernel<0>), dim3(nwg), dim3(G::T), lds, s, a);
     return pwc_launch_status();

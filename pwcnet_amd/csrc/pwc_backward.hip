@@ -291,6 +291,8 @@ __global__ __launch_bounds__(256) void warp_grad_kernel(const WarpGradArgs a) {
         const int gy = (int)(r % a.H), n = (int)(r / a.H);
         const float* fp = a.flow + pix * a.flow_cs;
         const float fx = pwc_mul_rounded(fp[0], a.flow_scale), fy = pwc_mul_rounded(fp[1], a.flow_scale);
+        // the forward's corners and weight factors: pwc_bilinear_corners (pwc_common.h), spelled out -- through the helper, whose
+        // operation order is the forward kernels', this kernel was scheduled differently
         const float fx0 = floorf(fx), fy0 = floorf(fy);
         const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
         const float hl = (float)(a.H - 1), wl = (float)(a.W - 1);

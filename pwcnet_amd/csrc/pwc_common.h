@@ -93,6 +93,38 @@ __device__ __forceinline__ float pwc_mul_rounded(float a, float b) {
     return r;
 }
 
+// ---- the corner table of the bilinear warp (bilinear_warp, reference modules.py:107-137), for pixel (gy, gx) of an
+// H x W image and its displacement (fx, fy) = flow * scale, BOTH already rounded products (pwc_mul_rounded: model.py:109 is an
+// op of its own).  The weights come from the UN-clipped floors, the four corner coordinates are clipped independently -- at the
+// image edge two corners may be the same pixel while their weights still differ.  The forward warps (warp_kernel, the fused
+// gathers of cost_volume.hip, cost_volume_mfma.hip, cost_volume_h2.hip) take their corners from here; what a site does with them
+// -- byte or float offsets, out-of-image pixels, the 1/C of the mean -- is its own.  Two kernels spell the same operations out
+// because their device code changed through this function: the table block of cost_volume_blk_kernel and warp_grad_kernel.
+struct PwcCorners {
+    int y0, y1, x0, x1;               // clipped rows / columns of the corners (y0, x0), (y0, x1), (y1, x0), (y1, x1)
+    f32x4 w;                          // the corners' weights, in that order
+};
+__device__ __forceinline__ PwcCorners pwc_bilinear_corners(int gy, int gx, float fx, float fy, int H, int W) {
+    const float fx0 = floorf(fx), fy0 = floorf(fy);
+    const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
+    const float hl = (float)(H - 1), wl = (float)(W - 1);
+    PwcCorners k;
+    k.y0 = (int)fminf(fmaxf((float)gy + fy0, 0.f), hl);
+    k.y1 = (int)fminf(fmaxf((float)gy + fy1, 0.f), hl);
+    k.x0 = (int)fminf(fmaxf((float)gx + fx0, 0.f), wl);
+    k.x1 = (int)fminf(fmaxf((float)gx + fx1, 0.f), wl);
+    k.w = f32x4{(fy1 - fy) * (fx1 - fx), (fy1 - fy) * (fx - fx0), (fy - fy0) * (fx1 - fx), (fy - fy0) * (fx - fx0)};
+    return k;
+}
+// modules.py:132-135: c00*x00 + c01*x01 + c10*x10 + c11*x11, summed left to right (one multiply, three fused multiply-adds)
+__device__ __forceinline__ f32x4 pwc_blend_corners(f32x4 w, f32x4 x00, f32x4 x01, f32x4 x10, f32x4 x11) {
+    f32x4 v = w[0] * x00;
+    v = __builtin_elementwise_fma(f32x4{w[1], w[1], w[1], w[1]}, x01, v);
+    v = __builtin_elementwise_fma(f32x4{w[2], w[2], w[2], w[2]}, x10, v);
+    v = __builtin_elementwise_fma(f32x4{w[3], w[3], w[3], w[3]}, x11, v);
+    return v;
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a fence over global memory as well, which
 // hipcc lowers to `s_waitcnt vmcnt(0)` in front of the s_barrier: every LDS-DMA piece (buffer_load ... lds) and every
 // store in flight is drained at each barrier, and a software pipeline that waits for its pieces with counted

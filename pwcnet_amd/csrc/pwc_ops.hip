@@ -47,21 +47,13 @@ __global__ __launch_bounds__(256) void warp_kernel(const WarpArgs a) {
         const float* xn = a.x + (size_t)n * a.H * a.W * a.x_cs + cq * 4;
         f32x4 v;
         if (BILINEAR) {
-            // modules.py:107-137: weights from un-clipped floors, corners clipped independently
-            const float fx0 = floorf(fx), fy0 = floorf(fy);
-            const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
-            const float hl = (float)(a.H - 1), wl = (float)(a.W - 1);
-            const int y0 = (int)fminf(fmaxf((float)gy + fy0, 0.f), hl);
-            const int y1 = (int)fminf(fmaxf((float)gy + fy1, 0.f), hl);
-            const int x0 = (int)fminf(fmaxf((float)gx + fx0, 0.f), wl);
-            const int x1 = (int)fminf(fmaxf((float)gx + fx1, 0.f), wl);
-            const float c00 = (fy1 - fy) * (fx1 - fx), c01 = (fy1 - fy) * (fx - fx0);
-            const float c10 = (fy - fy0) * (fx1 - fx), c11 = (fy - fy0) * (fx - fx0);
-            const f32x4 v00 = *reinterpret_cast<const f32x4*>(xn + ((size_t)y0 * a.W + x0) * a.x_cs);
-            const f32x4 v01 = *reinterpret_cast<const f32x4*>(xn + ((size_t)y0 * a.W + x1) * a.x_cs);
-            const f32x4 v10 = *reinterpret_cast<const f32x4*>(xn + ((size_t)y1 * a.W + x0) * a.x_cs);
-            const f32x4 v11 = *reinterpret_cast<const f32x4*>(xn + ((size_t)y1 * a.W + x1) * a.x_cs);
-            v = c00 * v00 + c01 * v01 + c10 * v10 + c11 * v11;
+            const PwcCorners k = pwc_bilinear_corners(gy, gx, fx, fy, a.H, a.W);
+            const f32x4 c = k.w;
+            const f32x4 v00 = *reinterpret_cast<const f32x4*>(xn + ((size_t)k.y0 * a.W + k.x0) * a.x_cs);
+            const f32x4 v01 = *reinterpret_cast<const f32x4*>(xn + ((size_t)k.y0 * a.W + k.x1) * a.x_cs);
+            const f32x4 v10 = *reinterpret_cast<const f32x4*>(xn + ((size_t)k.y1 * a.W + k.x0) * a.x_cs);
+            const f32x4 v11 = *reinterpret_cast<const f32x4*>(xn + ((size_t)k.y1 * a.W + k.x1) * a.x_cs);
+            v = c[0] * v00 + c[1] * v01 + c[2] * v10 + c[3] * v11;
         } else {
             // modules.py:85-92: int32 cast truncates toward zero, then clip
             int yy = gy + (int)fy, xx = gx + (int)fx;

@@ -96,12 +96,13 @@ int main() {
             a.f1 = f1;
             // standalone warp kernel
             WarpArgs w{}; w.x = f1; w.flow = fl; w.out = f1w; w.x_cs = sh.C; w.flow_cs = 2; w.out_cs = sh.C; w.H = sh.H; w.W = sh.W;
-            w.C4 = sh.C / 4; w.flow_scale = 5.f; w.total = (long)npix * w.C4;
-            long blocks = (w.total + 255) / 256; if (blocks > 4096) blocks = 4096;
+            w.C4 = sh.C / 4; w.flow_scale = 5.f; w.rows = (int)(npix / sh.W);
+            // (the grid of warp_common, pwc_ops.hip: x walks a row's (pixel, channel quad) elements, y the rows)
+            const dim3 blocks((unsigned)(((long)sh.W * w.C4 + 255) / 256), (unsigned)(w.rows < 65535 ? w.rows : 65535));
             hipEvent_t s, e; hipEventCreate(&s); hipEventCreate(&e);
-            hipLaunchKernelGGL(warp_kernel<true>, dim3(blocks), dim3(256), 0, 0, w);
+            hipLaunchKernelGGL(warp_kernel<true>, blocks, dim3(256), 0, 0, w);
             hipEventRecord(s);
-            for (int i = 0; i < 10; ++i) hipLaunchKernelGGL(warp_kernel<true>, dim3(blocks), dim3(256), 0, 0, w);
+            for (int i = 0; i < 10; ++i) hipLaunchKernelGGL(warp_kernel<true>, blocks, dim3(256), 0, 0, w);
             hipEventRecord(e); hipEventSynchronize(e);
             float ms; hipEventElapsedTime(&ms, s, e);
             rep("warp kernel alone", ms * 100.f, npix * (2.0 * sh.C + 2) * 4 / 1e6);

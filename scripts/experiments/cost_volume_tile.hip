@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void cost_volume_tile_kernel(const CvmArgs 
                 *reinterpret_cast<f32x4*>(en + 4) = w;
             }
         }
-        cvm_barrier();
+        pwc_lds_barrier();
     }
 
     // ---- gather items of a Q row: item e = i * 256 + t -> (pixel, plane g, quad): the C/4 quads of a pixel sit in consecutive
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256, 2) void cost_volume_tile_kernel(const CvmArgs 
             }
         }
     }
-    cvm_barrier();                                                      // the images are complete; the tables are dead
+    pwc_lds_barrier();                                                  // the images are complete; the tables are dead
 
     // ---- D fragment: lane holds P pixels (row kq, column r = 0..3) x Q pixel (row mrow, column mcol).  Stage address of
     // entry (by, bx, r) = sbase + 83 r + 36 by + 4 bx floats; entries with |dx| > 4 go to the dump area, entries with

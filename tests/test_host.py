@@ -202,6 +202,94 @@ def test_f16_conv_entry_points_report_the_same_codes():
     assert not got, got
 
 
+_MIS2 = 4098                # not even 4-byte aligned: the flow operand of the buffer-resource kernels
+_CV_CONCAT_ARGS = "f0 f0_cs f1 f1_cs flow flow_cs scale out out_cs pad copy copy_cs N H W C R slope stream"
+_CV_GOOD = dict(f0=_AL, f0_cs=32, f1=_AL, f1_cs=32, flow=_AL, flow_cs=2, scale=1.25, out=_AL, out_cs=84, pad=0, copy=_AL, copy_cs=32,
+                N=1, H=16, W=32, C=32, R=4, slope=0.1, stream=None)
+_CV_C64 = dict(C=64, f0_cs=64, f1_cs=64, copy_cs=64)
+# entry point -> (argument names in call order, what a call that passes every check changes in _CV_GOOD)
+_CV_CALLS = {
+    "pwc_cost_volume_f32": ("f0 f0_cs f1 f1_cs out out_cs N H W C R slope stream", {}),
+    "pwc_warp_cost_volume_f32": ("f0 f0_cs f1 f1_cs flow flow_cs scale out out_cs N H W C R slope stream", {}),
+    "pwc_cost_volume_coarse_f32": ("f0 f0_cs f1 f1_cs flow flow_cs scale out out_cs copy copy_cs N H W C R slope stream", {}),
+    "pwc_warp_cost_volume_concat_f32": (_CV_CONCAT_ARGS, {}),
+    "pwc_warp_cost_volume_concat_h2_f32": (_CV_CONCAT_ARGS, {}),
+    "pwc_warp_cost_volume_concat_blk_f32": (_CV_CONCAT_ARGS, _CV_C64),
+}
+_CV_CONCAT = tuple(n for n in _CV_CALLS if "concat" in n)
+_CV_COPY = _CV_CONCAT + ("pwc_cost_volume_coarse_f32",)                       # entry points with the f0 concat copy
+_CV_WIDE = dict(H=2048, W=2048)        # 2^22 pixels: a 128-float channel stride is past 2^31 bytes, the 84-float records are not
+# (entry point, the bad arguments, the code): one fault per row first, then rows with two faults that pin which one is reported
+_CV_FAULTS = [(name, bad, code) for name in _CV_CALLS for bad, code in (
+    (dict(f0=None), _EINVAL), (dict(f1=None), _EINVAL), (dict(out=None), _EINVAL),      # a null pointer
+    (dict(N=0), _EINVAL), (dict(H=-1), _EINVAL), (dict(W=0), _EINVAL), (dict(C=0), _EINVAL),    # a non-positive size
+    (dict(R=0), _EUNSUP), (dict(R=5), _EUNSUP),                                         # the search range
+    (dict(f0_cs=28), _EINVAL), (dict(f1_cs=28), _EINVAL), (dict(out_cs=80), _EINVAL),   # a channel stride below C, out_cs below 81
+    (dict(C=30), _EALIGN), (dict(f0=_MIS), _EALIGN), (dict(f1=_MIS), _EALIGN), (dict(f0_cs=66), _EALIGN), (dict(f1_cs=66), _EALIGN),
+    (dict(_BIG), _ERANGE),                                                              # one image past 2^31 bytes
+    (dict(f0=None, f1=_MIS), _EINVAL), (dict(N=0, R=5), _EINVAL), (dict(R=5, f0_cs=28), _EUNSUP), (dict(f0_cs=28, f0=_MIS), _EINVAL),
+    (dict(out_cs=80, f1_cs=66), _EINVAL), (dict(_BIG, f0=_MIS), _EALIGN), (dict(_BIG, N=0), _EINVAL), (dict(_BIG, R=5), _EUNSUP))] + [
+    # search range 3: the two plain entry points take it (rows with a second fault), the others refuse it
+    ("pwc_cost_volume_f32", dict(R=3, out_cs=48), _EINVAL), ("pwc_cost_volume_f32", dict(R=3, f0=_MIS), _EALIGN),
+    ("pwc_cost_volume_f32", dict(_BIG, R=3), _ERANGE), ("pwc_cost_volume_f32", dict(R=1, out_cs=8), _EINVAL),
+    ("pwc_warp_cost_volume_f32", dict(R=3, out_cs=48), _EINVAL), ("pwc_warp_cost_volume_f32", dict(R=3, flow=None), _EINVAL),
+    ("pwc_warp_cost_volume_f32", dict(_BIG, R=3), _ERANGE),
+    ("pwc_warp_cost_volume_f32", dict(flow=None), _EINVAL), ("pwc_warp_cost_volume_f32", dict(flow_cs=1), _EINVAL),
+    ("pwc_warp_cost_volume_f32", dict(_BIG, flow=None), _EINVAL), ("pwc_warp_cost_volume_f32", dict(flow=None, f0=_MIS), _EALIGN),
+    ("pwc_warp_cost_volume_f32", dict(_BIG, flow=_MIS2), _ERANGE)] + [
+    (name, bad, code) for name in _CV_COPY for bad, code in (
+        (dict(R=3), _EUNSUP), (dict(R=3, f0_cs=28), _EUNSUP if name not in _CV_CONCAT else _EINVAL),
+        (dict(R=3, f0=_MIS), _EUNSUP if name not in _CV_CONCAT else _EALIGN),
+        (dict(flow_cs=1), _EINVAL), (dict(copy_cs=28), _EINVAL), (dict(copy=_MIS), _EALIGN), (dict(copy_cs=66), _EALIGN),
+        (dict(flow_cs=1, R=5), _EUNSUP), (dict(copy_cs=28, f0=_MIS), _EINVAL if name not in _CV_CONCAT else _EALIGN),
+        (dict(_BIG, copy=_MIS), _EALIGN if name not in _CV_CONCAT else _ERANGE))] + [
+    ("pwc_cost_volume_coarse_f32", dict(flow_cs=1, R=3), _EUNSUP), ("pwc_cost_volume_coarse_f32", dict(H=4096, W=4096, f1_cs=128), _ERANGE)] + [
+    (name, bad, code) for name in _CV_CONCAT for bad, code in (
+        (dict(out=_MIS), _EALIGN), (dict(out_cs=86), _EALIGN), (dict(flow=_MIS2), _EALIGN),     # what only the buffer-resource kernels need
+        (dict(pad=1, out_cs=81), _EINVAL), (dict(pad=1, out_cs=82), _EINVAL), (dict(pad=2, out_cs=82), _EINVAL),      # out_pad_writable with out_cs < 84
+        (dict(pad=1, out_cs=82, R=3), _EINVAL), (dict(flow_cs=1, R=3), _EINVAL), (dict(pad=1, out_cs=82, f0=_MIS), _EALIGN),
+        (dict(C=48, f0_cs=64, f1_cs=64, copy_cs=64), _EUNSUP), (dict(C=48, f0_cs=64, f1_cs=64, copy_cs=64, out=_MIS), _EUNSUP),
+        (dict(C=16), _EUNSUP), (dict(C=256, f0_cs=256, f1_cs=256, copy_cs=256), _EUNSUP), (dict(R=3, out=_MIS), _EUNSUP),
+        (dict(_BIG, out=_MIS), _ERANGE), (dict(_BIG, flow=_MIS2), _ERANGE),
+        # the range part of a failed eligibility is reported as such only for `out` and f0
+        (dict(_CV_WIDE, f1_cs=128), _EALIGN), (dict(_CV_WIDE, copy_cs=128), _EALIGN), (dict(_CV_WIDE, flow_cs=128), _EALIGN),
+        (dict(_CV_WIDE, f0_cs=128), _ERANGE), (dict(_CV_WIDE, out_cs=128), _ERANGE))] + [
+    # the channel sets of the two families
+    ("pwc_warp_cost_volume_concat_f32", dict(C=128, f0_cs=128, f1_cs=128, copy_cs=128), _EUNSUP),
+    ("pwc_warp_cost_volume_concat_h2_f32", dict(C=128, f0_cs=128, f1_cs=128, copy_cs=128), _EUNSUP),
+    ("pwc_warp_cost_volume_concat_blk_f32", dict(C=32), _EUNSUP),
+    # out_pad_writable == 2 (the flow in channels 81, 82): the h2 entry point only, and only with a flow
+    ("pwc_warp_cost_volume_concat_f32", dict(pad=2), _EUNSUP), ("pwc_warp_cost_volume_concat_blk_f32", dict(pad=2), _EUNSUP),
+    ("pwc_warp_cost_volume_concat_f32", dict(pad=2, out=_MIS), _EUNSUP), ("pwc_warp_cost_volume_concat_blk_f32", dict(pad=2, out=_MIS), _EUNSUP),
+    ("pwc_warp_cost_volume_concat_f32", dict(_BIG, pad=2), _EUNSUP), ("pwc_warp_cost_volume_concat_blk_f32", dict(_BIG, pad=2), _EUNSUP),
+    ("pwc_warp_cost_volume_concat_f32", dict(pad=2, flow_cs=1), _EINVAL), ("pwc_warp_cost_volume_concat_blk_f32", dict(pad=2, flow_cs=1), _EINVAL),
+    ("pwc_warp_cost_volume_concat_h2_f32", dict(pad=2, flow=None), _EINVAL), ("pwc_warp_cost_volume_concat_h2_f32", dict(pad=2, flow=None, out=_MIS), _EALIGN),
+    ("pwc_warp_cost_volume_concat_h2_f32", dict(_BIG, pad=2, flow=None), _ERANGE), ("pwc_warp_cost_volume_concat_h2_f32", dict(pad=2, out=_MIS), _EALIGN),
+    ("pwc_warp_cost_volume_concat_h2_f32", dict(pad=2, flow=None, R=3), _EUNSUP), ("pwc_warp_cost_volume_concat_h2_f32", dict(_BIG, pad=2), _ERANGE),
+]
+
+
+def test_correlation_entry_points_report_the_same_codes():
+    """The argument checks of the correlation entry points (plain, fused-warp, coarse and the three warp + cost volume + concat
+    forms) go through one shared checker; every family keeps the rules that are its own (out_pad_writable == 2, the channel sets,
+    which code a failed eligibility reports).  This table pins which code each entry point returns for a bad call -- one fault at a
+    time, then two at once (which one wins) -- as recorded from the library before the checks were shared.  Every row fails a
+    check: nothing is launched, no GPU is needed."""
+    L = _lib.lib()
+    assert all(code != 0 for _, _, code in _CV_FAULTS)
+    assert {name for name, _, _ in _CV_FAULTS} == set(_CV_CALLS)
+    got = []
+    for name, bad, code in _CV_FAULTS:
+        names, own = _CV_CALLS[name]
+        good = dict(_CV_GOOD, **own)
+        assert set(bad) <= set(good), (name, bad)
+        args = dict(good, **bad)
+        rc = getattr(L, name)(*[args[k] for k in names.split()])
+        if rc != code:
+            got.append((name, bad, code, rc))
+    assert not got, got
+
+
 def test_round5_routing_rules_are_host_logic():
     """Which kernel takes which launch is decided by pure host functions of the library (no GPU needed): the small-launch conv
     (up to 1e8 multiply-adds and 4096 output pixels; stride-2 / thin layers beyond), the weights-stationary thin-input conv
