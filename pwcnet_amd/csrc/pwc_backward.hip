@@ -14,7 +14,6 @@
 //   pwc_resize_bilinear_grad    transpose of the TF-legacy resize  modules.py:283-284
 //   pwc_warp_bilinear_grad      d/dx and d/dflow of bilinear_warp  modules.py:99-137
 //   pwc_cost_volume_grad        d/df0 and d/df1w of the cost volume modules.py:158-204
-//   pwc_flow_norm_grad_f32      gradient of L1loss / L2loss terms  losses.py:4-8,20-29
 //   pwc_adam_step_f32           tf.train.AdamOptimizer update + the weights' L2 term  train.py:75,90
 //   pwc_conv3x3_dgrad_s2_narrow_f32   data gradient of a stride-2 conv with 1..4 input channels (the images)
 #include "pwc_common.h"
@@ -583,63 +582,6 @@ extern "C" int pwc_cost_volume_grad_f32(const float* f0, int f0_cs, const float*
     }
     if (df0) hipLaunchKernelGGL(cost_volume_grad_kernel<0>, dim3((unsigned)nblk), dim3(256), lds0, (hipStream_t)stream, a);
     if (df1w) hipLaunchKernelGGL(cost_volume_grad_kernel<1>, dim3((unsigned)nblk), dim3(256), lds1, (hipStream_t)stream, a);
-    return pwc_launch_status();
-}
-
-// ------------------------------------------------------------------ loss gradient
-// d/dpred of  scale * sum_p || pred[p] - gt[nearest(p)] / gt_div ||_ord   (losses.py:4-8 inside :20-29,38-45):
-//   ord 2: (pred - g) / ||pred - g||_2   (0 where the norm is 0);   ord 1: sign(pred - g)
-struct FlowNormGradArgs {
-    const float* pred;
-    const float* gt;
-    float* dpred;
-    int pred_cs, gt_cs, dpred_cs;
-    int N, H, W, GH, GW;
-    float sy, sx, gt_div, scale;
-    int ord, accumulate;
-};
-
-__global__ __launch_bounds__(256) void flow_norm_grad_kernel(const FlowNormGradArgs a) {
-    const long npix = (long)a.N * a.H * a.W;
-    for (long p = blockIdx.x * 256L + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
-        const int x = (int)(p % a.W);
-        const long r = p / a.W;
-        const int y = (int)(r % a.H), n = (int)(r / a.H);
-        const int gy = min((int)floorf(pwc_mul_rounded((float)y, a.sy)), a.GH - 1);
-        const int gx = min((int)floorf(pwc_mul_rounded((float)x, a.sx)), a.GW - 1);
-        const float* pp = a.pred + p * a.pred_cs;
-        const float* gp = a.gt + (((long)n * a.GH + gy) * a.GW + gx) * a.gt_cs;
-        // the loss is norm(gt_down - pred): its gradient w.r.t. pred is -(gt_down - pred) / norm
-        const float dx = pp[0] - gp[0] / a.gt_div, dy = pp[1] - gp[1] / a.gt_div;
-        float ox, oy;
-        if (a.ord == 1) {
-            ox = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : 0.f);
-            oy = dy > 0.f ? 1.f : (dy < 0.f ? -1.f : 0.f);
-        } else {
-            const float nrm = sqrtf(dx * dx + dy * dy);
-            ox = nrm > 0.f ? dx / nrm : 0.f;
-            oy = nrm > 0.f ? dy / nrm : 0.f;
-        }
-        float* d = a.dpred + p * a.dpred_cs;
-        d[0] = a.accumulate ? d[0] + a.scale * ox : a.scale * ox;
-        d[1] = a.accumulate ? d[1] + a.scale * oy : a.scale * oy;
-    }
-}
-
-extern "C" int pwc_flow_norm_grad_f32(const float* pred, int pred_cs, const float* gt, int gt_cs, int N, int H, int W, int GH,
-                                      int GW, float gt_div, int ord, float scale, float* dpred, int dpred_cs,
-                                      int accumulate, pwc_stream_t stream) {
-    if (!pred || !gt || !dpred || N <= 0 || H <= 0 || W <= 0 || GH <= 0 || GW <= 0) return PWC_EINVAL;
-    if (pred_cs < 2 || gt_cs < 2 || dpred_cs < 2 || !(gt_div != 0.f)) return PWC_EINVAL;
-    if (ord != 1 && ord != 2) return PWC_EUNSUPPORTED;
-    FlowNormGradArgs a;
-    a.pred = pred; a.gt = gt; a.dpred = dpred; a.pred_cs = pred_cs; a.gt_cs = gt_cs; a.dpred_cs = dpred_cs;
-    a.N = N; a.H = H; a.W = W; a.GH = GH; a.GW = GW;
-    a.sy = (float)GH / (float)H; a.sx = (float)GW / (float)W; a.gt_div = gt_div; a.scale = scale; a.ord = ord;
-    a.accumulate = accumulate;
-    long blocks = ((long)N * H * W + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(flow_norm_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return pwc_launch_status();
 }
 

@@ -9,58 +9,17 @@
 //
 // rho(d) = (d^2 + eps^2)^q (generalised Charbonnier), rho'(d) = 2 q d (d^2 + eps^2)^(q - 1).  The images are constants.
 // A pixel of the photometric term contributes iff it is valid and its sample point lies inside the frame; the others are
-// selected out as in pwc_masked.hip: a masked pixel reads neither its flow nor an image, an out-of-frame one no image.
+// selected out as in pwc_flow_loss.hip: a masked pixel reads neither its flow nor an image, an out-of-frame one no image.
 // rho' turns a rounding error of d into one of up to 1 / eps times its size in the gradient, so the sample point, the bilinear
 // weights and the difference d are computed in double (a few dozen operations per pixel of kernels that wait for memory) and d is
 // rounded to fp32 once: the gradient then carries fp32's RELATIVE error.  Images have 1..4 channels at any channel stride:
 // scalar loads, no alignment asked.  Sums: every workgroup adds its pixels in a fixed tree and writes one partial, one thread
 // per image adds the partials in index order -- two calls give the same bits.  The gradients are gathers, one lane per pixel.
-#include "pwc_common.h"
+// Partition, tree, final sum and the gradients' pixel walk and store are those of loss_common.h.
+#include "loss_common.h"
 
 __device__ __forceinline__ float unsup_rho(float d, float eps2, float q) { return powf(d * d + eps2, q); }
 __device__ __forceinline__ float unsup_rho_grad(float d, float eps2, float q) { return 2.f * q * d * powf(d * d + eps2, q - 1.f); }
-
-// the partition of pwc_flow_norm_workspace_floats (pwc_ops.hip): at most 256 parts of an image
-static inline long unsup_parts(int H, int W) {
-    long parts = ((long)H * W + 255) / 256;
-    return parts > 256 ? 256 : parts;
-}
-
-// workgroup sum of (s, cnt) in a fixed tree; thread 0 writes the part
-__device__ __forceinline__ void unsup_block_sums(float s, int cnt, float* partial, int* partial_n) {
-    __shared__ float red[256];
-    __shared__ int redn[256];
-    red[threadIdx.x] = s;
-    redn[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            red[threadIdx.x] += red[threadIdx.x + k];
-            redn[threadIdx.x] += redn[threadIdx.x + k];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const size_t o = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        partial[o] = red[0];
-        if (partial_n) partial_n[o] = redn[0];
-    }
-}
-
-__global__ void unsup_final_kernel(const float* __restrict__ partial, const int* __restrict__ partial_n, int nparts, int nimg,
-                                   float* __restrict__ out, int* __restrict__ out_n) {
-    // one thread per image: the partials are added in index order (deterministic), the counts as integers (exact)
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= nimg) return;
-    float s = 0.f;
-    int c = 0;
-    for (int i = 0; i < nparts; ++i) {
-        s += partial[(size_t)n * nparts + i];
-        if (partial_n) c += partial_n[(size_t)n * nparts + i];
-    }
-    out[n] = s;
-    if (out_n) out_n[n] = c;
-}
 
 // ------------------------------------------------------------------ photometric term
 struct PhotoArgs {
@@ -128,20 +87,18 @@ __global__ __launch_bounds__(256) void photometric_partial_kernel(const PhotoArg
             ++cnt;
         }
     }
-    unsup_block_sums(s, cnt, a.partial, a.partial_n);
+    pwc_loss_write_part<true>(s, cnt, a.partial, a.partial_n);
 }
 
 template <int C>
 __global__ __launch_bounds__(256) void photometric_grad_kernel(const PhotoArgs a) {
     const long npix = (long)a.N * a.H * a.W;
     for (long p = blockIdx.x * 256L + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
-        const int x = (int)(p % a.W);
-        const long r = p / a.W;
-        const int y = (int)(r % a.H), n = (int)(r / a.H);
+        const PwcLossPixel px = pwc_loss_pixel(p, a.H, a.W);
         float* o = a.dflow + p * a.dflow_cs;
         float d[C], gx[C], gy[C];
-        if (!photo_pixel<C, true>(a, n, y, x, (size_t)p, d, gx, gy)) {
-            if (!a.accumulate) { o[0] = 0.f; o[1] = 0.f; }       // accumulate: a pixel that does not contribute adds nothing
+        if (!photo_pixel<C, true>(a, px.n, px.y, px.x, (size_t)p, d, gx, gy)) {
+            pwc_grad_skip2(o, a.accumulate);
             continue;
         }
         float sx = 0.f, sy = 0.f;
@@ -152,10 +109,8 @@ __global__ __launch_bounds__(256) void photometric_grad_kernel(const PhotoArgs a
             sy -= rg * gy[c];
         }
         // (the products are rounded on their own: accumulate adds exactly what a plain call writes)
-        const float up = a.dsums[n] * a.flow_scale;
-        const float vx = pwc_mul_rounded(up, sx), vy = pwc_mul_rounded(up, sy);
-        o[0] = a.accumulate ? o[0] + vx : vx;
-        o[1] = a.accumulate ? o[1] + vy : vy;
+        const float up = a.dsums[px.n] * a.flow_scale;
+        pwc_grad_store2(o, a.accumulate, 1.f, pwc_mul_rounded(up, sx), pwc_mul_rounded(up, sy));
     }
 }
 
@@ -165,24 +120,21 @@ static int photo_check(const float* im0, int im0_cs, const float* im1, int im1_c
     if (C < 1 || C > 4) return PWC_EUNSUPPORTED;
     if (im0_cs < C || im1_cs < C || flow_cs < 2) return PWC_EINVAL;
     if (!(eps > 0.f) || !(q > 0.f && q <= 1.f)) return PWC_EINVAL;
-    if ((long)H * W >= (1L << 31) || N > 65535) return PWC_ERANGE;
     return PWC_OK;
 }
 
-extern "C" size_t pwc_photometric_workspace_floats(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0) return 0;
-    return 2 * (size_t)N * unsup_parts(H, W);       // a float sum and an int32 count per part
-}
+// a float sum and an int32 count per part
+extern "C" size_t pwc_photometric_workspace_floats(int N, int H, int W) { return pwc_loss_workspace_floats(N, H, W, 2); }
 
 extern "C" int pwc_photometric_sums_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
                                         float flow_scale, const uint8_t* valid, int N, int H, int W, int C, float eps, float q,
                                         float* workspace, size_t workspace_floats, float* out_sums, int32_t* out_counts,
                                         pwc_stream_t stream) {
-    const int rc = photo_check(im0, im0_cs, im1, im1_cs, flow, flow_cs, N, H, W, C, eps, q);
+    int rc = photo_check(im0, im0_cs, im1, im1_cs, flow, flow_cs, N, H, W, C, eps, q);
+    if (rc == PWC_OK) rc = pwc_loss_sums_check(N, H, W, 2, workspace_floats);
     if (rc != PWC_OK) return rc;
     if (!workspace || !out_sums || !out_counts) return PWC_EINVAL;
-    if (workspace_floats < pwc_photometric_workspace_floats(N, H, W)) return PWC_EINVAL;
-    const int parts = (int)unsup_parts(H, W);
+    const int parts = (int)pwc_loss_parts(H, W);
     PhotoArgs a;
     a.im0 = im0; a.im1 = im1; a.flow = flow; a.valid = valid; a.dsums = nullptr; a.dflow = nullptr;
     a.partial = workspace; a.partial_n = reinterpret_cast<int*>(workspace + (size_t)N * parts);
@@ -195,8 +147,7 @@ extern "C" int pwc_photometric_sums_f32(const float* im0, int im0_cs, const floa
     case 3: hipLaunchKernelGGL(photometric_partial_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
     default: hipLaunchKernelGGL(photometric_partial_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
     }
-    hipLaunchKernelGGL(unsup_final_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
-                       (const float*)a.partial, (const int*)a.partial_n, parts, N, out_sums, (int*)out_counts);
+    pwc_loss_final_launch(workspace, parts, N, out_sums, out_counts, stream);
     return pwc_launch_status();
 }
 
@@ -205,15 +156,14 @@ extern "C" int pwc_photometric_grad_f32(const float* im0, int im0_cs, const floa
                                         const float* dsums, float* dflow, int dflow_cs, int accumulate, pwc_stream_t stream) {
     const int rc = photo_check(im0, im0_cs, im1, im1_cs, flow, flow_cs, N, H, W, C, eps, q);
     if (rc != PWC_OK) return rc;
+    if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
     if (!dsums || !dflow || dflow_cs < 2) return PWC_EINVAL;
     PhotoArgs a;
     a.im0 = im0; a.im1 = im1; a.flow = flow; a.valid = valid; a.dsums = dsums; a.dflow = dflow;
     a.partial = nullptr; a.partial_n = nullptr;
     a.im0_cs = im0_cs; a.im1_cs = im1_cs; a.flow_cs = flow_cs; a.dflow_cs = dflow_cs;
     a.N = N; a.H = H; a.W = W; a.flow_scale = flow_scale; a.eps2 = eps * eps; a.q = q; a.accumulate = accumulate;
-    long blocks = ((long)N * H * W + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid = pwc_loss_grad_blocks(N, H, W);
     switch (C) {
     case 1: hipLaunchKernelGGL(photometric_grad_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
     case 2: hipLaunchKernelGGL(photometric_grad_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
@@ -264,15 +214,14 @@ __global__ __launch_bounds__(256) void flow_smoothness_partial_kernel(const Smoo
             s += smooth_weight(a, pix, pix + a.W) * (unsup_rho(g[0] - u, a.eps2, a.q) + unsup_rho(g[1] - v, a.eps2, a.q));
         }
     }
-    unsup_block_sums(s, 0, a.partial, nullptr);
+    pwc_loss_write_part<false>(s, 0, a.partial, nullptr);
 }
 
 __global__ __launch_bounds__(256) void flow_smoothness_grad_kernel(const SmoothArgs a) {
     const long npix = (long)a.N * a.H * a.W;
     for (long p = blockIdx.x * 256L + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
-        const int x = (int)(p % a.W);
-        const long r = p / a.W;
-        const int y = (int)(r % a.H), n = (int)(r / a.H);
+        const PwcLossPixel px = pwc_loss_pixel(p, a.H, a.W);
+        const int x = px.x, y = px.y;
         const float* f = a.flow + p * a.flow_cs;
         const float u = f[0], v = f[1];
         float gu = 0.f, gv = 0.f;
@@ -301,11 +250,8 @@ __global__ __launch_bounds__(256) void flow_smoothness_grad_kernel(const SmoothA
             gu += w * unsup_rho_grad(u - g[0], a.eps2, a.q);
             gv += w * unsup_rho_grad(v - g[1], a.eps2, a.q);
         }
-        const float up = a.dsums[n];
-        const float vu = pwc_mul_rounded(up, gu), vv = pwc_mul_rounded(up, gv);
-        float* o = a.dflow + p * a.dflow_cs;
-        o[0] = a.accumulate ? o[0] + vu : vu;
-        o[1] = a.accumulate ? o[1] + vv : vv;
+        const float up = a.dsums[px.n];
+        pwc_grad_store2(a.dflow + p * a.dflow_cs, a.accumulate, 1.f, pwc_mul_rounded(up, gu), pwc_mul_rounded(up, gv));
     }
 }
 
@@ -315,30 +261,25 @@ static int smooth_check(const float* flow, int flow_cs, const float* image, int 
     if (image && (C < 1 || C > 4)) return PWC_EUNSUPPORTED;
     if (image && image_cs < C) return PWC_EINVAL;
     if (!(eps > 0.f) || !(q > 0.f && q <= 1.f) || !(alpha >= 0.f)) return PWC_EINVAL;
-    if ((long)H * W >= (1L << 31) || N > 65535) return PWC_ERANGE;
     return PWC_OK;
 }
 
-extern "C" size_t pwc_flow_smoothness_workspace_floats(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)N * unsup_parts(H, W);
-}
+extern "C" size_t pwc_flow_smoothness_workspace_floats(int N, int H, int W) { return pwc_loss_workspace_floats(N, H, W, 1); }
 
 extern "C" int pwc_flow_smoothness_sums_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
                                             float eps, float q, int N, int H, int W, float* workspace, size_t workspace_floats,
                                             float* out_sums, pwc_stream_t stream) {
-    const int rc = smooth_check(flow, flow_cs, image, image_cs, C, alpha, eps, q, N, H, W);
+    int rc = smooth_check(flow, flow_cs, image, image_cs, C, alpha, eps, q, N, H, W);
+    if (rc == PWC_OK) rc = pwc_loss_sums_check(N, H, W, 1, workspace_floats);
     if (rc != PWC_OK) return rc;
     if (!workspace || !out_sums) return PWC_EINVAL;
-    if (workspace_floats < pwc_flow_smoothness_workspace_floats(N, H, W)) return PWC_EINVAL;
-    const int parts = (int)unsup_parts(H, W);
+    const int parts = (int)pwc_loss_parts(H, W);
     SmoothArgs a;
     a.flow = flow; a.image = image; a.dsums = nullptr; a.dflow = nullptr; a.partial = workspace;
     a.flow_cs = flow_cs; a.image_cs = image_cs; a.dflow_cs = 0;
     a.N = N; a.H = H; a.W = W; a.C = C; a.alpha = alpha; a.eps2 = eps * eps; a.q = q; a.accumulate = 0;
     hipLaunchKernelGGL(flow_smoothness_partial_kernel, dim3((unsigned)parts, (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(unsup_final_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
-                       (const float*)workspace, (const int*)nullptr, parts, N, out_sums, (int*)nullptr);
+    pwc_loss_final_launch(workspace, parts, N, out_sums, nullptr, stream);
     return pwc_launch_status();
 }
 
@@ -347,13 +288,12 @@ extern "C" int pwc_flow_smoothness_grad_f32(const float* flow, int flow_cs, cons
                                             int dflow_cs, int accumulate, pwc_stream_t stream) {
     const int rc = smooth_check(flow, flow_cs, image, image_cs, C, alpha, eps, q, N, H, W);
     if (rc != PWC_OK) return rc;
+    if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
     if (!dsums || !dflow || dflow_cs < 2) return PWC_EINVAL;
     SmoothArgs a;
     a.flow = flow; a.image = image; a.dsums = dsums; a.dflow = dflow; a.partial = nullptr;
     a.flow_cs = flow_cs; a.image_cs = image_cs; a.dflow_cs = dflow_cs;
     a.N = N; a.H = H; a.W = W; a.C = C; a.alpha = alpha; a.eps2 = eps * eps; a.q = q; a.accumulate = accumulate;
-    long blocks = ((long)N * H * W + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(flow_smoothness_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(flow_smoothness_grad_kernel, pwc_loss_grad_blocks(N, H, W), dim3(256), 0, (hipStream_t)stream, a);
     return pwc_launch_status();
 }

@@ -1,4 +1,4 @@
-"""GPU tests of the sparse-ground-truth path: the masked loss sums and gradient (pwc_masked.hip) against float64, their
+"""GPU tests of the sparse-ground-truth path: the masked loss sums and gradient (pwc_flow_loss.hip) against float64, their
 identity with the unmasked kernels under an all-ones mask, the flow-metrics kernel, the Trainer with a mask against float64
 autograd (bounds and machinery of tests/test_gpu_grad.py), the sharded evaluation with metrics and the two CLIs.
 
