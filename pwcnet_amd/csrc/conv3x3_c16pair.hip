@@ -73,7 +73,6 @@ constexpr int C16_NPC = 48;                    // 1 KB staging pieces (45 hold r
 constexpr int C16_S0 = 0, C16_IN0 = C16_NPC * 1024, C16_MID0 = C16_IN0 + C16_IMG, C16_LDS = C16_MID0 + C16_IMG + 1024;
 constexpr int C16_MT_A = 41;                   // 16-pixel tiles of the intermediate: linear pixels [36, 692)
 constexpr int C16_MT_B = 36;                   // ... of the output: [72, 648) = rows 2 .. 17
-constexpr unsigned C16_OOB = 0x7FFF0000u;
 // FIRST form: the raw patch is 41 rows x 73 pixels x 3 floats = 55 16-byte chunks a row; a row's fetch instruction writes 1 KB, the
 // row pitch of 1072 bytes keeps the three rows a pixel reads 12 banks apart (41 x 1072 = 43 952 bytes of the 48 KB staging area)
 constexpr int C16_RAW_ROWS = 41, C16_RAW_CHUNKS = 55, C16_RAW_PITCH = 1072;
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
                 const int cb = (2 * (bx * 32 - 2)) * 12 + 16 * c;                    // first byte of the chunk within the image row
                 const bool ok = r < C16_RAW_ROWS && (unsigned)c < (unsigned)C16_RAW_CHUNKS && (unsigned)yy < (unsigned)a.H0 &&
                                 (unsigned)cb < (unsigned)rowb;
-                p_voff[i] = ok ? (unsigned)(yy * rowb + cb) : C16_OOB;
+                p_voff[i] = ok ? (unsigned)(yy * rowb + cb) : PWC_OOB;
             }
             return;
         }
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
             const int pr = rec / C16_P, pc = rec - pr * C16_P;
             const int yy = by * 16 - 2 + pr, xx = bx * 32 - 2 + pc;
             const bool ok = rec < C16_NPIX && (unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W;
-            p_voff[i] = ok ? (unsigned)(((yy * a.W + xx) * a.x_cs + (lane & 3) * 4) * 4) : C16_OOB;
+            p_voff[i] = ok ? (unsigned)(((yy * a.W + xx) * a.x_cs + (lane & 3) * 4) * 4) : PWC_OOB;
         }
     };
     auto patch_issue = [&]() {
@@ -334,7 +333,7 @@ __global__ __launch_bounds__(512) void conv3x3_c16pair_kernel(const C16Args a) {
             const bool ok = pc >= 2 && pc < 34 && yy < a.H && xx < a.W;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], o[e] * a.slope);
-            const unsigned vo = ok ? (unsigned)(((yy * a.W + xx) * a.y_cs + 4 * kq) * 4) : C16_OOB;
+            const unsigned vo = ok ? (unsigned)(((yy * a.W + xx) * a.y_cs + 4 * kq) * 4) : PWC_OOB;
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, (int)vo, 0, 0);
         }
     }
@@ -423,7 +422,7 @@ static int c3c16pair_run(const float* x_a, int N_a, const float* x_b, int N_b, c
         !pwc_aligned16(bias0) || !pwc_aligned16(bias1) || !pwc_aligned16(bias2))
         return PWC_EALIGN;
     const int H = (H0 + 1) / 2, W = W0 / 2;
-    if ((long)H0 * W0 * 12 >= (long)C16_OOB || (long)H * W * y_cs * 4 >= (long)C16_OOB) return PWC_ERANGE;
+    if ((long)H0 * W0 * 12 >= (long)PWC_OOB || (long)H * W * y_cs * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     C16Args a;
     a.x = x_a; a.x_b = x_b; a.N_a = N_a; a.wp = packed; a.b0 = bias0; a.b1 = bias1; a.b2 = bias2; a.y = y; a.x_cs = 3; a.y_cs = y_cs;
     a.N = N_a + N_b; a.H = H; a.W = W; a.H0 = H0; a.W0 = W0; a.pad_t = H0 & 1; a.slope = slope;      // TF 'SAME', stride 2: odd sizes pad one row on top
@@ -449,7 +448,7 @@ static int c16pair_run(const float* x, int x_cs, const float* packed, const floa
     if (!bias2) return PWC_EINVAL;
     if (const int rc = pwc_conv_io_check(x, x_cs, 16, y, y_cs, 16, packed, bias1, N, H, W, true)) return rc;
     if (!pwc_aligned16(bias2)) return PWC_EALIGN;
-    if ((long)H * W * x_cs * 4 >= (long)C16_OOB || (long)H * W * y_cs * 4 >= (long)C16_OOB) return PWC_ERANGE;
+    if ((long)H * W * x_cs * 4 >= (long)PWC_OOB || (long)H * W * y_cs * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     C16Args a;
     a.x = x; a.wp = packed; a.b1 = bias1; a.b2 = bias2; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;
     a.N = N; a.H = H; a.W = W; a.slope = slope;

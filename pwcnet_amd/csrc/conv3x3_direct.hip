@@ -128,10 +128,7 @@ __global__ __launch_bounds__(256) void conv3x3_smallcin_kernel(const DirectArgs 
                 }
             }
         }
-        if (a.apply_act) {
-            acc[0] = pwc_lrelu(acc[0], a.slope); acc[1] = pwc_lrelu(acc[1], a.slope);
-            acc[2] = pwc_lrelu(acc[2], a.slope); acc[3] = pwc_lrelu(acc[3], a.slope);
-        }
+        if (a.apply_act) acc = pwc_lrelu4(acc, a.slope);
         *reinterpret_cast<f32x4*>(a.y + (size_t)m * a.y_cs + cq * 4) = acc;
     }
 }
@@ -299,7 +296,6 @@ __global__ __launch_bounds__(256) void conv3x3_head2_wide_kernel(const DirectArg
 //                is a kernel constant and whose scalar offset is the group's origin -- no address arithmetic in the loop
 //                (groups that touch the SAME padding take a masked path: out-of-image taps become out-of-range offsets);
 //   D: lane holds couts 4 (lane >> 4) .. + 3 of pixel lane & 15: one 16-byte store.
-constexpr unsigned C3M_OOB = 0x7FFF0000u;
 __global__ __launch_bounds__(256) void conv3x3_cin3_mfma_kernel(const DirectArgs a, int groups_per_row, int nrows, int rstep, int N) {
     const int lane = threadIdx.x & 63;
     const int fr = lane & 15, fq = lane >> 4;
@@ -316,7 +312,7 @@ __global__ __launch_bounds__(256) void conv3x3_cin3_mfma_kernel(const DirectArgs
         kdy[i] = kv ? ty * a.dil : -(1 << 20);           // k = 27: never inside the image
         kdx[i] = tx * a.dil + fr * a.stride;
         kci[i] = ci;
-        koff[i] = kv ? (unsigned)(((kdy[i] * a.W + kdx[i]) * a.x_cs + ci) * 4) : C3M_OOB;
+        koff[i] = kv ? (unsigned)(((kdy[i] * a.W + kdx[i]) * a.x_cs + ci) * 4) : PWC_OOB;
     }
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)a.x, 0, (int)((long)N * a.H * a.W * a.x_cs * 4), 0x00020000);
@@ -345,16 +341,13 @@ __global__ __launch_bounds__(256) void conv3x3_cin3_mfma_kernel(const DirectArgs
                 const int iy = iy0 + kdy[i], ix = ix0 + kdx[i];
                 const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
                 const long off = (((long)n * a.H + iy) * a.W + ix) * a.x_cs * 4 + kci[i] * 4;
-                b[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, ok ? (int)off : (int)C3M_OOB, 0, 0));
+                b[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, ok ? (int)off : (int)PWC_OOB, 0, 0));
             }
         }
         f32x4 acc = b4;
 #pragma unroll
         for (int i = 0; i < 7; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], b[i], acc, 0, 0, 0);
-        if (a.apply_act) {
-            acc[0] = pwc_lrelu(acc[0], a.slope); acc[1] = pwc_lrelu(acc[1], a.slope);
-            acc[2] = pwc_lrelu(acc[2], a.slope); acc[3] = pwc_lrelu(acc[3], a.slope);
-        }
+        if (a.apply_act) acc = pwc_lrelu4(acc, a.slope);
         if (ox0 + fr < a.Wo)
             *reinterpret_cast<f32x4*>(a.y + (((size_t)n * a.Ho + oy) * a.Wo + ox0 + fr) * a.y_cs + 4 * fq) = acc;
     }
@@ -400,7 +393,7 @@ __global__ __launch_bounds__(256) void conv3x3_head2_mfma_kernel(const DirectArg
         const int py = j / HM_PW, px = j - py * HM_PW;
         const int yy = y0 - 1 + py, xx = x0 - 1 + px;
         const bool ok = wave + 4 * gi < HM_NG && j < HM_NP && (unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W;
-        const int vo = ok ? ((yy * a.W + xx) * a.x_cs + 8 * kq) * 4 : (int)C3M_OOB;
+        const int vo = ok ? ((yy * a.W + xx) * a.x_cs + 8 * kq) * 4 : (int)PWC_OOB;
         lo[gi] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, vo, 0, 0));
         hi[gi] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, vo, 16, 0));
     }
@@ -493,7 +486,7 @@ __global__ __launch_bounds__(256) void conv3x3_head2_widemfma_kernel(const Direc
         f32x4 lo[GPW], hi[GPW];
 #pragma unroll
         for (int gi = 0; gi < GPW; ++gi) {
-            const int vo = (pvo[gi] >= 0 && cok) ? pvo[gi] + c0 * 4 : (int)C3M_OOB;
+            const int vo = (pvo[gi] >= 0 && cok) ? pvo[gi] + c0 * 4 : (int)PWC_OOB;
             lo[gi] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, vo, 0, 0));
             hi[gi] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, vo, 16, 0));
         }
@@ -555,7 +548,7 @@ extern "C" int pwc_conv3x3_direct_f32(const float* x, int x_cs, const float* w_h
     const unsigned gx = (unsigned)((a.M + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
     if (Cin == 3 && Cout == 16 && !residual && (y_cs & 3) == 0 && pwc_aligned16(y) && pwc_aligned16(bias) &&
-        (long)N * H * W * x_cs * 4 < (long)C3M_OOB) {
+        (long)N * H * W * x_cs * 4 < (long)PWC_OOB) {
         const int gpr = (a.Wo + 15) / 16;
         const long nrows = (long)N * a.Ho;
         if (nrows < (1L << 30) && gpr <= 8192) {
@@ -576,7 +569,7 @@ extern "C" int pwc_conv3x3_direct_f32(const float* x, int x_cs, const float* w_h
         return pwc_launch_status();
     }
     if (Cout == 2 && Cin == 32 && vec4 && stride == 1 && dilation == 1 && (long)H * W >= 4096 &&
-        (long)H * W * x_cs * 4 < (long)C3M_OOB) {
+        (long)H * W * x_cs * 4 < (long)PWC_OOB) {
         const int tiles_x = (W + HM_C - 1) / HM_C, tiles_y = (H + HM_R - 1) / HM_R;
         const long nblk = (long)N * tiles_x * tiles_y;
         if (nblk < (1L << 31)) {
@@ -585,7 +578,7 @@ extern "C" int pwc_conv3x3_direct_f32(const float* x, int x_cs, const float* w_h
         }
     }
     if (Cout == 2 && Cin >= 64 && Cin % 16 == 0 && vec4 && stride == 1 && dilation == 1 && pwc_aligned16(w_hwio) &&
-        (long)H * W * x_cs * 4 < (long)C3M_OOB) {
+        (long)H * W * x_cs * 4 < (long)PWC_OOB) {
         // wide heads (use_dc=True): the 1x1-GEMM form on the matrix pipe
         const int tiles_x = (W + HM_C - 1) / HM_C, tiles_y = (H + HM_R - 1) / HM_R;
         const long nblk = (long)N * tiles_x * tiles_y;

@@ -103,7 +103,6 @@ struct H2Args {
     unsigned* status;
 };
 
-constexpr unsigned H2_OOB = 0x7FFF0000u;
 constexpr int H2_MAX_COUT = 512;             // (the bias lives in LDS)
 constexpr int H2_SC1 = 16;                   // aux bit of the buffer intrinsics: device-scope access (gfx940+)
 constexpr int H2_MIN_STAGES = 3;              // stream-K only where a CU gets at least this many 16-channel stages
@@ -443,7 +442,7 @@ __global__ __launch_bounds__(512) void conv3x3_h2_kernel(const H2Args a) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], o[e] * a.slope);
                     }
-                    const unsigned vo = inside ? (unsigned)(((opy * a.Wo + opx) * a.y_cs + co) * 4) : H2_OOB;
+                    const unsigned vo = inside ? (unsigned)(((opy * a.Wo + opx) * a.y_cs + co) * 4) : PWC_OOB;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, (int)vo, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);                    // (also bounds the registers the hoisted loads take)
                     asm volatile("s_nop 7" ::: "memory");                 // see the published sums above
@@ -829,13 +828,13 @@ static int h2_run(const float* x, int x_cs, const float* packed_w, const float* 
         const int cb = x3 ? Cin_b_phys : Cin_phys - Cin_a_phys;
         if (Cin_a_phys <= 0 || Cin_a_phys >= Cin_phys || (Cin_a_phys % 16) || x_cs < Cin_a_phys - slack || x2_cs < cb - slack) return PWC_EINVAL;
         if ((x2_cs & 3) || !pwc_aligned16(x2)) return PWC_EALIGN;
-        if ((long)H * W * x2_cs * 4 >= (long)H2_OOB) return PWC_ERANGE;
+        if ((long)H * W * x2_cs * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     }
     if (x3) {
         const int cc = Cin_phys - Cin_a_phys - Cin_b_phys;
         if (Cin_b_phys <= 0 || (Cin_b_phys % 16) || cc <= 0 || x3_cs < cc - 12 || dilation != 1) return PWC_EINVAL;
         if ((x3_cs & 3) || !pwc_aligned16(x3)) return PWC_EALIGN;
-        if ((long)H * W * x3_cs * 4 >= (long)H2_OOB) return PWC_ERANGE;
+        if ((long)H * W * x3_cs * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     }
     if (reinterpret_cast<uintptr_t>(status) & 7u) return PWC_EALIGN;
     if (dilation < 1 || (stride != 1 && stride != 2)) return PWC_EINVAL;
@@ -843,7 +842,7 @@ static int h2_run(const float* x, int x_cs, const float* packed_w, const float* 
     // (the channels x itself must hold: all of them, or -- checked above -- its share of two or three operands)
     if (const int rc = pwc_conv_io_check(x, x_cs, x2 ? Cin_a_phys - slack : Cin_phys, y, y_cs, Cout, packed_w, bias, N, H, W, shape_ok)) return rc;
     if (!pwc_aligned16(workspace)) return PWC_EALIGN;
-    if (((long)H * W + W + 2) * x_cs * 4 >= (long)H2_OOB || (long)H * W * y_cs * 4 >= (long)H2_OOB) return PWC_ERANGE;
+    if (((long)H * W + W + 2) * x_cs * 4 >= (long)PWC_OOB || (long)H * W * y_cs * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     H2Args a;
     a.x = x; a.wp = packed_w; a.bias = bias; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;
     a.N = N; a.H = H; a.W = W; a.Cin_phys = Cin_phys; a.Cout = Cout; a.apply_act = apply_act; a.slope = slope;

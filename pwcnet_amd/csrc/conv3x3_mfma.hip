@@ -23,7 +23,7 @@
 // Pipeline: register-staged prefetch of stage s+1 (global -> VGPR) is issued before the
 // MFMAs of stage s; the VGPRs are written to the other LDS buffer after them; one
 // barrier per stage.
-#include "pwc_common.h"
+#include "conv_fp32_common.h"
 
 struct ConvArgs {
     const float* x;
@@ -43,8 +43,6 @@ struct ConvArgs {
     float* ws;            // split-K: raw partial sums ws[z][pixel][Cout_pad] (no bias/act)
     int xcd_remap;        // consecutive pixel tiles on the same XCD (shared halo rows hit its L2)
 };
-
-__device__ __forceinline__ int swz4(int row) { return (4 - ((row >> 2) & 3)) & 3; }
 
 // ABL: ablation switch for scripts/exp_conv_ablate.hip only (0 in every shipped
 // instantiation): 1 = no global loads in the k loop, 2 = no LDS store / barrier,
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const ConvArgs a) {
         a_iy0[i] = ok ? oy * a.stride - a.pad_t : -(1 << 28);
         a_ix0[i] = ox * a.stride - a.pad_l;
         const int g = a_ch >> 2, j = a_ch & 3;
-        a_lds[i] = ((g * BM + row) * 16) + ((j ^ swz4(row)) << 2);
+        a_lds[i] = ((g * BM + row) * 16) + ((j ^ pwc_swz4(row)) << 2);
     }
     // ---- per-thread B-load bookkeeping
     int b_src[B_LD], b_lds[B_LD];
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const ConvArgs a) {
 
     const int fr = lane & 15;            // fragment row (cout for W, pixel for X)
     const int fq = lane >> 4;            // k-slot
-    const int f_off = fr * 16 + ((fq ^ swz4(fr)) << 2);
+    const int f_off = fr * 16 + ((fq ^ pwc_swz4(fr)) << 2);
 
     int tap = tap0, cc = 0;
     load_stage(tap0, 0);
@@ -220,12 +218,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const ConvArgs a) {
             const int pix = m0 + (wm * WM + m) * 16 + fr;
             if (pix >= a.m_end) continue;
             f32x4 v = acc[n][m] + b4;
-            if (a.apply_act) {
-                v[0] = pwc_lrelu(v[0], a.slope);
-                v[1] = pwc_lrelu(v[1], a.slope);
-                v[2] = pwc_lrelu(v[2], a.slope);
-                v[3] = pwc_lrelu(v[3], a.slope);
-            }
+            if (a.apply_act) v = pwc_lrelu4(v, a.slope);
             float* dst = a.y + (size_t)pix * a.y_cs + co;
             if (a.y_vec4) {
                 *reinterpret_cast<f32x4*>(dst) = v;
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv3x3_mfma_glds_kernel(const
         const int rem = mm - n_img * HoWo;
         const int oy = rem / a.Wo;
         const int ox = rem - oy * a.Wo;
-        const int j = lslot ^ swz4(row);
+        const int j = lslot ^ pwc_swz4(row);
         a_base[i] = a.x + (size_t)n_img * a.H * a.W * a.x_cs + g * 16 + j * 4;
         a_iy0[i] = ok ? oy * a.stride - a.pad_t : -(1 << 28);
         a_ix0[i] = ox * a.stride - a.pad_l;
@@ -339,7 +332,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv3x3_mfma_glds_kernel(const
         for (int m = 0; m < WM; ++m) acc[n][m] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int fr = lane & 15, fq = lane >> 4;
-    const int f_off = fr * 16 + ((fq ^ swz4(fr)) << 2);
+    const int f_off = fr * 16 + ((fq ^ pwc_swz4(fr)) << 2);
 
     int tap = tap0, cc = 0;
     issue_stage(tap0, 0, 0);
@@ -399,12 +392,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv3x3_mfma_glds_kernel(const
             const int pix = m0 + (wm * WM + m) * 16 + fr;
             if (pix >= a.m_end) continue;
             f32x4 v = acc[n][m] + b4;
-            if (a.apply_act) {
-                v[0] = pwc_lrelu(v[0], a.slope);
-                v[1] = pwc_lrelu(v[1], a.slope);
-                v[2] = pwc_lrelu(v[2], a.slope);
-                v[3] = pwc_lrelu(v[3], a.slope);
-            }
+            if (a.apply_act) v = pwc_lrelu4(v, a.slope);
             float* dst = a.y + (size_t)pix * a.y_cs + co;
             if (a.y_vec4) {
                 *reinterpret_cast<f32x4*>(dst) = v;
@@ -488,7 +476,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const HaloArgs a) {
             const int pr = rb * 16 + (lane >> 2);
             if (pr < PR) {
                 const int py = pr / PW, px = pr - py * PW;
-                const int j = (lane & 3) ^ swz4(pr);          // source chunk for this LDS slot
+                const int j = (lane & 3) ^ pwc_swz4(pr);          // source chunk for this LDS slot
                 v = (py << 16) | (px << 8) | (g * 16 + j * 4);
             }
         }
@@ -546,12 +534,12 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const HaloArgs a) {
 #pragma unroll
                 for (int n = 0; n < NT; ++n)
                     wf[n] = *reinterpret_cast<const f32x4*>(wl + ((tap * KG + g) * COUT + n * 16 + fr) * 16 +
-                                                            ((fq ^ swz4(fr)) << 2));
+                                                            ((fq ^ pwc_swz4(fr)) << 2));
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     const int pt = wave * MT + m;               // pixel tile: row pt/2, columns 16*(pt&1)..
                     const int pr = ((pt >> 1) + ty) * PW + (pt & 1) * 16 + fr + tx;
-                    xf[m] = *reinterpret_cast<const f32x4*>(pb + (g * PRP + pr) * 16 + ((fq ^ swz4(pr)) << 2));
+                    xf[m] = *reinterpret_cast<const f32x4*>(pb + (g * PRP + pr) * 16 + ((fq ^ pwc_swz4(pr)) << 2));
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
@@ -576,10 +564,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const HaloArgs a) {
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
                     f32x4 v = acc[n][m] + b4[n];
-                    if (a.apply_act) {
-                        v[0] = pwc_lrelu(v[0], a.slope); v[1] = pwc_lrelu(v[1], a.slope);
-                        v[2] = pwc_lrelu(v[2], a.slope); v[3] = pwc_lrelu(v[3], a.slope);
-                    }
+                    if (a.apply_act) v = pwc_lrelu4(v, a.slope);
                     if (a.y_vec4) *reinterpret_cast<f32x4*>(dst + n * 16) = v;
                     else { dst[n * 16] = v[0]; dst[n * 16 + 1] = v[1]; dst[n * 16 + 2] = v[2]; dst[n * 16 + 3] = v[3]; }
                 }
@@ -595,11 +580,7 @@ static int launch_halo(const HaloArgs& a0, hipStream_t s) {
     constexpr int KG = CIN / 16, PW = 34, PH = TH + 2;
     constexpr int PRP = (PH * PW + 15) & ~15;
     const size_t lds = ((size_t)9 * CIN * COUT + (size_t)NB * KG * PRP * 16) * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<CIN, COUT, TH, NB>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&conv3x3_halo_kernel<CIN, COUT, TH, NB>>((int)lds);
     a.tiles_x = (a.W + 31) / 32;
     a.tiles_y = (a.H + TH - 1) / TH;
     const long ntiles = (long)a.tiles_x * a.tiles_y * a.N;
@@ -612,56 +593,12 @@ static int launch_halo(const HaloArgs& a0, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- weight packing
-// packed[tap][c16][cout_pad][16]: element (j*4+e) of row `co` holds
-// w_hwio[tap][cin_map[c16*16 + ((j ^ swz4(co))*4 + e)]][co]   (0 for padding)
-// i.e. the 16-byte chunk index is pre-swizzled so the LDS image is a linear copy.
-__global__ void conv3x3_pack_kernel(const float* __restrict__ w, const int32_t* __restrict__ cin_map,
-                                    int Cin, int Cin_phys, int Cout, int Cout_pad, float* __restrict__ packed) {
-    const size_t total = (size_t)9 * Cin_phys * Cout_pad;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (size_t)gridDim.x * blockDim.x) {
-        const int e16 = (int)(idx & 15);
-        size_t r = idx >> 4;
-        const int co = (int)(r % Cout_pad);
-        r /= Cout_pad;
-        const int c16 = (int)(r % (Cin_phys >> 4));
-        const int tap = (int)(r / (Cin_phys >> 4));
-        const int jpos = e16 >> 2, e = e16 & 3;
-        const int j = jpos ^ swz4(co);
-        const int cphys = c16 * 16 + j * 4 + e;
-        int clog = cin_map ? cin_map[cphys] : (cphys < Cin ? cphys : -1);
-        float v = 0.f;
-        if (clog >= 0 && clog < Cin && co < Cout) v = w[((size_t)tap * Cin + clog) * Cout + co];
-        packed[idx] = v;
+// packed[tap][c16][cout_pad][16] (conv_fp32_pack_kernel): the taps of w_hwio as they are
+struct ConvTapValue {
+    static __device__ __forceinline__ float at(const float* __restrict__ w, int tap, int clog, int co, int Cin, int Cout) {
+        return w[((size_t)tap * Cin + clog) * Cout + co];
     }
-}
-
-// ---------------------------------------------------------------- split-K reduce
-// y[pix][co] = act(bias[co] + sum_z ws[z][pix][co]); z summed in a fixed order, so the
-// result is deterministic.
-__global__ __launch_bounds__(256) void conv3x3_splitk_reduce_kernel(const float* __restrict__ ws,
-                                                                    const float* __restrict__ bias, float* y,
-                                                                    int y_cs, int y_vec4, int M, int Cout,
-                                                                    int Cout_pad, int nsplit, int apply_act,
-                                                                    float slope) {
-    const int c4n = Cout >> 2;
-    const long total = (long)M * c4n;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % c4n);
-        const long pix = idx / c4n;
-        f32x4 v = *reinterpret_cast<const f32x4*>(bias + c4 * 4);
-        for (int z = 0; z < nsplit; ++z)
-            v += *reinterpret_cast<const f32x4*>(ws + ((size_t)z * M + pix) * Cout_pad + c4 * 4);
-        if (apply_act) {
-            v[0] = pwc_lrelu(v[0], slope); v[1] = pwc_lrelu(v[1], slope);
-            v[2] = pwc_lrelu(v[2], slope); v[3] = pwc_lrelu(v[3], slope);
-        }
-        float* dst = y + (size_t)pix * y_cs + c4 * 4;
-        if (y_vec4) *reinterpret_cast<f32x4*>(dst) = v;
-        else { dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3]; }
-    }
-}
+};
 
 // ---------------------------------------------------------------- host side
 typedef void (*conv_kernel_t)(const ConvArgs);
@@ -772,23 +709,11 @@ extern "C" size_t pwc_conv3x3_workspace_floats(int M, int Cout) {
     return (size_t)9 * M * ((Cout + 15) & ~15);
 }
 
-extern "C" size_t pwc_conv3x3_packed_floats(int Cin_phys, int Cout) {
-    if (Cin_phys <= 0 || Cout <= 0) return 0;
-    const int Cout_pad = (Cout + 15) & ~15;
-    return (size_t)9 * Cin_phys * Cout_pad;
-}
+extern "C" size_t pwc_conv3x3_packed_floats(int Cin_phys, int Cout) { return conv_fp32_packed_floats(9, Cin_phys, Cout); }
 
 extern "C" int pwc_conv3x3_pack_f32(const float* w_hwio, const int32_t* cin_map, int Cin, int Cin_phys,
                                     int Cout, float* packed, pwc_stream_t stream) {
-    if (!w_hwio || !packed || Cin <= 0 || Cout <= 0 || Cin_phys < Cin) return PWC_EINVAL;
-    if (Cin_phys % 16) return PWC_EALIGN;
-    const int Cout_pad = (Cout + 15) & ~15;
-    const size_t total = (size_t)9 * Cin_phys * Cout_pad;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv3x3_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map,
-                       Cin, Cin_phys, Cout, Cout_pad, packed);
-    return pwc_launch_status();
+    return conv_fp32_pack<ConvTapValue>(9, w_hwio, cin_map, Cin, Cin_phys, Cout, packed, stream);
 }
 
 static int launch_tile(const ConvArgs& base, int tile, int m_begin, int m_end, int nsplit, hipStream_t s) {
@@ -810,12 +735,8 @@ extern "C" int pwc_conv3x3_f32(const float* x, int x_cs, const float* packed, co
                                int y_cs, int N, int H, int W, int Cin_phys, int Cout, int stride,
                                int dilation, int apply_act, float slope, int tile, int split,
                                float* workspace, size_t workspace_floats, pwc_stream_t stream) {
-    if (!x || !packed || !bias || !y) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0) return PWC_EINVAL;
-    if (stride < 1 || stride > 2 || dilation < 1) return PWC_EINVAL;
-    if (Cin_phys % 16 || Cout % 16) return PWC_EUNSUPPORTED;
-    if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(packed) || !pwc_aligned16(bias)) return PWC_EALIGN;
+    if (stride < 1 || stride > 2) return PWC_EINVAL;            // (in front of the channel multiples' PWC_EUNSUPPORTED)
+    if (const int rc = conv_fp32_io_check(x, x_cs, packed, bias, y, y_cs, N, H, W, Cin_phys, Cout, dilation, false)) return rc;
     if (split != 0 && split != 1 && split != 3 && split != 9) return PWC_EINVAL;
     ConvArgs a;
     a.x = x; a.wp = packed; a.bias = bias; a.y = y;
@@ -830,7 +751,7 @@ extern "C" int pwc_conv3x3_f32(const float* x, int x_cs, const float* packed, co
     // within-image offsets and the pixel count are 32-bit in the kernel
     if (M >= (1L << 31) || (long)H * W * x_cs >= (1L << 31)) return PWC_ERANGE;
     a.M = (int)M;
-    a.y_vec4 = ((y_cs & 3) == 0 && pwc_aligned16(y)) ? 1 : 0;
+    a.y_vec4 = conv_fp32_y_vec4(y, y_cs) ? 1 : 0;
     a.ws = workspace;
     a.xcd_remap = 1;
     hipStream_t s = (hipStream_t)stream;
@@ -859,11 +780,7 @@ extern "C" int pwc_conv3x3_f32(const float* x, int x_cs, const float* packed, co
         if (!ws_ok || workspace_floats < (size_t)p.nsplit * a.M * a.Cout_pad) return PWC_EINVAL;
         int rc = launch_tile(a, p.tile, 0, a.M, p.nsplit, s);
         if (rc) return rc;
-        const long total = (long)a.M * (Cout >> 2);
-        long blocks = (total + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(conv3x3_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, workspace, bias,
-                           y, y_cs, a.y_vec4, a.M, Cout, a.Cout_pad, p.nsplit, apply_act, slope);
+        conv_fp32_split_reduce(workspace, bias, y, y_cs, a.M, Cout, p.nsplit, apply_act, slope, 2048, s);
         return pwc_launch_status();
     }
     int rc = launch_tile(a, p.tile, 0, p.m_main, 1, s);

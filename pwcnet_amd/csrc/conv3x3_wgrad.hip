@@ -235,7 +235,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_lds_kernel(const WgLdsAr
     }
     const int xslot = ((xquad / QPP) * Geo::XPIX + xpp0) * QPP + (xquad % QPP);      // 16-byte units; + (512 / QX) * QPP per piece
     const int dslot = Geo::XS / 4 + ((dquad / QPP) * Geo::DPIX + dpp0) * QPP + (dquad % QPP);
-    constexpr unsigned WL_OOB = 0x7FFF0000u;
     f32x4 stx[NX], std_[ND];
     const bool xch_ok = cit * CPP * NCI + xquad * 4 < a.Cin_phys, dch_ok = cot * CPP * NCO + dquad * 4 < a.Cout;
     auto issue = [&](int tile) {
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_lds_kernel(const WgLdsAr
         for (int j = 0; j < NX; ++j) {
             const int iy = ry + d * (sy0 + pc_py[j] - 1), ix = rx + d * (sx0 + pc_px[j] - 1);
             const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W && xch_ok;
-            const unsigned off = ok ? (unsigned)(((iy * a.W + ix) * a.x_cs + xquad * 4) * 4) : WL_OOB;
+            const unsigned off = ok ? (unsigned)(((iy * a.W + ix) * a.x_cs + xquad * 4) * 4) : PWC_OOB;
             stx[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)off, 0, 0));
         }
 #pragma unroll
@@ -262,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_lds_kernel(const WgLdsAr
             const int pix = dpp0 + (512 / QY) * j;
             const int oy = ry + d * (sy0 + (pix >> a.tw_log)), ox = rx + d * (sx0 + (pix & (a.tw - 1)));
             const bool ok = pix < Geo::P && oy < a.H && ox < a.W && dch_ok;
-            const unsigned off = ok ? (unsigned)(((oy * a.W + ox) * a.dy_cs + dquad * 4) * 4) : WL_OOB;
+            const unsigned off = ok ? (unsigned)(((oy * a.W + ox) * a.dy_cs + dquad * 4) * 4) : PWC_OOB;
             std_[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dr, (int)off, 0, 0));
         }
     };
@@ -422,11 +421,7 @@ static bool wgrad_lds_plan(int N, int H, int W, int Cin_phys, int Cout, int stri
 template <int NCI, int NCO, int G, int V>
 static void wgrad_lds_launch(const WgLdsArgs& l, hipStream_t stream) {
     typedef WgLdsGeom<NCI, NCO, G, V> Geo;
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_lds_kernel<NCI, NCO, G, V>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS_BYTES);
-    }
+    pwc_allow_dynamic_lds<&conv3x3_wgrad_lds_kernel<NCI, NCO, G, V>>(Geo::LDS_BYTES);
     hipLaunchKernelGGL((conv3x3_wgrad_lds_kernel<NCI, NCO, G, V>), dim3((unsigned)((l.ksplit + 7) / 8 * 8 * l.ci_tiles * l.co_tiles)), dim3(512),
                        Geo::LDS_BYTES, stream, l);
 }

@@ -29,7 +29,7 @@
 //   refetched as soon as they have been read (PIPE); 2 workgroups per CU.
 //   Other tile shapes of the same kernel (WinoGeom): two short sub-lattice images per
 //   workgroup, 4 x 64-pixel blocks; 16 instead of 32 output channels (NT = 1).
-#include "pwc_common.h"
+#include "conv_fp32_common.h"
 #include <cstdlib>
 
 #ifndef WINO_BN32_MIN_WG
@@ -54,7 +54,6 @@ struct WinoArgs {
     long slab;                   //      raw partial outputs (no bias, no activation) to y + z * slab (floats), see wino_split
 };
 
-__device__ __forceinline__ int wswz(int row) { return (4 - ((row >> 2) & 3)) & 3; }   // weight rows
 // Patch image in LDS: pixel (py, px) of the 18 x 18 patch sits in 64-byte row
 //   py * 20 + (px & 1) * 10 + (px >> 1)
 // (even pixel columns first, then the odd ones; rows 9 and 19 of every 20 are unused), its
@@ -65,7 +64,6 @@ __device__ __forceinline__ int wswz(int row) { return (4 - ((row >> 2) & 3)) & 3
 // 16 patch reads of a stage: SQ_LDS_BANK_CONFLICT = 40 % of SQ_LDS_IDX_ACTIVE.)
 __device__ __forceinline__ int wpswz(int row) { return (row >> 1) & 2; }
 
-constexpr unsigned WN_OOB = 0x7FFF0000u;  // byte offset beyond every buffer: loads return 0, stores are dropped
 // NT = 16-cout MFMA tiles per workgroup (2: 32 output channels, 1: 16).
 // GEO = shape of the workgroup's 64 Winograd tiles:
 //   0  8 x 8 tiles = 16 x 16 pixels (patch 18 x 18);
@@ -91,30 +89,17 @@ template <int NT, int GEO = 0> struct WinoGeom {
 
 template <bool B> struct WinoBool { static constexpr bool value = B; };
 
-// -1.0f in an SGPR the optimiser cannot see through: p - q is written fma(q, -1, p) so that it
-// can become one v_pk_fma_f32 per two floats (a vector fsub is scalarised by the backend: there
-// is v_pk_add_f32 but no packed subtract).  The VALU instructions of the transforms share the
-// issue port with the MFMAs and their time ADDS to the MFMA time (measured: removing the 128
-// scalar transform instructions of a stage saved 10 % of the kernel).
-// (Inline-asm v_pk_add_f32 with neg modifiers was tried: fully packed, same speed, but every
-// VALU write an MFMA reads next needs 2 wait states that the hazard recogniser only inserts
-// for instructions it can see -- results were wrong until the s_nop moved into the asm.)
-__device__ __forceinline__ float wino_minus_one() {
-    float m;
-    asm volatile("s_mov_b32 %0, 0xbf800000" : "=s"(m));
-    return m;
-}
-
 // ABL (scripts/exp_wino.hip only, 0 in the library): 1 = no patch DMA, 2 = no weight DMA, 4 = no MFMA,
 // 8 = s_setprio(1) around the MFMA clusters, 16 = k innermost in the MFMA order (both measured: no gain),
 // 64 = no input transform
 // PIPE = 1: the stage is fetched in three parts (patch, weights of positions 0-7, of 8-15), each
 // re-fetched for the next stage as soon as its LDS region is free, one barrier per part.
-// PERSIST = 1 (needs PIPE; scripts/exp_wino.hip only): the grid is 2 workgroups per CU and each walks
-// tiles blockIdx.x, + gridDim.x, ...; the first stage of the next tile is requested before the
-// current tile's output transform and stores, so its fetch latency and the per-tile setup hide behind
-// them.  Correct, but the 7 offsets of the next tile live across the epilogue push the kernel over
-// 256 VGPRs (84 B of scratch per lane) and it measures 289 us against 255 us: not used by the library.
+// PERSIST = 1 (needs PIPE): the grid is 2 workgroups per CU and each walks tiles blockIdx.x, + gridDim.x,
+// ...; the first stage of the next tile is requested before the current tile's output transform and
+// stores, so its fetch latency and the per-tile setup hide behind them.  With 32 couts (NT = 2) the 7
+// offsets of the next tile live across the epilogue push the kernel over 256 VGPRs (84 B of scratch per
+// lane) and it measures 289 us against 255 us: wino_run launches it for the 16-cout layers with
+// Cin_phys <= 32 and more than 1024 tiles only (NT = 1, GEO 0 and 2: 64 accumulator registers, no spill).
 // barriers of the stage pipeline: LDS only (pwc_lds_barrier) -- WINO_DRAIN_BARRIERS=1 restores the round-1/2 behaviour
 // (__syncthreads(), which drains every DMA piece in flight) for A/B measurements
 #ifndef WINO_DRAIN_BARRIERS
@@ -137,9 +122,8 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    const float m1 = wino_minus_one();
-    const f32x4 M1 = {m1, m1, m1, m1};
-#define WSUB(p, q) __builtin_elementwise_fma((q), M1, (p))    /* p - q */
+    const f32x4 M1 = pwc_minus_one4();
+#define WSUB(p, q) pwc_sub4((p), (q), M1)
 
     const int d = a.dil;
     const int Cout_pad = (a.Cout + 15) & ~15;
@@ -157,7 +141,7 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
     // bookkeeping.  Both operands are fetched with buffer_load_dwordx4 ... lds: a per-lane BYTE
     // offset that is fixed over the channel loop (VGPR), the stage advance in the scalar offset
     // (SGPR) -- no vector instruction per fetch -- and the buffer range check gives the zeros of
-    // the SAME padding: out-of-image lanes carry the offset WN_OOB.
+    // the SAME padding: out-of-image lanes carry the offset PWC_OOB.
     int n, n0, y0, x0, ry_g[2], rx_g[2];
     int zsplit = 0, c_begin = 0, c_end = nc16;     // this workgroup's share of the channel stages
     __amdgpu_buffer_rsrc_t xrsrc;
@@ -200,13 +184,13 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
             const int y = ry_g[g] + d * (y0 - 1 + pyl), x = rx_g[g] + d * (x0 - 1 + px);
             const int ch = (lane & 3) ^ wpswz(pr);                     // source chunk for this LDS slot
             const bool ok = py < WN_PH && col < WN_PW / 2 && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-            p_voff[i] = ok ? (unsigned)(((y * a.W + x) * a.x_cs + ch * 4) * 4) : WN_OOB;
+            p_voff[i] = ok ? (unsigned)(((y * a.W + x) * a.x_cs + ch * 4) * 4) : PWC_OOB;
         }
         // weight blocks: block wave + 4*i holds rows (xi, cout) = ((wave + 4*i) * 16 + lane/4); 4 blocks
         // = 64 rows = 64 / WN_BN positions, so one per-lane offset plus a uniform stride covers all i
         const int ur = wave * 16 + (lane >> 2);
         const int xi = ur / WN_BN, co = ur - xi * WN_BN;
-        u_voff = (n0 + co < Cout_pad) ? (unsigned)((((xi * nc16) * Cout_pad + n0 + co) * 16 + (lane & 3) * 4) * 4) : WN_OOB;
+        u_voff = (n0 + co < Cout_pad) ? (unsigned)((((xi * nc16) * Cout_pad + n0 + co) * 16 + (lane & 3) * 4) * 4) : PWC_OOB;
     };
     int tile = blockIdx.x;
     setup(tile);
@@ -226,8 +210,6 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(ursrc, (lptr_t)(smem + (WN_NBP + wave + 4 * i) * 256), 16,
                                                          (int)u_voff, us + i * u_step, 0, 0);
     };
-    // s_waitcnt vmcnt(n) only (gfx9 encoding: vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8])
-#define WAIT_VM(n) __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | (7 << 4) | (15 << 8))
 
     // ---- this lane's tile and its 16 patch read offsets (floats, swizzled for k-slot fq)
     // tile (tr, tc) of this lane: 8 x 8 tiles (wave = 2 tile rows) or, WIDE, 2 x 32 tiles (wave = half a row)
@@ -241,7 +223,7 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
             const int row = prow * WN_PS + (j & 1) * (WN_PS / 2) + tc + (j >> 1);
             poff[i][j] = row * 16 + ((fq ^ wpswz(row)) << 2);
         }
-    const int u_off = WN_PRP * 16 + fr * 16 + ((fq ^ wswz(fr)) << 2);   // A-fragment row fr of a 16-row tile
+    const int u_off = WN_PRP * 16 + fr * 16 + ((fq ^ pwc_swz4(fr)) << 2);   // A-fragment row fr of a 16-row tile
 
     f32x4 acc[16][NT];
     // one 16-channel stage; FIRST: the accumulators start from the MFMA's zero C operand
@@ -249,13 +231,13 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
         constexpr bool FIRST = decltype(first)::value;
         const bool has_next = c16 + 1 < c_end;
         if (PIPE) {
-            WAIT_VM(UH);                             // patch(c) landed (weights A(c) may be in flight)
+            PWC_WAIT_VM(UH);                             // patch(c) landed (weights A(c) may be in flight)
             WINO_SYNC();                         // ... for every wave; positions 8-15 of c-1 fully read
             issue_u(c16, 1);
         } else {
             WINO_SYNC();                         // previous stage fully read
             issue_patch(c16); issue_u(c16, 0); issue_u(c16, 1);
-            WAIT_VM(0);
+            PWC_WAIT_VM(0);
             WINO_SYNC();
         }
 
@@ -311,7 +293,7 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
             }
         };
         if (PIPE) {
-            WAIT_VM(UH);                             // weights A(c) landed (B(c) may be in flight)
+            PWC_WAIT_VM(UH);                             // weights A(c) landed (B(c) may be in flight)
             WINO_SYNC();                         // ... for every wave; patch(c) fully read
             if (has_next) issue_patch(c16 + 1);
         }
@@ -319,7 +301,7 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
         mfma_half(0);
         if (ABL & 8) __builtin_amdgcn_s_setprio(0);
         if (PIPE) {
-            if (has_next) WAIT_VM(PPW); else WAIT_VM(0);   // weights B(c) landed (patch(c+1) may be in flight)
+            if (has_next) PWC_WAIT_VM(PPW); else PWC_WAIT_VM(0);   // weights B(c) landed (patch(c+1) may be in flight)
             WINO_SYNC();                         // ... for every wave; positions 0-7 of c fully read
             if (has_next) issue_u(c16 + 1, 0);
         }
@@ -358,7 +340,7 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int py = py0 + i * d, px = px0 + j * d;
-            y_voff[i][j] = (py < a.H && px < a.W) ? (unsigned)(((py * a.W + px) * a.y_cs + on0 + fq * 4) * 4) : WN_OOB;
+            y_voff[i][j] = (py < a.H && px < a.W) ? (unsigned)(((py * a.W + px) * a.y_cs + on0 + fq * 4) * 4) : PWC_OOB;
         }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -378,11 +360,7 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
             for (int j = 0; j < 2; ++j) {
                 f32x4 yv = (j == 0) ? s[i][0] + s[i][1] + s[i][2] : WSUB(WSUB(s[i][1], s[i][2]), s[i][3]);
                 yv += b4;
-                if (a.apply_act) {               // tf.nn.leaky_relu = max(v, slope * v)
-                    const f32x4 sv = yv * a.slope;
-                    yv[0] = fmaxf(yv[0], sv[0]); yv[1] = fmaxf(yv[1], sv[1]);
-                    yv[2] = fmaxf(yv[2], sv[2]); yv[3] = fmaxf(yv[3], sv[3]);
-                }
+                if (a.apply_act) yv = pwc_lrelu4_packed(yv, a.slope);
                 if (a.y_vec4) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, yv), yrsrc, (int)y_voff[i][j], nt * 64, 0);
                 } else {
@@ -399,57 +377,29 @@ __global__ __launch_bounds__(256, NT >= 4 ? 1 : 2) void conv3x3_wino_kernel(cons
     tile = next;
     }   // tiles
 #undef WSUB
-#undef WAIT_VM
 }
 
 // ---------------------------------------------------------------- weight transform + packing
 // packed[xi][c16][cout_pad][16]: U_xi = (G g G^T)[a][b], xi = 4a + b, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1],
-// chunk-swizzled like the direct kernel's image; cin_map as in pwc_conv3x3_pack_f32.
-__global__ void conv3x3_wino_pack_kernel(const float* __restrict__ w, const int32_t* __restrict__ cin_map, int Cin,
-                                         int Cin_phys, int Cout, int Cout_pad, float* __restrict__ packed) {
-    const size_t total = (size_t)16 * Cin_phys * Cout_pad;
-    const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (size_t)gridDim.x * blockDim.x) {
-        const int e16 = (int)(idx & 15);
-        size_t r = idx >> 4;
-        const int co = (int)(r % Cout_pad);
-        r /= Cout_pad;
-        const int c16 = (int)(r % (Cin_phys >> 4));
-        const int xi = (int)(r / (Cin_phys >> 4));
-        const int jpos = e16 >> 2, e = e16 & 3;
-        const int j = jpos ^ wswz(co);
-        const int cphys = c16 * 16 + j * 4 + e;
-        const int clog = cin_map ? cin_map[cphys] : (cphys < Cin ? cphys : -1);
+// in the layout of conv_fp32_pack_kernel.
+struct WinoValue {
+    static __device__ __forceinline__ float at(const float* __restrict__ w, int xi, int clog, int co, int Cin, int Cout) {
+        const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
+        const int ua = xi >> 2, ub = xi & 3;
         float u = 0.f;
-        if (clog >= 0 && clog < Cin && co < Cout) {
-            const int ua = xi >> 2, ub = xi & 3;
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < 3; ++p)
 #pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    u += G[ua][p] * G[ub][q] * w[((size_t)(p * 3 + q) * Cin + clog) * Cout + co];
-        }
-        packed[idx] = u;
+            for (int q = 0; q < 3; ++q) u += G[ua][p] * G[ub][q] * w[((size_t)(p * 3 + q) * Cin + clog) * Cout + co];
+        return u;
     }
-}
+};
 
-extern "C" size_t pwc_conv3x3_wino_packed_floats(int Cin_phys, int Cout) {
-    if (Cin_phys <= 0 || Cout <= 0) return 0;
-    return (size_t)16 * Cin_phys * ((Cout + 15) & ~15);
-}
+extern "C" size_t pwc_conv3x3_wino_packed_floats(int Cin_phys, int Cout) { return conv_fp32_packed_floats(16, Cin_phys, Cout); }
 
 extern "C" int pwc_conv3x3_wino_pack_f32(const float* w_hwio, const int32_t* cin_map, int Cin, int Cin_phys,
                                          int Cout, float* packed, pwc_stream_t stream) {
-    if (!w_hwio || !packed || Cin <= 0 || Cout <= 0 || Cin_phys < Cin) return PWC_EINVAL;
-    if (Cin_phys % 16) return PWC_EALIGN;
-    const int Cout_pad = (Cout + 15) & ~15;
-    const size_t total = (size_t)16 * Cin_phys * Cout_pad;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv3x3_wino_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map,
-                       Cin, Cin_phys, Cout, Cout_pad, packed);
-    return pwc_launch_status();
+    return conv_fp32_pack<WinoValue>(16, w_hwio, cin_map, Cin, Cin_phys, Cout, packed, stream);
 }
 
 // output channels per workgroup: 32, or 16 when 32 would leave most of the 512 workgroup slots
@@ -490,28 +440,6 @@ extern "C" long pwc_conv3x3_wino_workgroups(int N, int H, int W, int Cout, int d
     long pix_blocks;
     wino_grid(N, H, W, dilation, wino_geo(H, W, dilation), &tx, &ty, &pix_blocks);
     return pix_blocks * (Cout / wino_bn(pix_blocks, Cout));
-}
-
-// sum of the channel-split partial outputs (fixed order) + bias + leaky-relu -> y
-__global__ __launch_bounds__(256) void conv3x3_wino_split_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ bias,
-                                                                        float* __restrict__ y, int y_cs, int y_vec4, long M,
-                                                                        int Cout, int Cout_pad, int nsplit, int apply_act,
-                                                                        float slope) {
-    const int c4n = Cout >> 2;
-    const long total = M * c4n;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int c4 = (int)(idx % c4n);
-        const long pix = idx / c4n;
-        f32x4 v = *reinterpret_cast<const f32x4*>(bias + c4 * 4);
-        for (int z = 0; z < nsplit; ++z) v += *reinterpret_cast<const f32x4*>(ws + ((size_t)z * M + pix) * Cout_pad + c4 * 4);
-        if (apply_act) {
-            v[0] = pwc_lrelu(v[0], slope); v[1] = pwc_lrelu(v[1], slope);
-            v[2] = pwc_lrelu(v[2], slope); v[3] = pwc_lrelu(v[3], slope);
-        }
-        float* dst = y + (size_t)pix * y_cs + c4 * 4;
-        if (y_vec4) *reinterpret_cast<f32x4*>(dst) = v;
-        else { dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3]; }
-    }
 }
 
 static int wino_run(const float* x, int x_cs, const float* packed_u, const float* bias, float* y, int y_cs, int N, int H,
@@ -569,17 +497,13 @@ static int wino_run(const float* x, int x_cs, const float* packed_u, const float
                     int W, int Cin_phys, int Cout, int dilation, int apply_act, float slope, int csplit, float* workspace,
                     size_t workspace_floats, pwc_stream_t stream) {
     (void)workspace_floats;
-    if (!x || !packed_u || !bias || !y) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0 || dilation < 1) return PWC_EINVAL;
-    if (Cin_phys % 16 || Cout % 16) return PWC_EUNSUPPORTED;
-    if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(packed_u) || !pwc_aligned16(bias)) return PWC_EALIGN;
+    if (const int rc = conv_fp32_io_check(x, x_cs, packed_u, bias, y, y_cs, N, H, W, Cin_phys, Cout, dilation, false)) return rc;
     // per-image slabs are addressed with 32-bit byte offsets through buffer resources
-    if ((long)H * W * x_cs * 4 >= (long)WN_OOB || (long)H * W * y_cs * 4 >= (long)WN_OOB) return PWC_ERANGE;
-    if ((long)16 * Cin_phys * ((Cout + 15) & ~15) * 4 >= (long)WN_OOB) return PWC_ERANGE;
+    if ((long)H * W * x_cs * 4 >= (long)PWC_OOB || (long)H * W * y_cs * 4 >= (long)PWC_OOB) return PWC_ERANGE;
+    if ((long)16 * Cin_phys * ((Cout + 15) & ~15) * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     const int Cout_pad = (Cout + 15) & ~15;
     const long M = (long)N * H * W;
-    if (csplit > 1 && (long)H * W * Cout_pad * 4 >= (long)WN_OOB) return PWC_ERANGE;
+    if (csplit > 1 && (long)H * W * Cout_pad * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     WinoArgs a;
     a.x = x; a.up = packed_u; a.bias = bias; a.x_cs = x_cs;
     a.N = N; a.H = H; a.W = W; a.Cin_phys = Cin_phys; a.Cout = Cout;
@@ -596,7 +520,7 @@ static int wino_run(const float* x, int x_cs, const float* packed_u, const float
     wino_grid(N, H, W, dilation, geo, &a.tiles_x, &a.tiles_y, &pix_blocks);
     const int bn = wino_bn(pix_blocks, Cout);
     a.ncb = Cout / bn;
-    a.y_vec4 = csplit > 1 ? 1 : (((y_cs & 3) == 0 && pwc_aligned16(y)) ? 1 : 0);
+    a.y_vec4 = (csplit > 1 || conv_fp32_y_vec4(y, y_cs)) ? 1 : 0;
     const long nblk = pix_blocks * a.ncb * csplit;
     if (nblk >= (1L << 31)) return PWC_ERANGE;
     a.ntiles = (int)nblk;
@@ -605,11 +529,7 @@ static int wino_run(const float* x, int x_cs, const float* packed_u, const float
 #define WINO_LAUNCH_P(NT, GEO, PERS)                                                                        \
     do {                                                                                                    \
         const size_t lds = (size_t)WinoGeom<NT, GEO>::STAGE * sizeof(float);                                \
-        static PwcDevOnce attr_once;                                                                          \
-        if (pwc_first_on_device(&attr_once)) {                                                              \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<0, NT, 1, GEO, PERS>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-        }                                                                                                   \
+        pwc_allow_dynamic_lds<&conv3x3_wino_kernel<0, NT, 1, GEO, PERS>>((int)lds);                         \
         const long grid = (PERS && nblk > 512) ? 512 : nblk;   /* persistent: 2 workgroups per CU walk the tiles */ \
         hipLaunchKernelGGL((conv3x3_wino_kernel<0, NT, 1, GEO, PERS>), dim3((unsigned)grid), dim3(256), lds, \
                            (hipStream_t)stream, a);                                                         \
@@ -634,13 +554,7 @@ static int wino_run(const float* x, int x_cs, const float* packed_u, const float
     else          { if (geo == 1) WINO_LAUNCH(1, 1); else if (geo == 2) WINO_LAUNCH(1, 2); else WINO_LAUNCH(1, 0); }
 #undef WINO_LAUNCH
 #undef WINO_LAUNCH_P
-    if (csplit > 1) {
-        long blocks = (M * (Cout >> 2) + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(conv3x3_wino_split_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)workspace, bias, y, y_cs, ((y_cs & 3) == 0 && pwc_aligned16(y)) ? 1 : 0, M, Cout,
-                           Cout_pad, csplit, apply_act, slope);
-    }
+    if (csplit > 1) conv_fp32_split_reduce(workspace, bias, y, y_cs, M, Cout, csplit, apply_act, slope, 4096, (hipStream_t)stream);
     return pwc_launch_status();
 }
 

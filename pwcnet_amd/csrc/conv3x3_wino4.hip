@@ -37,7 +37,7 @@
 // What bounds it: on gfx950 nothing overlaps an fp32 MFMA on its SIMD; per wave and stage 72 MFMAs carry
 // 180 packed VALU instructions of transform, 54 ds_read_b128 and 20 fetch pieces: a cap of 0.6 on the MFMA fraction.
 #pragma once
-#include "pwc_common.h"
+#include "conv_fp32_common.h"
 #include <type_traits>
 #ifndef WINO_SYNC
 #define WINO_SYNC() pwc_lds_barrier()
@@ -58,7 +58,6 @@ struct Wino4Args {
     int ntiles;
 };
 
-constexpr unsigned W4_OOB = 0x7FFF0000u;
 constexpr int W4_PS = 36;                    // patch records per patch row: 4 quarter rows (px & 3) of 9 (px >> 2)
 constexpr int W4_PH = 18, W4_PW = 34;
 constexpr int W4_NW = 4, W4_T = 64 * W4_NW;
@@ -70,7 +69,6 @@ constexpr int W4_STAGE = (W4_PREC + W4_NBU * 16) * 16;     // floats per LDS sta
 constexpr int W4_XCH = W4_NW * 64 * 36;      // floats of the output exchange (4 waves x 64 lanes x (32 + 4 pad)): 36 864 B
 static_assert(W4_XCH <= W4_STAGE && 2 * W4_STAGE * 4 <= 160 * 1024, "the exchange reuses the stage buffer; two workgroups share a CU");
 
-__device__ __forceinline__ int w4_wswz(int row) { return (4 - ((row >> 2) & 3)) & 3; }   // weight rows (as conv3x3_wino.hip)
 // Patch image: pixel (py, px) of the 18 x 34 patch sits in record py * 36 + (px & 3) * 9 + (px >> 2) -- the 8 tile
 // columns a wave reads at one (i, j) of the 6 x 6 window are then CONSECUTIVE records -- and its 16-byte chunk c at
 // slot c ^ w4_pswz(py): the two tile rows of a wave differ in (py >> 2) & 1, so every ds_read_b128 lane group
@@ -92,10 +90,8 @@ __global__ __launch_bounds__(W4_T, 2) void conv3x3_wino4_kernel(const Wino4Args 
     const int g = wave >> 1, h = wave & 1;          // tile group, position half
     const int fr = lane & 15, fq = lane >> 4;
     const int trl = fr >> 3, tc = fr & 7;           // tile (2g + trl, tc)
-    float m1s;
-    asm volatile("s_mov_b32 %0, 0xbf800000" : "=s"(m1s));   // -1.0f the optimiser cannot see through (see conv3x3_wino.hip)
-    const f32x4 M1 = {m1s, m1s, m1s, m1s};
-#define W4SUB(p, q) __builtin_elementwise_fma((q), M1, (p))    /* p - q, packable */
+    const f32x4 M1 = pwc_minus_one4();
+#define W4SUB(p, q) pwc_sub4((p), (q), M1)
 #define W4FMA(x, c, y) __builtin_elementwise_fma((x), f32x4{c, c, c, c}, (y))   /* x * c + y */
 
     const int d = a.dil;
@@ -132,12 +128,12 @@ __global__ __launch_bounds__(W4_T, 2) void conv3x3_wino4_kernel(const Wino4Args 
         const int yy = ry + d * (y0 - 1 + py), xx = rx + d * (x0 - 1 + px);
         const int ch = (lane & 3) ^ w4_pswz(py);                       // source chunk for this LDS slot
         const bool ok = py < W4_PH && px < W4_PW && (unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W;
-        p_voff[i] = ok ? (unsigned)(((yy * a.W + xx) * a.x_cs + ch * 4) * 4) : W4_OOB;
+        p_voff[i] = ok ? (unsigned)(((yy * a.W + xx) * a.x_cs + ch * 4) * 4) : PWC_OOB;
     }
     // weights, in three parts P of 6 positions per half: wave w fetches positions 18 (w & 1) + 6 P + 3 (w >> 1) + i, i = 0..2
     const int u_xi0 = 18 * (wave & 1) + 3 * (wave >> 1);
     const int u_co = n0 + (lane >> 2);
-    const unsigned u_voff = (u_co < Cout_pad) ? (unsigned)((((u_xi0 * nc16) * Cout_pad + u_co) * 16 + (lane & 3) * 4) * 4) : W4_OOB;
+    const unsigned u_voff = (u_co < Cout_pad) ? (unsigned)((((u_xi0 * nc16) * Cout_pad + u_co) * 16 + (lane & 3) * 4) * 4) : PWC_OOB;
     const int u_step = nc16 * Cout_pad * 64;        // bytes between consecutive positions
     auto issue_patch = [&](int c16) {
 #pragma unroll
@@ -157,21 +153,20 @@ __global__ __launch_bounds__(W4_T, 2) void conv3x3_wino4_kernel(const Wino4Args 
                                                          (int)u_voff, (ABL & 16) ? 0 : us + (6 * part + i) * u_step, 0, 0);
         }
     };
-#define W4_WAIT_VM(n) __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | (7 << 4) | (15 << 8))
 
     // ---- this lane's patch reads: record (4 trow + i) * 36 + (j & 3) * 9 + (j >> 2) + tc, chunk fq ^ pswz(py);
     // pswz flips between window rows i < 4 and i >= 4: two per-lane bases, everything else is an immediate
     const int trow = 2 * g + trl;
     const float* pb_lo = smem + ((4 * trow) * W4_PS + tc) * 16 + ((fq ^ w4_pswz(4 * trow)) << 2);
     const float* pb_hi = smem + ((4 * trow) * W4_PS + tc) * 16 + ((fq ^ w4_pswz(4 * trow + 4)) << 2);
-    const int u_off = W4_PREC * 16 + ((18 * h) * 16 + fr) * 16 + ((fq ^ w4_wswz(fr)) << 2);   // this wave's A-fragment rows
+    const int u_off = W4_PREC * 16 + ((18 * h) * 16 + fr) * 16 + ((fq ^ pwc_swz4(fr)) << 2);   // this wave's A-fragment rows
 
     f32x4 acc[18];
     auto stage = [&](auto first, int c16) {
         constexpr bool FIRST = decltype(first)::value;
         const bool has_next = c16 + 1 < nc16;
         // in flight here (oldest first): patch(c), weight parts 0 and 1 of c
-        W4_WAIT_VM(6);                               // patch(c) landed
+        PWC_WAIT_VM(6);                               // patch(c) landed
         WINO_SYNC();                             // ... for every wave; part 2 of c-1 fully read
         issue_u(c16, 2);
 
@@ -243,15 +238,15 @@ __global__ __launch_bounds__(W4_T, 2) void conv3x3_wino4_kernel(const Wino4Args 
                 }
             }
         };
-        W4_WAIT_VM(6);                               // weight part 0 of c landed (parts 1, 2 may be in flight)
+        PWC_WAIT_VM(6);                               // weight part 0 of c landed (parts 1, 2 may be in flight)
         WINO_SYNC();                             // ... for every wave; patch(c) fully read
         if (has_next) issue_patch(c16 + 1);
         mfma_part(0);
-        if (has_next) W4_WAIT_VM(3 + PPW); else W4_WAIT_VM(3);   // part 1 landed (part 2, patch(c+1) may be in flight)
+        if (has_next) PWC_WAIT_VM(3 + PPW); else PWC_WAIT_VM(3);   // part 1 landed (part 2, patch(c+1) may be in flight)
         WINO_SYNC();                             // ... for every wave; part 0 fully read
         if (has_next) issue_u(c16 + 1, 0);
         mfma_part(1);
-        if (has_next) W4_WAIT_VM(PPW + 3); else W4_WAIT_VM(0);   // part 2 landed (patch(c+1), part 0 of c+1 may be in flight)
+        if (has_next) PWC_WAIT_VM(PPW + 3); else PWC_WAIT_VM(0);   // part 2 landed (patch(c+1), part 0 of c+1 may be in flight)
         WINO_SYNC();                             // ... for every wave; part 1 fully read
         if (has_next) issue_u(c16 + 1, 1);
         mfma_part(2);
@@ -321,13 +316,9 @@ __global__ __launch_bounds__(W4_T, 2) void conv3x3_wino4_kernel(const Wino4Args 
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     f32x4 yv = Yp[2 * HH + i][j] + *reinterpret_cast<const f32x4*>(src + (i * 4 + j) * 4) + b4;
-                    if (a.apply_act) {               // tf.nn.leaky_relu = max(v, slope * v)
-                        const f32x4 sv = yv * a.slope;
-                        yv[0] = fmaxf(yv[0], sv[0]); yv[1] = fmaxf(yv[1], sv[1]);
-                        yv[2] = fmaxf(yv[2], sv[2]); yv[3] = fmaxf(yv[3], sv[3]);
-                    }
+                    if (a.apply_act) yv = pwc_lrelu4_packed(yv, a.slope);
                     const int py = py0 + i * d, px = px0 + j * d;
-                    const unsigned vo = (py < a.H && px < a.W) ? (unsigned)(((py * a.W + px) * a.y_cs + co) * 4) : W4_OOB;
+                    const unsigned vo = (py < a.H && px < a.W) ? (unsigned)(((py * a.W + px) * a.y_cs + co) * 4) : PWC_OOB;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, yv), yrsrc, (int)vo, 0, 0);
                 }
         }
@@ -336,59 +327,31 @@ __global__ __launch_bounds__(W4_T, 2) void conv3x3_wino4_kernel(const Wino4Args 
     else epilogue(std::integral_constant<int, 1>{});
 #undef W4SUB
 #undef W4FMA
-#undef W4_WAIT_VM
 }
 
 // ---------------------------------------------------------------- weight transform + packing
 // packed[xi][c16][cout_pad][16]: U_xi = (G g G^T)[a][b], xi = 6a + b,
 //   G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]   (double, rounded once),
-// chunk-swizzled like conv3x3_wino.hip's image; cin_map as in pwc_conv3x3_pack_f32.
-__global__ void conv3x3_wino4_pack_kernel(const float* __restrict__ w, const int32_t* __restrict__ cin_map, int Cin,
-                                          int Cin_phys, int Cout, int Cout_pad, float* __restrict__ packed) {
-    const size_t total = (size_t)36 * Cin_phys * Cout_pad;
-    const double G[6][3] = {{0.25, 0., 0.}, {-1. / 6, -1. / 6, -1. / 6}, {-1. / 6, 1. / 6, -1. / 6},
-                            {1. / 24, 1. / 12, 1. / 6}, {1. / 24, -1. / 12, 1. / 6}, {0., 0., 1.}};
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (size_t)gridDim.x * blockDim.x) {
-        const int e16 = (int)(idx & 15);
-        size_t r = idx >> 4;
-        const int co = (int)(r % Cout_pad);
-        r /= Cout_pad;
-        const int c16 = (int)(r % (Cin_phys >> 4));
-        const int xi = (int)(r / (Cin_phys >> 4));
-        const int jpos = e16 >> 2, e = e16 & 3;
-        const int j = jpos ^ w4_wswz(co);
-        const int cphys = c16 * 16 + j * 4 + e;
-        const int clog = cin_map ? cin_map[cphys] : (cphys < Cin ? cphys : -1);
+// in the layout of conv_fp32_pack_kernel.
+struct Wino4Value {
+    static __device__ __forceinline__ float at(const float* __restrict__ w, int xi, int clog, int co, int Cin, int Cout) {
+        const double G[6][3] = {{0.25, 0., 0.}, {-1. / 6, -1. / 6, -1. / 6}, {-1. / 6, 1. / 6, -1. / 6},
+                                {1. / 24, 1. / 12, 1. / 6}, {1. / 24, -1. / 12, 1. / 6}, {0., 0., 1.}};
+        const int ua = xi / 6, ub = xi % 6;
         double u = 0.;
-        if (clog >= 0 && clog < Cin && co < Cout) {
-            const int ua = xi / 6, ub = xi % 6;
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < 3; ++p)
 #pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    u += G[ua][p] * G[ub][q] * (double)w[((size_t)(p * 3 + q) * Cin + clog) * Cout + co];
-        }
-        packed[idx] = (float)u;
+            for (int q = 0; q < 3; ++q) u += G[ua][p] * G[ub][q] * (double)w[((size_t)(p * 3 + q) * Cin + clog) * Cout + co];
+        return (float)u;
     }
-}
+};
 
-extern "C" size_t pwc_conv3x3_wino4_packed_floats(int Cin_phys, int Cout) {
-    if (Cin_phys <= 0 || Cout <= 0) return 0;
-    return (size_t)36 * Cin_phys * ((Cout + 15) & ~15);
-}
+extern "C" size_t pwc_conv3x3_wino4_packed_floats(int Cin_phys, int Cout) { return conv_fp32_packed_floats(36, Cin_phys, Cout); }
 
 extern "C" int pwc_conv3x3_wino4_pack_f32(const float* w_hwio, const int32_t* cin_map, int Cin, int Cin_phys,
                                           int Cout, float* packed, pwc_stream_t stream) {
-    if (!w_hwio || !packed || Cin <= 0 || Cout <= 0 || Cin_phys < Cin) return PWC_EINVAL;
-    if (Cin_phys % 16) return PWC_EALIGN;
-    const int Cout_pad = (Cout + 15) & ~15;
-    const size_t total = (size_t)36 * Cin_phys * Cout_pad;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv3x3_wino4_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map,
-                       Cin, Cin_phys, Cout, Cout_pad, packed);
-    return pwc_launch_status();
+    return conv_fp32_pack<Wino4Value>(36, w_hwio, cin_map, Cin, Cin_phys, Cout, packed, stream);
 }
 
 // Where F(4x4) pays (measured against conv3x3_wino.hip: scripts/exp_wino4.hip on isolated layers, profiles/r03_exp_wino4.txt,
@@ -411,11 +374,7 @@ extern "C" int pwc_conv3x3_wino4_supported(int N, int H, int W, int Cin_phys, in
 template <int ABL>
 static int wino4_launch(const Wino4Args& a, hipStream_t stream) {
     const size_t lds = (size_t)W4_STAGE * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino4_kernel<ABL>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&conv3x3_wino4_kernel<ABL>>((int)lds);
     hipLaunchKernelGGL((conv3x3_wino4_kernel<ABL>), dim3((unsigned)a.ntiles), dim3(W4_T), lds, stream, a);
     return pwc_launch_status();
 }
@@ -423,14 +382,9 @@ static int wino4_launch(const Wino4Args& a, hipStream_t stream) {
 extern "C" int pwc_conv3x3_wino4_f32(const float* x, int x_cs, const float* packed_u, const float* bias, float* y,
                                      int y_cs, int N, int H, int W, int Cin_phys, int Cout, int dilation,
                                      int apply_act, float slope, pwc_stream_t stream) {
-    if (!x || !packed_u || !bias || !y) return PWC_EINVAL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0 || dilation < 1) return PWC_EINVAL;
-    if (Cin_phys % 16 || Cout % 16) return PWC_EUNSUPPORTED;
-    if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed_u) || !pwc_aligned16(bias))
-        return PWC_EALIGN;
-    if ((long)H * W * x_cs * 4 >= (long)W4_OOB || (long)H * W * y_cs * 4 >= (long)W4_OOB) return PWC_ERANGE;
-    if ((long)36 * Cin_phys * ((Cout + 15) & ~15) * 4 >= (long)W4_OOB) return PWC_ERANGE;
+    if (const int rc = conv_fp32_io_check(x, x_cs, packed_u, bias, y, y_cs, N, H, W, Cin_phys, Cout, dilation, true)) return rc;
+    if ((long)H * W * x_cs * 4 >= (long)PWC_OOB || (long)H * W * y_cs * 4 >= (long)PWC_OOB) return PWC_ERANGE;
+    if ((long)36 * Cin_phys * ((Cout + 15) & ~15) * 4 >= (long)PWC_OOB) return PWC_ERANGE;
     Wino4Args a;
     a.x = x; a.up = packed_u; a.bias = bias; a.y = y; a.x_cs = x_cs; a.y_cs = y_cs;
     a.N = N; a.H = H; a.W = W; a.Cin_phys = Cin_phys; a.Cout = Cout; a.apply_act = apply_act; a.slope = slope;

@@ -97,7 +97,6 @@ struct CvRollGeom {
 #endif
 #define CVR_OOB 0x80000000u
 // s_waitcnt vmcnt(n) only (gfx9 encoding: vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8])
-#define CVR_WAIT_VM(n) __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | (7 << 4) | (15 << 8))
 
 typedef unsigned int cvr_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int cvr_u32x2 __attribute__((ext_vector_type(2)));
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(CvRollGeom::T) void cost_volume_roll_kernel(const C
         issue_pieces(Y0 - 4, 0, Y0, 0, true);
         issue_pieces(Y0, 4, 0, 0, false);
         issue_pieces(Y0 + 4, 8, 0, 0, false);
-        CVR_WAIT_VM(0);
+        PWC_WAIT_VM(0);
         stamp();
         pwc_lds_barrier();
         stamp();
@@ -353,8 +352,8 @@ __global__ __launch_bounds__(CvRollGeom::T) void cost_volume_roll_kernel(const C
             stamp();
             // the DMA pieces of step s+1 are older than this step's stores: wait for them only
             if (more) {
-                if (a.f0_copy) CVR_WAIT_VM(2 * G::NST_OUT + G::NST_CPY);
-                else CVR_WAIT_VM(2 * G::NST_OUT);
+                if (a.f0_copy) PWC_WAIT_VM(2 * G::NST_OUT + G::NST_CPY);
+                else PWC_WAIT_VM(2 * G::NST_OUT);
             }
             stamp();
             pwc_lds_barrier();

@@ -18,27 +18,20 @@ static inline int pwc_launch_status() {
     return e == hipSuccess ? PWC_OK : (int)e;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute: a launch site keeps one flag per device
-// (a process that uses the library on a second GPU must set it there too).  Idempotent, benign if raced.
-struct PwcDevOnce {
-    unsigned long long done[4] = {0, 0, 0, 0};
-};
-static inline bool pwc_first_on_device(PwcDevOnce* o) {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 256) return true;    // unknown: just set it again
-    const unsigned long long bit = 1ull << (d & 63);
-    if (o->done[d >> 6] & bit) return false;
-    o->done[d >> 6] |= bit;
-    return true;
-}
-
-// "Set the dynamic-LDS ceiling of this kernel once per device", in front of a launch: one flag set per kernel (the template is
-// instantiated per kernel POINTER, not per kernel type -- the instantiations of a kernel template share a type).
+// "Set the dynamic-LDS ceiling of this kernel once per device", in front of a launch.  hipFuncAttributeMaxDynamicSharedMemorySize
+// is a PER-DEVICE attribute: one flag per kernel and device (a process that uses the library on a second GPU must set it there
+// too).  Idempotent, benign if raced.  The template is instantiated per kernel POINTER, not per kernel type -- the
+// instantiations of a kernel template share a type.
 template <auto Kernel>
 static inline void pwc_allow_dynamic_lds(int bytes) {
-    static PwcDevOnce once;
-    if (pwc_first_on_device(&once))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    static unsigned long long done[4] = {0, 0, 0, 0};
+    int d = 0;
+    if (hipGetDevice(&d) == hipSuccess && d >= 0 && d < 256) {                  // (unknown device: just set it again)
+        const unsigned long long bit = 1ull << (d & 63);
+        if (done[d >> 6] & bit) return;
+        done[d >> 6] |= bit;
+    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 // Compute units of the current device, asked once per device (256 where the runtime cannot say): the grid of the persistent kernels.
@@ -56,21 +49,25 @@ static inline int pwc_cu_count() {
 
 static inline bool pwc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// The argument checks the F16-matrix-pipe conv entry points share, in the order they report: null pointers and non-positive
+// The argument checks the conv entry points share (F16 and fp32 matrix pipe), in the order they report: null pointers and non-positive
 // sizes (PWC_EINVAL), the family's own shape rule (`supported` false: PWC_EUNSUPPORTED), a channel stride below the channel
 // count (PWC_EINVAL), channel strides that are not whole 16-byte chunks and pointers off a 16-byte boundary (PWC_EALIGN).
+// y_aligned false: the kernel falls back to scalar stores, y and y_cs need no alignment.
 // What a family checks besides -- stride and dilation, further operands, the 32-bit range of ITS buffer resources -- stays with
 // it, in front of or behind this call as the code it reports has to win or lose.
 static inline int pwc_conv_io_check(const void* x, int x_cs, int Cin_phys, const void* y, int y_cs, int Cout, const void* packed_w,
-                                    const void* bias, int N, int H, int W, bool supported) {
+                                    const void* bias, int N, int H, int W, bool supported, bool y_aligned = true) {
     if (!x || !packed_w || !bias || !y) return PWC_EINVAL;
     if (N <= 0 || H <= 0 || W <= 0 || Cin_phys <= 0 || Cout <= 0) return PWC_EINVAL;
     if (!supported) return PWC_EUNSUPPORTED;
     if (x_cs < Cin_phys || y_cs < Cout) return PWC_EINVAL;
-    if ((x_cs & 3) || (y_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(y) || !pwc_aligned16(packed_w) || !pwc_aligned16(bias))
-        return PWC_EALIGN;
+    if ((x_cs & 3) || !pwc_aligned16(x) || !pwc_aligned16(packed_w) || !pwc_aligned16(bias)) return PWC_EALIGN;
+    if (y_aligned && ((y_cs & 3) || !pwc_aligned16(y))) return PWC_EALIGN;
     return PWC_OK;
 }
+// The out-of-range byte offset of the kernels whose buffer resources cover one image of less than PWC_OOB bytes: a load from it
+// returns zeros (the SAME padding), a store to it is dropped.
+constexpr unsigned PWC_OOB = 0x7FFF0000u;
 // A whole tensor behind ONE buffer resource with 32-bit byte offsets (an out-of-range offset, 2^31, is how a lane asks for
 // zeros): n x h x w records of cs floats must end below 2^31 bytes.
 static inline bool pwc_fits_2g(long n, long h, long w, long cs) { return n * h * w * cs * 4 < (1L << 31); }
@@ -154,9 +151,23 @@ __device__ __forceinline__ void pwc_lds_barrier() {
 #endif
 }
 
+// s_waitcnt vmcnt(n) only (gfx9 encoding: vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8]): the counted wait of the
+// software pipelines over buffer_load ... lds pieces
+#define PWC_WAIT_VM(n) __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | (7 << 4) | (15 << 8))
+
 __device__ __forceinline__ float pwc_lrelu(float v, float slope) {
     // tf.nn.leaky_relu(x, alpha) = max(alpha*x, x)
     return fmaxf(v, slope * v);
+}
+// ... of four values.  Two spellings of the same values, because each kernel's device code changed through the other one: the
+// MFMA, direct and reduce kernels multiply per element (four v_mul_f32 that the scheduler places between the stores), the
+// Winograd epilogues multiply the vector (two v_pk_mul_f32: their VALU time adds to the MFMA time, see conv3x3_wino.hip).
+__device__ __forceinline__ f32x4 pwc_lrelu4(f32x4 v, float slope) {
+    return f32x4{pwc_lrelu(v[0], slope), pwc_lrelu(v[1], slope), pwc_lrelu(v[2], slope), pwc_lrelu(v[3], slope)};
+}
+__device__ __forceinline__ f32x4 pwc_lrelu4_packed(f32x4 v, float slope) {
+    const f32x4 sv = v * slope;
+    return f32x4{fmaxf(v[0], sv[0]), fmaxf(v[1], sv[1]), fmaxf(v[2], sv[2]), fmaxf(v[3], sv[3])};
 }
 
 // Bijective XCD-aware remap of a linear workgroup id (MI355X: 8 XCDs, block b is

@@ -547,11 +547,7 @@ extern "C" int pwc_conv3x3_wino4b_supported(int N, int H, int W, int Cin_phys, i
 
 template <int ABL>
 static int wino4b_launch(const Wino4bArgs& a, hipStream_t stream) {
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino4b_kernel<ABL>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, WB_LDS + ((ABL & 128) ? 9216 : 0));
-    }
+    pwc_allow_dynamic_lds<&conv3x3_wino4b_kernel<ABL>>(WB_LDS + ((ABL & 128) ? 9216 : 0));
     hipLaunchKernelGGL((conv3x3_wino4b_kernel<ABL>), dim3((unsigned)a.ntiles), dim3(WB_T), WB_LDS + ((ABL & 128) ? 9216 : 0), stream, a);
     return pwc_launch_status();
 }

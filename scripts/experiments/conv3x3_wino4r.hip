@@ -447,11 +447,7 @@ extern "C" int pwc_conv3x3_wino4r_supported(int N, int H, int W, int Cin_phys, i
 template <int ABL>
 static int wino4r_launch(const Wino4rArgs& a, hipStream_t stream) {
     const int lds = WR_LDS + ((ABL & 128) ? 9216 : 0);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino4r_kernel<ABL>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
+    pwc_allow_dynamic_lds<&conv3x3_wino4r_kernel<ABL>>(lds);
     hipLaunchKernelGGL((conv3x3_wino4r_kernel<ABL>), dim3((unsigned)a.ntiles), dim3(WR_T), lds, stream, a);
     return pwc_launch_status();
 }

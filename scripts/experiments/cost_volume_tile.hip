@@ -375,11 +375,7 @@ template <bool WARP, bool PAD, bool FLOWPAD = false>
 static int cvt_launch_t(CvmArgs& a, hipStream_t s) {
     using GT = CvtGeom<CVT_TBY>;
     const size_t lds = (size_t)GT::LDS_F * sizeof(float);
-    static PwcDevOnce attr_once;   // the attribute is per device
-    if (pwc_first_on_device(&attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_volume_tile_kernel<CVT_TBY, WARP, PAD, FLOWPAD>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    pwc_allow_dynamic_lds<&cost_volume_tile_kernel<CVT_TBY, WARP, PAD, FLOWPAD>>((int)lds);
     a.nstrips = (a.W + 15) / 16;
     a.seg_brows = CVT_TBY;
     a.nseg = (a.nbrows + CVT_TBY - 1) / CVT_TBY;

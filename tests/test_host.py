@@ -202,6 +202,103 @@ def test_f16_conv_entry_points_report_the_same_codes():
     assert not got, got
 
 
+_FP32_CONV_ARGS = "x x_cs pw bias y y_cs N H W Cin Cout dil act slope stream"
+_FP32_CONV_GOOD = dict(x=_AL, x_cs=32, pw=_AL, bias=_AL, y=_AL, y_cs=32, N=1, H=16, W=32, Cin=32, Cout=32, dil=1, act=1, slope=0.1, stream=None)
+_FP32_PACK_GOOD = dict(w=_AL, cmap=None, Cin=16, Cin_phys=16, Cout=16, packed=_AL, stream=None)
+# entry point -> (argument names in call order, a call that passes every check)
+_FP32_CONV_CALLS = {
+    "pwc_conv3x3_f32": (
+        "x x_cs pw bias y y_cs N H W Cin Cout stride dil act slope tile split ws wsf stream",
+        dict(_FP32_CONV_GOOD, stride=1, tile=-1, split=0, ws=None, wsf=0)),
+    "pwc_conv3x3_wino_f32": (_FP32_CONV_ARGS, _FP32_CONV_GOOD),
+    "pwc_conv3x3_wino_split_f32": (
+        "x x_cs pw bias y y_cs N H W Cin Cout dil act slope csplit ws wsf stream",
+        dict(_FP32_CONV_GOOD, csplit=1, ws=_AL, wsf=2 * 16 * 32 * 32)),
+    "pwc_conv3x3_wino4_f32": (_FP32_CONV_ARGS, _FP32_CONV_GOOD),
+    "pwc_conv3x3_pack_f32": ("w cmap Cin Cin_phys Cout packed stream", _FP32_PACK_GOOD),
+    "pwc_conv3x3_wino_pack_f32": ("w cmap Cin Cin_phys Cout packed stream", _FP32_PACK_GOOD),
+    "pwc_conv3x3_wino4_pack_f32": ("w cmap Cin Cin_phys Cout packed stream", _FP32_PACK_GOOD),
+}
+_FP32_CONVS = tuple(n for n in _FP32_CONV_CALLS if "pack" not in n)
+_FP32_PACKERS = tuple(n for n in _FP32_CONV_CALLS if "pack" in n)
+_FP32_Y_ALIGNED = ("pwc_conv3x3_wino4_f32",)       # F(4x4) stores 16 bytes at a time; the others fall back to scalar stores
+_FP32_WIDE = dict(_BIG, wsf=1 << 35)               # (a workspace long enough for the channel split's own check)
+# (entry point, the bad arguments, the code): one fault per row first, then rows with two faults that pin which one is reported
+_FP32_CONV_FAULTS = [(name, bad, code) for name in _FP32_CONVS for bad, code in (
+    (dict(x=None), _EINVAL), (dict(pw=None), _EINVAL), (dict(bias=None), _EINVAL), (dict(y=None), _EINVAL),        # a null pointer
+    (dict(N=0), _EINVAL), (dict(H=-1), _EINVAL), (dict(W=0), _EINVAL), (dict(Cin=0), _EINVAL), (dict(Cout=0), _EINVAL),     # a zero size
+    (dict(dil=0), _EINVAL),
+    (dict(Cin=24), _EUNSUP), (dict(Cout=24), _EUNSUP),                                  # channel counts that are no multiple of 16
+    (dict(x_cs=16), _EINVAL), (dict(y_cs=16), _EINVAL),                                 # a channel stride below the channel count
+    (dict(x=_MIS), _EALIGN), (dict(pw=_MIS), _EALIGN), (dict(bias=_MIS), _EALIGN), (dict(Cin=16, x_cs=18), _EALIGN),
+    # a misaligned y or y_cs: F(4x4) refuses it, the others go on to their next rule (a short x_cs is reported first by all)
+    (dict(y=_MIS, x_cs=16), _EINVAL), (dict(_FP32_WIDE, y=_MIS), _EALIGN if name in _FP32_Y_ALIGNED else _ERANGE),
+    (dict(_FP32_WIDE, y_cs=34), _EALIGN if name in _FP32_Y_ALIGNED else _ERANGE),
+    (dict(_FP32_WIDE), _ERANGE),                                                        # an image beyond 2^31 bytes
+    # two faults of adjacent rules: null pointer / size, size / channel multiple, channel multiple / short stride,
+    # short stride / alignment, alignment / range
+    (dict(x=None, N=0), _EINVAL), (dict(x=None, Cin=24), _EINVAL), (dict(N=0, Cin=24), _EINVAL), (dict(dil=0, Cout=24), _EINVAL),
+    (dict(Cin=24, x_cs=16), _EUNSUP), (dict(Cout=24, y_cs=16), _EUNSUP), (dict(Cin=24, x=_MIS), _EUNSUP),
+    (dict(x_cs=16, x=_MIS), _EINVAL), (dict(y_cs=16, bias=_MIS), _EINVAL),
+    (dict(_FP32_WIDE, x=_MIS), _EALIGN), (dict(_FP32_WIDE, pw=_MIS), _EALIGN), (dict(_FP32_WIDE, N=0), _EINVAL),
+    (dict(_FP32_WIDE, Cin=24), _EUNSUP), (dict(_FP32_WIDE, y_cs=16), _EINVAL))] + [
+    # the MFMA kernel's own: stride, tile, tap split and its workspace (the split is checked in front of the range, the tile
+    # and the workspace behind it)
+    ("pwc_conv3x3_f32", dict(stride=3), _EINVAL), ("pwc_conv3x3_f32", dict(stride=0), _EINVAL), ("pwc_conv3x3_f32", dict(stride=3, Cin=24), _EINVAL),
+    ("pwc_conv3x3_f32", dict(split=2), _EINVAL), ("pwc_conv3x3_f32", dict(split=-1), _EINVAL), ("pwc_conv3x3_f32", dict(split=27), _EINVAL),
+    ("pwc_conv3x3_f32", dict(split=2, x=_MIS), _EALIGN), ("pwc_conv3x3_f32", dict(_BIG, split=2), _EINVAL),
+    ("pwc_conv3x3_f32", dict(tile=15), _EINVAL), ("pwc_conv3x3_f32", dict(tile=0), _EINVAL), ("pwc_conv3x3_f32", dict(_BIG, tile=15), _ERANGE),
+    ("pwc_conv3x3_f32", dict(tile=14, split=3), _EINVAL), ("pwc_conv3x3_f32", dict(tile=14, split=3, ws=_MIS, wsf=1 << 20), _EINVAL),
+    ("pwc_conv3x3_f32", dict(tile=14, split=3, ws=_AL, wsf=3 * 512 * 32 - 1), _EINVAL), ("pwc_conv3x3_f32", dict(split=9, ws=_AL, wsf=100), _EINVAL),
+    ("pwc_conv3x3_f32", dict(N=1 << 12, H=1 << 10, W=1 << 9), _ERANGE),                 # 2^31 output pixels, each image in range
+    # the channel split's own: csplit, its workspace -- reported in front of every shared rule
+    ("pwc_conv3x3_wino_split_f32", dict(csplit=0), _EINVAL), ("pwc_conv3x3_wino_split_f32", dict(csplit=-2), _EINVAL),
+    ("pwc_conv3x3_wino_split_f32", dict(csplit=3), _EINVAL), ("pwc_conv3x3_wino_split_f32", dict(csplit=2, ws=None), _EINVAL),
+    ("pwc_conv3x3_wino_split_f32", dict(csplit=2, ws=_MIS), _EINVAL), ("pwc_conv3x3_wino_split_f32", dict(csplit=2, wsf=2 * 16 * 32 * 32 - 1), _EINVAL),
+    ("pwc_conv3x3_wino_split_f32", dict(csplit=0, x=_MIS), _EINVAL), ("pwc_conv3x3_wino_split_f32", dict(csplit=2, ws=None, x=_MIS), _EINVAL),
+    ("pwc_conv3x3_wino_split_f32", dict(csplit=2, ws=None, Cout=24), _EINVAL), ("pwc_conv3x3_wino_split_f32", dict(_BIG, csplit=2), _EINVAL),
+    ("pwc_conv3x3_wino_split_f32", dict(csplit=2, Cin=24), _EINVAL), ("pwc_conv3x3_wino_split_f32", dict(csplit=2, x=_MIS), _EALIGN),
+    ("pwc_conv3x3_wino_split_f32", dict(csplit=2, Cout=24), _EUNSUP), ("pwc_conv3x3_wino_split_f32", dict(_FP32_WIDE, csplit=2), _ERANGE)] + [
+    # the packed weights behind one buffer resource: the two Winograd families only
+    (name, dict(Cin=8192, x_cs=8192, Cout=4096, y_cs=4096, wsf=1 << 35), _ERANGE)
+    for name in ("pwc_conv3x3_wino_f32", "pwc_conv3x3_wino_split_f32", "pwc_conv3x3_wino4_f32")] + [
+    ("pwc_conv3x3_wino_f32", dict(Cin=8192, x_cs=8192, Cout=4096, y_cs=4096, x=_MIS), _EALIGN),
+    ("pwc_conv3x3_wino4_f32", dict(Cin=8192, x_cs=8192, Cout=4096, y_cs=4096, y=_MIS), _EALIGN),
+    ("pwc_conv3x3_wino4_f32", dict(y=_MIS), _EALIGN), ("pwc_conv3x3_wino4_f32", dict(y_cs=34), _EALIGN), ("pwc_conv3x3_wino4_f32", dict(y_cs=34, x_cs=16), _EINVAL),
+    ("pwc_conv3x3_wino4_f32", dict(y=_MIS, Cout=24), _EUNSUP)] + [
+    (name, bad, code) for name in _FP32_PACKERS for bad, code in (
+        (dict(w=None), _EINVAL), (dict(packed=None), _EINVAL), (dict(Cin=0), _EINVAL), (dict(Cout=0), _EINVAL), (dict(Cout=-16), _EINVAL),
+        (dict(Cin_phys=8), _EINVAL), (dict(Cin=24), _EINVAL),                           # fewer physical than logical channels
+        (dict(Cin=8, Cin_phys=8), _EALIGN), (dict(Cin_phys=24), _EALIGN),               # physical channels in whole groups of 16
+        (dict(w=None, Cin_phys=24), _EINVAL), (dict(Cin=24, Cin_phys=20), _EINVAL))]
+
+
+def test_fp32_conv_entry_points_report_the_same_codes():
+    """The argument checks of the fp32-matrix-pipe conv entry points (conv3x3_mfma / wino / wino4) and of their weight packers go
+    through shared checkers (pwc_conv_io_check, pwc_common.h; the packers' in conv_fp32_common.h); every family keeps the rules
+    that are its own (stride, tile, tap split, channel split, the ranges of its buffer resources, whether y must be aligned).
+    This table pins which code each entry point returns for a bad call -- one fault at a time, then two at once (which one wins) --
+    as recorded from the library before the checks were shared.  Every row fails a check: nothing is launched, no GPU is needed."""
+    L = _lib.lib()
+    assert all(code != 0 for _, _, code in _FP32_CONV_FAULTS)
+    assert {name for name, _, _ in _FP32_CONV_FAULTS} == set(_FP32_CONV_CALLS)
+    got = []
+    for name, bad, code in _FP32_CONV_FAULTS:
+        names, good = _FP32_CONV_CALLS[name]
+        assert set(bad) <= set(good) | {"wsf"}, (name, bad)
+        args = dict(good, **{k: v for k, v in bad.items() if k in good})                # (wsf: the entry points with a workspace)
+        assert args != good, (name, bad)
+        rc = getattr(L, name)(*[args[k] for k in names.split()])
+        if rc != code:
+            got.append((name, bad, code, rc))
+    assert not got, got
+    # the packed sizes: positions x physical input channels x output channels in whole groups of 16; 0 for a bad call
+    for name, positions in (("pwc_conv3x3", 9), ("pwc_conv3x3_wino", 16), ("pwc_conv3x3_wino4", 36)):
+        floats = getattr(L, name + "_packed_floats")
+        assert floats(48, 24) == positions * 48 * 32 and floats(16, 16) == positions * 256
+        assert floats(0, 16) == 0 and floats(16, 0) == 0 and floats(-16, 16) == 0
+
+
 _MIS2 = 4098                # not even 4-byte aligned: the flow operand of the buffer-resource kernels
 _CV_CONCAT_ARGS = "f0 f0_cs f1 f1_cs flow flow_cs scale out out_cs pad copy copy_cs N H W C R slope stream"
 _CV_GOOD = dict(f0=_AL, f0_cs=32, f1=_AL, f1_cs=32, flow=_AL, flow_cs=2, scale=1.25, out=_AL, out_cs=84, pad=0, copy=_AL, copy_cs=32,
