@@ -600,7 +600,7 @@ int pwc_flow_metrics_f32(const float* pred, int pred_cs, const float* gt, int gt
                          int N, int H, int W, float* workspace, size_t workspace_floats, double* out,
                          pwc_stream_t stream);
 
-/* ==== self-supervised losses: the photometric warp term and the edge-aware smoothness of the flow ====
+/* ==== self-supervised losses: the photometric warp term, the edge-aware smoothness of the flow, the soft census term ====
  * Two loss terms that need no ground truth, each as per-image sums (a deterministic two-stage reduction: workgroup partials in
  * `workspace`, added in index order) and as the gradient of those sums with respect to the flow (a gather, one lane per pixel,
  * no atomics: deterministic).  All tensors NHWC fp32, pointer + channel stride; images have C = 1..4 channels and no alignment
@@ -642,6 +642,39 @@ int pwc_flow_smoothness_sums_f32(const float* flow, int flow_cs, const float* im
 int pwc_flow_smoothness_grad_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
                                  float eps, float q, int N, int H, int W, const float* dsums, float* dflow, int dflow_cs,
                                  int accumulate, pwc_stream_t stream);
+
+/* Soft census (ternary) term: the photometric term on the local intensity ORDER, invariant to additive and largely to
+ * multiplicative brightness changes.  Grey planes a(p) = scale * mean_c images_0[p] and b(p) = scale * mean_c (the photometric
+ * term's bilinear sample of images_1 at p moved by flow_scale * flow[p]; sample point, weights and blend in double, rounded
+ * once); b(p) = 0 with zero derivative where the sample point is out of frame or the flow is not finite.  With the K =
+ * (2 radius + 1)^2 - 1 offsets o != 0 of the window,
+ *   t0 = a(p+o) - a(p), t1 = b(p+o) - b(p), tau(t) = t / sqrt(c1 + t^2), d = (tau(t0) - tau(t1))^2, h(p) = (1/K) sum_o d / (c2 + d).
+ * Pixel p CONTRIBUTES iff it is at least `radius` pixels from every border (no padding), its sample point is in frame, and
+ * (valid == NULL or valid[p] != 0).  Unlike the photometric term's, the mask and the in-frame test select CENTRES only: the
+ * neighbours of a contributing centre are always read (images_0 at a masked pixel must hold numbers).  out_sums[n] = sum over
+ * the contributing pixels of rho(h(p)), out_counts[n] = their number (exact); H <= 2 radius or W <= 2 radius: both 0, no error.
+ * Three launches: a per-pixel pass that writes a, b and the in-frame flag to workspace planes, a windowed pass (32 x 8 tiles of
+ * centres with a `radius` halo staged in the LDS) that adds its tiles' terms in a fixed tree, and the parts added in index
+ * order: two calls give the same bits.  workspace: at least pwc_census_workspace_floats(N, H, W, with_grad) floats, with_grad
+ * 0 for the sums and 1 for the gradient.  Checks, in this order: null pointers and sizes <= 0 (PWC_EINVAL); C outside 1..4
+ * or radius outside 1..3 (PWC_EUNSUPPORTED); a channel stride below the channel count, eps, scale, c1 or c2 <= 0, q outside
+ * (0, 1] (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); a null or short workspace, null outputs (PWC_EINVAL). */
+size_t pwc_census_workspace_floats(int N, int H, int W, int with_grad);
+int pwc_census_sums_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
+                        float flow_scale, const uint8_t* valid, int N, int H, int W, int C, int radius, float scale,
+                        float c1, float c2, float eps, float q, float* workspace, size_t workspace_floats,
+                        float* out_sums, int32_t* out_counts, pwc_stream_t stream);
+/* dflow (+)= the gradient of sum_n dsums[n] * out_sums[n] w.r.t. the flow.  With G(p) = dsums[n] rho'(h(p)) / K where p
+ * contributes and 0 elsewhere, and D(t0, t1) = c2 / (c2 + d)^2 * 2 (tau(t1) - tau(t0)) * c1 / (c1 + t1^2)^(3/2):
+ *   dL/db(q) = -sum_o (G(q) + G(q+o)) D(t0(q,o), t1(q,o))   over the offsets with q+o inside the image
+ * (tau is odd, so q as a centre and q as a neighbour of the centre q+o share one loop), and, where q is in frame,
+ *   dflow[q] = flow_scale * scale * dL/db(q) * mean_c (d sample / d x, d sample / d y).
+ * A pixel that is out of frame gets 0 (accumulate == 0) or is left untouched (accumulate != 0).  A gather over the same tiles
+ * with a, b and G staged: no atomics, two calls give the same bits.  dsums: N floats on the device. */
+int pwc_census_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
+                        float flow_scale, const uint8_t* valid, int N, int H, int W, int C, int radius, float scale,
+                        float c1, float c2, float eps, float q, const float* dsums, float* workspace,
+                        size_t workspace_floats, float* dflow, int dflow_cs, int accumulate, pwc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,11 @@
-// loss_common.h -- what the loss, loss-gradient and metric kernels (pwc_flow_loss.hip, pwc_unsup.hip) share.  Their numerics are
+// loss_common.h -- what the loss, loss-gradient and metric kernels (pwc_flow_loss.hip, pwc_unsup.hip, pwc_census.hip) share.  Their numerics are
 // bit-level contracts (tests/test_gpu_loss_bits.py), and every rule of them is written here once:
 //   sums       an image is cut into at most 256 parts of 256-pixel strides (pwc_loss_parts), a workgroup adds its part in a fixed
 //              tree (pwc_block_tree_sum), one thread per image adds the parts in index order (pwc_loss_final_kernel) -- two calls
 //              give the same bits;
 //   norm       the ground truth's nearest-neighbour index (pwc_nearest_index), the difference with the ground truth DIVIDED
 //              (pwc_flow_diff), the norm of a pixel and its direction (pwc_norm_term, pwc_norm_direction);
+//   rho        the generalised Charbonnier function of the label-free terms and its derivative (unsup_rho, unsup_rho_grad);
 //   gradients  gathers, one lane per pixel of the batch: the flat pixel's (n, y, x) (pwc_loss_pixel), the launch width
 //              (pwc_loss_grad_blocks), the plain / accumulate store of the two channels (pwc_grad_store2, pwc_grad_skip2).
 #pragma once
@@ -130,6 +131,11 @@ __device__ __forceinline__ void pwc_norm_direction(float dx, float dy, int ord, 
         oy = nrm > 0.f ? dy / nrm : 0.f;
     }
 }
+
+// ---------------------------------------------------------------- device: the robust function of the label-free terms
+// rho(d) = (d^2 + eps^2)^q (generalised Charbonnier) and rho'(d); eps2 = eps * eps (pwc_unsup.hip, pwc_census.hip).
+__device__ __forceinline__ float unsup_rho(float d, float eps2, float q) { return powf(d * d + eps2, q); }
+__device__ __forceinline__ float unsup_rho_grad(float d, float eps2, float q) { return 2.f * q * d * powf(d * d + eps2, q - 1.f); }
 
 // ---------------------------------------------------------------- device: gradient scaffolding
 // Flat pixel p of an [N][H][W] batch.

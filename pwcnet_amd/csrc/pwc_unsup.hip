@@ -15,11 +15,8 @@
 // rounded to fp32 once: the gradient then carries fp32's RELATIVE error.  Images have 1..4 channels at any channel stride:
 // scalar loads, no alignment asked.  Sums: every workgroup adds its pixels in a fixed tree and writes one partial, one thread
 // per image adds the partials in index order -- two calls give the same bits.  The gradients are gathers, one lane per pixel.
-// Partition, tree, final sum and the gradients' pixel walk and store are those of loss_common.h.
+// Partition, tree, final sum, rho and the gradients' pixel walk and store are those of loss_common.h.
 #include "loss_common.h"
-
-__device__ __forceinline__ float unsup_rho(float d, float eps2, float q) { return powf(d * d + eps2, q); }
-__device__ __forceinline__ float unsup_rho_grad(float d, float eps2, float q) { return 2.f * q * d * powf(d * d + eps2, q - 1.f); }
 
 // ------------------------------------------------------------------ photometric term
 struct PhotoArgs {

@@ -5,12 +5,17 @@
     smoothness_sums(flows, images=None, ...)           -> sums (N,)
     smoothness_loss(...)                               -> sums.sum() / (N * H * W)
 
+    census_sums(images_0, images_1, flows, ...)        -> (sums (N,), counts (N,) int32)
+    census_loss(...)                                    -> sums.sum() / counts.sum().clamp(min=1)
+
 With rho(d) = (d^2 + eps^2)^q: the photometric term of a pixel is sum_c rho(images_0 - bilinear sample of images_1 at the pixel
 moved by flow_scale * flow), over the pixels that are valid (`valid`, grad_ops.mask_ptr's format, e.g. an occlusion mask of the
 caller's) and whose sample point lies inside the frame; the smoothness term is the sum of exp(-alpha * mean_c |d image|) *
 rho(d flow) over the forward differences along x and y (include/pwc_hip.h, "self-supervised losses").
 `sums` is differentiable with respect to `flows` (pwc_photometric_grad_f32 / pwc_flow_smoothness_grad_f32: gathers, bit
 reproducible), so the losses compose with PWCDCNetModule; the images are constants -- an image that requires grad is refused.
+The census term compares the local intensity ORDER in a (2 radius + 1)^2 window of the grey images instead of the intensities
+(csrc/pwc_census.hip; the formulas are in census_sums' docstring), so a brightness change between the frames does not pull the flow.
 No double backward.
 """
 import torch
@@ -98,6 +103,82 @@ def smoothness_grad(flows, dsums, dflow=None, images=None, alpha=10.0, eps=1e-3,
                                                        _p(up.data_ptr()), _p(dv.ptr), dv.cs, 1 if accumulate else 0,
                                                        _lib.current_stream()), "flow smoothness grad")
     return dflow
+
+
+def _check_census(radius, scale, c1, c2, eps, q, what):
+    eps, q = _check_rho(eps, q, what)
+    if isinstance(radius, bool) or not isinstance(radius, int) or radius not in (1, 2, 3):
+        raise ValueError(f"{what}: radius must be 1, 2 or 3, got {radius!r}")
+    scale, c1, c2 = float(scale), float(c1), float(c2)
+    for name, v in (("scale", scale), ("c1", c1), ("c2", c2)):
+        if not v > 0.0:
+            raise ValueError(f"{what}: {name} must be positive, got {v}")
+    return radius, scale, c1, c2, eps, q
+
+
+def _check_census_tensors(images_0, images_1, flows, valid):
+    _check_nhwc(flows, "flows", (2,))
+    _check_image(images_0, "images_0", flows)
+    _check_image(images_1, "images_1", flows)
+    if images_0.shape[3] != images_1.shape[3]:
+        raise ValueError(f"images_0 has {images_0.shape[3]} channels, images_1 {images_1.shape[3]}")
+    if valid is not None:
+        mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+    _check_gpu(flows, images_0=images_0, images_1=images_1)
+
+
+def census_grad(images_0, images_1, flows, dsums, dflow=None, flow_scale=1.0, valid=None, radius=3, scale=255.0, c1=0.81,
+                c2=0.1, eps=1e-2, q=0.4, accumulate=False):
+    """dflow (+)= the gradient of (dsums * census_sums(...)[0]).sum() w.r.t. flows (pwc_census_grad_f32); dsums: (N,) on the
+    GPU.  dflow None: a new tensor; accumulate: added onto dflow, out-of-frame pixels are left alone (without it they get 0).
+    Returns dflow.  What the autograd backward of census_sums calls."""
+    radius, scale, c1, c2, eps, q = _check_census(radius, scale, c1, c2, eps, q, "census_grad")
+    _check_census_tensors(images_0, images_1, flows, valid)
+    vp = None if valid is None else mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+    fv, flows = as_view(flows, "flows")
+    v0, images_0 = as_view(images_0, "images_0")
+    v1, images_1 = as_view(images_1, "images_1")
+    L = _lib.lib()
+    up = torch.empty((fv.N,), dtype=torch.float32, device=flows.device).copy_(dsums)       # contiguous float32, its own
+    dv, dflow = _dflow_view(dflow, fv, flows.device)
+    ws = torch.empty((max(L.pwc_census_workspace_floats(fv.N, fv.H, fv.W, 1), 1),), dtype=torch.float32, device=flows.device)
+    _lib.check(L.pwc_census_grad_f32(_p(v0.ptr), v0.cs, _p(v1.ptr), v1.cs, _p(fv.ptr), fv.cs, float(flow_scale), vp, fv.N, fv.H,
+                                     fv.W, v0.C, radius, scale, c1, c2, eps, q, _p(up.data_ptr()), _p(ws.data_ptr()), ws.numel(),
+                                     _p(dv.ptr), dv.cs, 1 if accumulate else 0, _lib.current_stream()), "census grad")
+    return dflow
+
+
+class _CensusSums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, images_0, images_1, flow_scale, valid, consts):
+        ctx.set_materialize_grads(False)
+        radius, scale, c1, c2, eps, q = consts
+        vp = None if valid is None else mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+        fv, flows = as_view(flows, "flows")
+        v0, images_0 = as_view(images_0, "images_0")
+        v1, images_1 = as_view(images_1, "images_1")
+        L = _lib.lib()
+        dev = flows.device
+        sums = torch.empty((fv.N,), dtype=torch.float32, device=dev)
+        counts = torch.empty((fv.N,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(L.pwc_census_workspace_floats(fv.N, fv.H, fv.W, 0), 1),), dtype=torch.float32, device=dev)
+        _lib.check(L.pwc_census_sums_f32(_p(v0.ptr), v0.cs, _p(v1.ptr), v1.cs, _p(fv.ptr), fv.cs, flow_scale, vp, fv.N, fv.H,
+                                         fv.W, v0.C, radius, scale, c1, c2, eps, q, _p(ws.data_ptr()), ws.numel(),
+                                         _p(sums.data_ptr()), _p(counts.data_ptr()), _lib.current_stream()), "census sums")
+        ctx.save_for_backward(flows, images_0, images_1)
+        ctx.valid, ctx.consts = valid, (flow_scale,) + tuple(consts)
+        ctx.mark_non_differentiable(counts)
+        return sums, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dsums, _dcounts):
+        if dsums is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        flows, images_0, images_1 = ctx.saved_tensors
+        flow_scale, radius, scale, c1, c2, eps, q = ctx.consts
+        dflow = census_grad(images_0, images_1, flows, dsums, None, flow_scale, ctx.valid, radius, scale, c1, c2, eps, q)
+        return dflow, None, None, None, None, None
 
 
 class _PhotometricSums(torch.autograd.Function):
@@ -210,3 +291,27 @@ def smoothness_loss(flows, images=None, alpha=10.0, eps=1e-3, q=0.5):
     """0-dim: smoothness_sums(...).sum() / (N * H * W)."""
     sums = smoothness_sums(flows, images, alpha, eps, q)
     return sums.sum() / float(flows.shape[0] * flows.shape[1] * flows.shape[2])
+
+
+def census_sums(images_0, images_1, flows, flow_scale=1.0, valid=None, radius=3, scale=255.0, c1=0.81, c2=0.1, eps=1e-2, q=0.4):
+    """(sums (N,) float32, counts (N,) int32) of the soft census (ternary) term.  Grey planes a = scale * mean_c images_0 and
+    b = scale * mean_c (images_1 sampled at the pixel moved by flow_scale * flows, photometric_sums' sample; 0 where the sample
+    point is out of frame or the flow is not finite).  Over the K = (2 radius + 1)^2 - 1 offsets o != 0 of the window:
+        t0 = a(p+o) - a(p),  t1 = b(p+o) - b(p),  tau(t) = t / sqrt(c1 + t^2),  d = (tau(t0) - tau(t1))^2,
+        h(p) = (1/K) sum_o d / (c2 + d),
+    sums[n] = the sum of rho(h(p)) = (h^2 + eps^2)^q over the contributing pixels, counts[n] their number.  A pixel contributes
+    when it is at least `radius` pixels from every border (no padding), its sample point is inside the frame, and valid[p] is
+    set (valid: (N,H,W) torch.bool / torch.uint8, None = all).  UNLIKE photometric_sums, `valid` and the in-frame test select
+    CENTRES only: the neighbours in a contributing centre's window are always read, so the images must hold numbers at masked
+    pixels too.  H <= 2 radius or W <= 2 radius: counts and sums are 0, no error.  images: (N,H,W,C), C = 1..4, in [0, 1] with
+    the default scale (the constants are UnFlow's, for 0..255 grey values); radius: 1, 2 or 3.  sums is differentiable w.r.t.
+    flows (pwc_census_grad_f32: a gather, bit reproducible); the images are constants."""
+    consts = _check_census(radius, scale, c1, c2, eps, q, "census_sums")
+    _check_census_tensors(images_0, images_1, flows, valid)
+    return _CensusSums.apply(flows, images_0, images_1, float(flow_scale), valid, consts)
+
+
+def census_loss(images_0, images_1, flows, flow_scale=1.0, valid=None, radius=3, scale=255.0, c1=0.81, c2=0.1, eps=1e-2, q=0.4):
+    """0-dim: the mean of rho(h) over the contributing pixels; 0 when no pixel contributes."""
+    sums, counts = census_sums(images_0, images_1, flows, flow_scale, valid, radius, scale, c1, c2, eps, q)
+    return sums.sum() / counts.sum().clamp(min=1).to(torch.float32)

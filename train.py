@@ -18,6 +18,8 @@ Both use_dc settings and both losses (multiscale, robust) are implemented (Train
 `--loss unsup` trains without labels: PWCDCNetModule under torch.optim.Adam on photometric_loss(flows_final) + --smooth_weight *
 smoothness_loss(flows_final, images_0) (pwcnet_amd/unsup.py: images_1 warped by the predicted flow against images_0, and an
 edge-aware first-order smoothness of the flow).  Ground truth, where the data set has it, is used for the validation line only.
+`--photo census` replaces the data term by census_loss(flows_final, radius=--census_radius): the soft census (ternary) term on the
+local intensity order, which a brightness change between the frames does not move.
 Single process, constant learning rate; --gamma is Adam's weight_decay (the same gamma * l2_loss gradient).
 
 Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
@@ -122,7 +124,8 @@ def validate(args, weights, ds, val_idx, dist=None):
 def train_unsup(args, ds, train_idx, val_idx):
     """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet."""
     from pwcnet_amd import PWCDCNetModule, ckpt
-    from pwcnet_amd.unsup import photometric_loss, smoothness_loss
+    from pwcnet_amd.unsup import census_loss, photometric_loss, smoothness_loss
+    term = "census" if args.photo == "census" else "photometric"
     model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                            use_dc=args.use_dc, output_level=args.output_level)
     if args.resume is not None:
@@ -138,7 +141,10 @@ def train_unsup(args, ds, train_idx, val_idx):
             images_0, images_1 = (images_0 / 255.0).cuda(), (images_1 / 255.0).cuda()
             opt.zero_grad(set_to_none=True)
             flows_final, _ = model(images_0, images_1)
-            photo = photometric_loss(images_0, images_1, flows_final, eps=args.photo_eps, q=args.photo_q)
+            if args.photo == "census":
+                photo = census_loss(images_0, images_1, flows_final, radius=args.census_radius)
+            else:
+                photo = photometric_loss(images_0, images_1, flows_final, eps=args.photo_eps, q=args.photo_q)
             smooth = smoothness_loss(flows_final, images_0, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q)
             loss = photo + args.smooth_weight * smooth
             loss.backward()
@@ -146,7 +152,7 @@ def train_unsup(args, ds, train_idx, val_idx):
             global_step += 1
             n_steps += 1
             loss_sum += float(loss)
-            print(f"step {global_step}: loss/unsup {float(loss):.6f}  photometric {float(photo):.6f}  smoothness {float(smooth):.6f}")
+            print(f"step {global_step}: loss/unsup {float(loss):.6f}  {term} {float(photo):.6f}  smoothness {float(smooth):.6f}")
         res = validate(args, model.tf_state_dict(), ds, val_idx)
         dt = time.time() - t0
         print(f"epoch {e + 1}: loss/unsup {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
@@ -173,6 +179,10 @@ def main():
     ap.add_argument("--output_level", type=int, default=4)
     ap.add_argument("--loss", default="multiscale", choices=["multiscale", "robust", "unsup"],
                     help="multiscale | robust: supervised (Trainer); unsup: photometric + smoothness, no labels [multiscale]")
+    ap.add_argument("--photo", default="charbonnier", choices=["charbonnier", "census"],
+                    help="--loss unsup: the data term, Charbonnier on intensities or soft census on their local order [charbonnier]")
+    ap.add_argument("--census_radius", type=int, default=3, choices=[1, 2, 3],
+                    help="--photo census: window radius, (2r+1)^2 - 1 neighbours [3]")
     ap.add_argument("--smooth_weight", type=float, default=0.1, help="--loss unsup: weight of the smoothness term [0.1]")
     ap.add_argument("--photo_eps", type=float, default=1e-3, help="--loss unsup: Charbonnier epsilon of both terms [1e-3]")
     ap.add_argument("--photo_q", type=float, default=0.5, help="--loss unsup: Charbonnier exponent of both terms [0.5]")
