@@ -676,6 +676,31 @@ int pwc_census_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_
                         float c1, float c2, float eps, float q, const float* dsums, float* workspace,
                         size_t workspace_floats, float* dflow, int dflow_cs, int accumulate, pwc_stream_t stream);
 
+/* ==== occlusion: forward-backward consistency of two flows (the `valid` masks of the data terms above) ====
+ * flow_a is the flow 0 -> 1, flow_b the flow 1 -> 0, both NHWC fp32 with 2 channels at channel strides a_cs, b_cs >= 2 (scalar
+ * loads, no alignment asked).  For direction a, pixel p = (n, y, x): f = flow_scale * flow_a[p], (px, py) = (x + f0, y + f1);
+ * the in-frame test 0 <= px <= W - 1, 0 <= py <= H - 1 (a NaN or Inf fails it) and the bilinear sample are the photometric
+ * term's (x0 = floor(px), x1 = min(x0 + 1, W - 1), weight px - x0 on x1, the same in y); g = flow_scale * (that sample of
+ * flow_b, both channels).  valid_a[p] = 1 iff (valid_a_in == NULL or valid_a_in[p] != 0) and the sample point is in frame and
+ *   |f + g|^2 <= alpha1 * (|f|^2 + |g|^2) + alpha2,
+ * else 0; evaluated as (right side - left side) >= 0, which is the same decision for finite values, false for a NaN on either
+ * side and false where the sampled flow holds an Inf.  Direction b: the same with the roles of the flows and masks swapped.  A
+ * pixel its input mask rules out reads neither flow, an out-of-frame pixel no sample (selected, not multiplied).  alpha2 is in
+ * px^2 at the flows' resolution after flow_scale (UnFlow: alpha1 0.01, alpha2 0.5).  Sample point, weights, f + g and both
+ * sides are computed in double: the decision is a float64 restatement's except at true near-ties.
+ * valid_a, valid_b: uint8_t[N][H][W] out; valid_b NULL: only direction a is computed (counts_b must then be NULL too).
+ * counts_a, counts_b: int32_t[N] out, the number of 1s per image (exact; workgroup partials added in a fixed tree, then in index
+ * order: two calls give the same bits; no atomics); both may be NULL, and then no workspace is needed.  Otherwise workspace: at
+ * least pwc_fb_workspace_floats(N, H, W) floats.  One launch for both directions, plus one small launch (a thread per image) per count
+ * vector.  Checks, all before any launch: null flows or valid_a, N, H, W <= 0, a channel stride below 2, alpha1 or alpha2
+ * negative or NaN, counts_b without valid_b (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); counts asked with a null or
+ * short workspace (PWC_EINVAL). */
+size_t pwc_fb_workspace_floats(int N, int H, int W);
+int pwc_fb_valid_u8(const float* flow_a, int a_cs, const float* flow_b, int b_cs, float flow_scale,
+                    const uint8_t* valid_a_in, const uint8_t* valid_b_in, int N, int H, int W, float alpha1, float alpha2,
+                    uint8_t* valid_a, uint8_t* valid_b, int32_t* counts_a, int32_t* counts_b,
+                    float* workspace, size_t workspace_floats, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

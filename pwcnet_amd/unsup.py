@@ -8,6 +8,8 @@
     census_sums(images_0, images_1, flows, ...)        -> (sums (N,), counts (N,) int32)
     census_loss(...)                                    -> sums.sum() / counts.sum().clamp(min=1)
 
+    fb_valid(flows_fw, flows_bw, ...)                   -> (mask_fw, mask_bw) torch.bool (N,H,W) [, counts_fw, counts_bw int32 (N,)]
+
 With rho(d) = (d^2 + eps^2)^q: the photometric term of a pixel is sum_c rho(images_0 - bilinear sample of images_1 at the pixel
 moved by flow_scale * flow), over the pixels that are valid (`valid`, grad_ops.mask_ptr's format, e.g. an occlusion mask of the
 caller's) and whose sample point lies inside the frame; the smoothness term is the sum of exp(-alpha * mean_c |d image|) *
@@ -17,6 +19,8 @@ reproducible), so the losses compose with PWCDCNetModule; the images are constan
 The census term compares the local intensity ORDER in a (2 radius + 1)^2 window of the grey images instead of the intensities
 (csrc/pwc_census.hip; the formulas are in census_sums' docstring), so a brightness change between the frames does not pull the flow.
 No double backward.
+fb_valid makes the occlusion masks that go into `valid`: the forward-backward consistency check of two flows (csrc/pwc_fbcheck.hip;
+the definition is in its docstring).  It is not differentiable: the masks are constants.
 """
 import torch
 
@@ -315,3 +319,51 @@ def census_loss(images_0, images_1, flows, flow_scale=1.0, valid=None, radius=3,
     """0-dim: the mean of rho(h) over the contributing pixels; 0 when no pixel contributes."""
     sums, counts = census_sums(images_0, images_1, flows, flow_scale, valid, radius, scale, c1, c2, eps, q)
     return sums.sum() / counts.sum().clamp(min=1).to(torch.float32)
+
+
+def fb_valid(flows_fw, flows_bw, flow_scale=1.0, alpha1=0.01, alpha2=0.5, valid_fw=None, valid_bw=None, return_counts=False):
+    """(mask_fw, mask_bw), torch.bool (N,H,W), contiguous -- mask_ptr's format, they go straight into `valid=` of the data terms;
+    with return_counts also (counts_fw, counts_bw), int32 (N,): the number of True pixels per image (exact, bit reproducible).
+    flows_fw: the flow 0 -> 1, flows_bw: the flow 1 -> 0, both (N,H,W,2) float32 (channel slices of wider buffers are read in
+    place).  With f = flow_scale * flows_fw[p] and g = flow_scale * (flows_bw sampled bilinearly at p moved by f,
+    photometric_sums' sample), mask_fw[p] is True iff valid_fw[p] (where given) and the sample point is inside the frame and
+        |f + g|^2 <= alpha1 * (|f|^2 + |g|^2) + alpha2
+    (UnFlow's check and constants); a NaN or Inf anywhere in it gives False.  mask_bw: the same with the roles swapped.  A pixel
+    that valid_* rules out reads neither flow.  alpha2 is in px^2 at the flows' resolution AFTER flow_scale: flow_scale =
+    20 / 2^level takes the pyramid flows with the same alpha2 in that level's pixels.  Not differentiable -- the masks are
+    constants, as in UnFlow; flows that require grad are read detached.  With census_loss remember that `valid` selects the
+    CENTRES only: an occluded neighbour in a visible centre's window is still read."""
+    alpha1, alpha2 = float(alpha1), float(alpha2)
+    for name, v in (("alpha1", alpha1), ("alpha2", alpha2)):
+        if not v >= 0.0:
+            raise ValueError(f"fb_valid: {name} must be non-negative, got {v}")
+    _check_nhwc(flows_fw, "flows_fw", (2,))
+    _check_nhwc(flows_bw, "flows_bw", (2,))
+    if tuple(flows_bw.shape) != tuple(flows_fw.shape):
+        raise ValueError(f"flows_bw: expected (N,H,W) {tuple(flows_fw.shape[:3])}, flows_fw's, got {tuple(flows_bw.shape[:3])}")
+    N, H, W, _ = flows_fw.shape
+    if N <= 0 or H <= 0 or W <= 0:
+        raise ValueError(f"flows_fw: empty tensor, shape {tuple(flows_fw.shape)}")
+    vp_fw = None if valid_fw is None else mask_ptr(valid_fw, N, H, W, flows_fw.device)
+    vp_bw = None if valid_bw is None else mask_ptr(valid_bw, N, H, W, flows_fw.device)
+    _check_gpu(flows_fw, flows_bw=flows_bw)
+    fa, flows_fw = as_view(flows_fw.detach(), "flows_fw")
+    fb, flows_bw = as_view(flows_bw.detach(), "flows_bw")
+    L = _lib.lib()
+    dev = flows_fw.device
+    mask_fw = torch.empty((N, H, W), dtype=torch.bool, device=dev)
+    mask_bw = torch.empty((N, H, W), dtype=torch.bool, device=dev)
+    counts_fw = counts_bw = ws = None
+    if return_counts:
+        counts_fw = torch.empty((N,), dtype=torch.int32, device=dev)
+        counts_bw = torch.empty((N,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(L.pwc_fb_workspace_floats(N, H, W), 1),), dtype=torch.float32, device=dev)
+    _lib.check(L.pwc_fb_valid_u8(_p(fa.ptr), fa.cs, _p(fb.ptr), fb.cs, float(flow_scale), vp_fw, vp_bw, N, H, W, alpha1, alpha2,
+                                 _p(mask_fw.data_ptr()), _p(mask_bw.data_ptr()),
+                                 _p(counts_fw.data_ptr()) if return_counts else None,
+                                 _p(counts_bw.data_ptr()) if return_counts else None,
+                                 _p(ws.data_ptr()) if return_counts else None, ws.numel() if return_counts else 0,
+                                 _lib.current_stream()), "fb valid")
+    if return_counts:
+        return mask_fw, mask_bw, counts_fw, counts_bw
+    return mask_fw, mask_bw

@@ -20,6 +20,12 @@ smoothness_loss(flows_final, images_0) (pwcnet_amd/unsup.py: images_1 warped by 
 edge-aware first-order smoothness of the flow).  Ground truth, where the data set has it, is used for the validation line only.
 `--photo census` replaces the data term by census_loss(flows_final, radius=--census_radius): the soft census (ternary) term on the
 local intensity order, which a brightness change between the frames does not move.
+`--occlusion fb` leaves occluded pixels out of the data term: ONE module forward on the pairs in both orders stacked along the
+batch axis (batch 2N) gives the forward and the backward flow, fb_valid (pwcnet_amd/unsup.py; --occ_alpha1, --occ_alpha2, UnFlow's
+forward-backward check) turns them into two masks -- constants, no gradient goes through them -- and the loss is the data term
+in both directions, each under its mask, plus --smooth_weight * the smoothness of both flows, each against its own first image,
+the total halved so that --smooth_weight keeps its meaning.  The step line then also prints the occluded fraction.  Validation
+is unchanged (forward flow only).
 Single process, constant learning rate; --gamma is Adam's weight_decay (the same gamma * l2_loss gradient).
 
 Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
@@ -124,8 +130,17 @@ def validate(args, weights, ds, val_idx, dist=None):
 def train_unsup(args, ds, train_idx, val_idx):
     """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet."""
     from pwcnet_amd import PWCDCNetModule, ckpt
-    from pwcnet_amd.unsup import census_loss, photometric_loss, smoothness_loss
+    from pwcnet_amd.unsup import census_loss, fb_valid, photometric_loss, smoothness_loss
     term = "census" if args.photo == "census" else "photometric"
+
+    def data_term(i0, i1, flows, valid=None):
+        if args.photo == "census":
+            return census_loss(i0, i1, flows, valid=valid, radius=args.census_radius)
+        return photometric_loss(i0, i1, flows, valid=valid, eps=args.photo_eps, q=args.photo_q)
+
+    def smooth_term(flows, images):
+        return smoothness_loss(flows, images, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q)
+
     model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                            use_dc=args.use_dc, output_level=args.output_level)
     if args.resume is not None:
@@ -140,19 +155,30 @@ def train_unsup(args, ds, train_idx, val_idx):
         for images_0, images_1, _, _ in batches(ds, order[:steps * args.batch_size], args.batch_size):
             images_0, images_1 = (images_0 / 255.0).cuda(), (images_1 / 255.0).cuda()
             opt.zero_grad(set_to_none=True)
-            flows_final, _ = model(images_0, images_1)
-            if args.photo == "census":
-                photo = census_loss(images_0, images_1, flows_final, radius=args.census_radius)
+            if args.occlusion == "fb":
+                # both pair orders in one forward: the first N flows are 0 -> 1, the last N are 1 -> 0
+                N = images_0.shape[0]
+                flows_final, _ = model(torch.cat([images_0, images_1]), torch.cat([images_1, images_0]))
+                fw, bw = flows_final[:N], flows_final[N:]
+                with torch.no_grad():
+                    m_fw, m_bw, c_fw, c_bw = fb_valid(fw.detach(), bw.detach(), alpha1=args.occ_alpha1, alpha2=args.occ_alpha2,
+                                                      return_counts=True)
+                photo = 0.5 * (data_term(images_0, images_1, fw, m_fw) + data_term(images_1, images_0, bw, m_bw))
+                smooth = 0.5 * (smooth_term(fw, images_0) + smooth_term(bw, images_1))
+                occluded = 1.0 - float(c_fw.sum() + c_bw.sum()) / float(m_fw.numel() + m_bw.numel())
+                tail = f"  occluded {occluded:.4f}"
             else:
-                photo = photometric_loss(images_0, images_1, flows_final, eps=args.photo_eps, q=args.photo_q)
-            smooth = smoothness_loss(flows_final, images_0, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q)
+                flows_final, _ = model(images_0, images_1)
+                photo = data_term(images_0, images_1, flows_final)
+                smooth = smooth_term(flows_final, images_0)
+                tail = ""
             loss = photo + args.smooth_weight * smooth
             loss.backward()
             opt.step()
             global_step += 1
             n_steps += 1
             loss_sum += float(loss)
-            print(f"step {global_step}: loss/unsup {float(loss):.6f}  {term} {float(photo):.6f}  smoothness {float(smooth):.6f}")
+            print(f"step {global_step}: loss/unsup {float(loss):.6f}  {term} {float(photo):.6f}  smoothness {float(smooth):.6f}{tail}")
         res = validate(args, model.tf_state_dict(), ds, val_idx)
         dt = time.time() - t0
         print(f"epoch {e + 1}: loss/unsup {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
@@ -183,6 +209,12 @@ def main():
                     help="--loss unsup: the data term, Charbonnier on intensities or soft census on their local order [charbonnier]")
     ap.add_argument("--census_radius", type=int, default=3, choices=[1, 2, 3],
                     help="--photo census: window radius, (2r+1)^2 - 1 neighbours [3]")
+    ap.add_argument("--occlusion", default="none", choices=["none", "fb"],
+                    help="--loss unsup: none, or fb: forward-backward consistency masks on the data term, both directions "
+                         "trained from one forward at batch 2N [none]")
+    ap.add_argument("--occ_alpha1", type=float, default=0.01,
+                    help="--occlusion fb: |f + g|^2 <= alpha1 (|f|^2 + |g|^2) + alpha2 keeps a pixel [0.01]")
+    ap.add_argument("--occ_alpha2", type=float, default=0.5, help="--occlusion fb: alpha2 of that check, px^2 [0.5]")
     ap.add_argument("--smooth_weight", type=float, default=0.1, help="--loss unsup: weight of the smoothness term [0.1]")
     ap.add_argument("--photo_eps", type=float, default=1e-3, help="--loss unsup: Charbonnier epsilon of both terms [1e-3]")
     ap.add_argument("--photo_q", type=float, default=0.5, help="--loss unsup: Charbonnier exponent of both terms [0.5]")
@@ -212,6 +244,10 @@ def main():
         ap.error("--output_level must be in [0, num_levels)")
     if not 0.0 <= args.synthetic_invalid < 1.0:
         ap.error("--synthetic_invalid must be in [0, 1)")
+    if args.occlusion != "none" and args.loss != "unsup":
+        ap.error("--occlusion fb belongs to --loss unsup (the supervised losses have ground truth and its own mask)")
+    if not (args.occ_alpha1 >= 0 and args.occ_alpha2 >= 0):
+        ap.error("--occ_alpha1 and --occ_alpha2 must be non-negative")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
