@@ -642,6 +642,21 @@ int pwc_flow_smoothness_sums_f32(const float* flow, int flow_cs, const float* im
 int pwc_flow_smoothness_grad_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
                                  float eps, float q, int N, int H, int W, const float* dsums, float* dflow, int dflow_cs,
                                  int accumulate, pwc_stream_t stream);
+/* Smoothness term, second order (UnFlow's published configurations): the same parameters, checks and workspace
+ * (pwc_flow_smoothness_workspace_floats) as the first-order pair.  out_sums[n] = sum over the centres 1 <= x <= W - 2 of
+ * wxx(p) * sum_k rho(flow[n,y,x-1,k] - 2 flow[n,y,x,k] + flow[n,y,x+1,k]), wxx(p) = exp(-alpha * mean_c |image[n,y,x+1,c] -
+ * image[n,y,x-1,c]|) -- the stride-2 image difference centred on the same pixel -- plus the same along y for 1 <= y <= H - 2.
+ * A constant flow AND a constant slope cost nothing beyond rho(0).  W < 3: no x terms, H < 3: no y terms, both: the sum is 0, no
+ * error.  image NULL: every weight is 1 (a constant image gives the same bits).  The second difference is formed in double
+ * (exact for three fp32 values) and rounded to fp32 once. */
+int pwc_flow_smoothness2_sums_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
+                                  float eps, float q, int N, int H, int W, float* workspace, size_t workspace_floats,
+                                  float* out_sums, pwc_stream_t stream);
+/* dflow (+)= dsums[n] * d out_sums[n] / d flow: every lane gathers the up to six second differences its pixel takes part in --
+ * along each axis as the left neighbour, the centre (factor -2) and the right neighbour.  No atomics. */
+int pwc_flow_smoothness2_grad_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
+                                  float eps, float q, int N, int H, int W, const float* dsums, float* dflow, int dflow_cs,
+                                  int accumulate, pwc_stream_t stream);
 
 /* Soft census (ternary) term: the photometric term on the local intensity ORDER, invariant to additive and largely to
  * multiplicative brightness changes.  Grey planes a(p) = scale * mean_c images_0[p] and b(p) = scale * mean_c (the photometric
@@ -676,7 +691,7 @@ int pwc_census_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_
                         float c1, float c2, float eps, float q, const float* dsums, float* workspace,
                         size_t workspace_floats, float* dflow, int dflow_cs, int accumulate, pwc_stream_t stream);
 
-/* ==== occlusion: forward-backward consistency of two flows (the `valid` masks of the data terms above) ====
+/* ==== occlusion: forward-backward consistency of two flows (the `valid` masks of the data terms above, and the consistency term) ====
  * flow_a is the flow 0 -> 1, flow_b the flow 1 -> 0, both NHWC fp32 with 2 channels at channel strides a_cs, b_cs >= 2 (scalar
  * loads, no alignment asked).  For direction a, pixel p = (n, y, x): f = flow_scale * flow_a[p], (px, py) = (x + f0, y + f1);
  * the in-frame test 0 <= px <= W - 1, 0 <= py <= H - 1 (a NaN or Inf fails it) and the bilinear sample are the photometric
@@ -700,6 +715,47 @@ int pwc_fb_valid_u8(const float* flow_a, int a_cs, const float* flow_b, int b_cs
                     const uint8_t* valid_a_in, const uint8_t* valid_b_in, int N, int H, int W, float alpha1, float alpha2,
                     uint8_t* valid_a, uint8_t* valid_b, int32_t* counts_a, int32_t* counts_b,
                     float* workspace, size_t workspace_floats, pwc_stream_t stream);
+
+/* The consistency term (UnFlow's third): the same two flows, sample and in-frame test as pwc_fb_valid_u8, word for word.  For
+ * direction a, e = f + g (double, rounded to fp32 once); pixel p CONTRIBUTES iff (valid_a == NULL or valid_a[p] != 0) and its
+ * sample point is in frame (a NaN or Inf flow fails the test; a pixel its mask rules out reads no flow of its own direction):
+ *   sums_a[n] = sum over the contributing pixels of rho(e0) + rho(e1),  counts_a[n] = their number (exact),
+ * rho as in the self-supervised losses above.  Direction b: the roles swapped.  The masks are usually pwc_fb_valid_u8's outputs.
+ * One launch for both directions (workgroup partials in `workspace`, at least pwc_fb_consistency_workspace_floats(N, H, W)
+ * floats, added in a fixed tree), then one small launch per direction that adds the parts in index order: two calls give the
+ * same bits.  Checks, all before any launch: null flows, N, H, W <= 0, a channel stride below 2, eps <= 0, q outside (0, 1],
+ * a null output (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); a null or short workspace (PWC_EINVAL). */
+size_t pwc_fb_consistency_workspace_floats(int N, int H, int W);
+int pwc_fb_consistency_sums_f32(const float* flow_a, int a_cs, const float* flow_b, int b_cs, float flow_scale,
+                                const uint8_t* valid_a, const uint8_t* valid_b, int N, int H, int W, float eps, float q,
+                                float* workspace, size_t workspace_floats, float* sums_a, int32_t* counts_a,
+                                float* sums_b, int32_t* counts_b, pwc_stream_t stream);
+/* dflow_a, dflow_b (+)= the gradient of sum_n dsums_a[n] sums_a[n] + dsums_b[n] sums_b[n] with respect to flow_a and flow_b.
+ * The masks are constants; floor and clip carry no gradient.  A flow collects two parts.  GATHER, from its own direction's
+ * contributing pixels (f and the sample position):
+ *   dflow_a[p,j] = flow_scale * dsums_a[n] * sum_k rho'(e_k) * (delta_kj + flow_scale * d sample_k / d pos_j).
+ * SCATTER, from the other direction's contributing pixels that read one of its four corners:
+ *   dflow_a[corner,k] += flow_scale * dsums_b[n] * (corner weight) * rho'(e_k).
+ * Several pixels may share a corner, so the scatter adds (corner weight) * rho'(e_k) -- dsums and flow_scale are constant per
+ * image and direction and are factored out, exactly -- into 64-bit FIXED-POINT accumulators of 2^-36 steps in `workspace`:
+ * integer addition is associative, the result does not depend on the order in which the atomics land, two calls give the same
+ * bits.  The call zeroes the accumulators (one per pixel and channel of each flow, and one poison word per flow), one launch
+ * over the pixels of both directions scatters, and a finish launch over the pixels of both flows forms the pixel's gather part,
+ * converts its accumulators once, multiplies by flow_scale * dsums[n] and stores the sum of the two parts.
+ * RANGE of the fixed point: a contribution below 1.5e-11 vanishes; a contribution that is not finite or reaches 2^26, and a
+ * non-finite entry of the dsums that scales a flow's scatter part (dsums_b for dflow_a, dsums_a for dflow_b), raise that flow's
+ * poison word, and EVERY element of that dflow is then NaN; a cell whose sum reaches 2^61 (|sum| >= 2^25) is NaN.  A diverging
+ * step never comes out finite.  (A non-finite dsums reaches its own direction's gather part by plain arithmetic.)
+ * accumulate == 0: every pixel of both dflows is written, 0 where neither part reaches; accumulate != 0: the same values are
+ * added to what is there.  dsums_a, dsums_b: N floats on the device, no host synchronisation.  workspace: 8-byte aligned, at
+ * least pwc_fb_consistency_grad_workspace_bytes(N, H, W) bytes.  Checks as above, with null dsums or dflows and a dflow channel
+ * stride below 2 in place of the null outputs, and a misaligned workspace with the short one (PWC_EINVAL). */
+size_t pwc_fb_consistency_grad_workspace_bytes(int N, int H, int W);
+int pwc_fb_consistency_grad_f32(const float* flow_a, int a_cs, const float* flow_b, int b_cs, float flow_scale,
+                                const uint8_t* valid_a, const uint8_t* valid_b, int N, int H, int W, float eps, float q,
+                                const float* dsums_a, const float* dsums_b, void* workspace, size_t workspace_bytes,
+                                float* dflow_a, int dflow_a_cs, float* dflow_b, int dflow_b_cs, int accumulate,
+                                pwc_stream_t stream);
 
 #ifdef __cplusplus
 }

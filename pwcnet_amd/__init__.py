@@ -6,11 +6,12 @@ Python host classes over hand-written HIP kernels in csrc/ (C ABI: include/pwc_h
 from .model import PWCDCNet  # noqa: F401
 from .pipeline import ForwardPipeline  # noqa: F401
 from .autograd import PWCDCNetModule  # noqa: F401
-from .unsup import (census_grad, census_loss, census_sums, fb_valid, photometric_loss, photometric_sums,  # noqa: F401
-                    smoothness_loss, smoothness_sums)
+from .unsup import (census_grad, census_loss, census_sums, fb_consistency_grad, fb_consistency_loss,  # noqa: F401
+                    fb_consistency_sums, fb_valid, photometric_loss, photometric_sums, smoothness_loss, smoothness_sums)
 from .modules import (ContextNetwork, CostVolumeLayer, FeaturePyramidExtractor_custom,  # noqa: F401
                       OpticalFlowEstimator_custom, WarpingLayer, resize_bilinear)
 
 __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtractor_custom", "WarpingLayer", "CostVolumeLayer",
            "OpticalFlowEstimator_custom", "ContextNetwork", "resize_bilinear", "photometric_sums", "photometric_loss",
-           "smoothness_sums", "smoothness_loss", "census_sums", "census_loss", "census_grad", "fb_valid"]
+           "smoothness_sums", "smoothness_loss", "census_sums", "census_loss", "census_grad", "fb_valid",
+           "fb_consistency_sums", "fb_consistency_loss", "fb_consistency_grad"]

@@ -132,11 +132,17 @@ SIGNATURES = {
     "pwc_flow_smoothness_workspace_floats": (_sz, [_i, _i, _i]),
     "pwc_flow_smoothness_sums_f32": (_i, [_vp, _i, _vp, _i, _i, _f, _f, _f, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "pwc_flow_smoothness_grad_f32": (_i, [_vp, _i, _vp, _i, _i, _f, _f, _f, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "pwc_flow_smoothness2_sums_f32": (_i, [_vp, _i, _vp, _i, _i, _f, _f, _f, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "pwc_flow_smoothness2_grad_f32": (_i, [_vp, _i, _vp, _i, _i, _f, _f, _f, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "pwc_census_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "pwc_census_sums_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _sz, _vp, _vp, _vp]),
     "pwc_census_grad_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _sz, _vp, _i, _i, _vp]),
     "pwc_fb_workspace_floats": (_sz, [_i, _i, _i]),
     "pwc_fb_valid_u8": (_i, [_vp, _i, _vp, _i, _f, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pwc_fb_consistency_workspace_floats": (_sz, [_i, _i, _i]),
+    "pwc_fb_consistency_sums_f32": (_i, [_vp, _i, _vp, _i, _f, _vp, _vp, _i, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "pwc_fb_consistency_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pwc_fb_consistency_grad_f32": (_i, [_vp, _i, _vp, _i, _f, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp]),
 }
 
 if HARNESS:

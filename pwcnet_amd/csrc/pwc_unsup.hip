@@ -6,6 +6,8 @@
 //   pwc_photometric_grad_f32       the gradient of those sums w.r.t. the flow, times an upstream gradient per image
 //   pwc_flow_smoothness_sums_f32   per-image sums of w * rho(forward difference of the flow), w = exp(-alpha * mean_c |d image|)
 //   pwc_flow_smoothness_grad_f32   their gradient w.r.t. the flow
+//   pwc_flow_smoothness2_sums_f32  the same with the SECOND difference of the flow, weighted by the image difference across the
+//   pwc_flow_smoothness2_grad_f32  centre (end of the file)
 //
 // rho(d) = (d^2 + eps^2)^q (generalised Charbonnier), rho'(d) = 2 q d (d^2 + eps^2)^(q - 1).  The images are constants.
 // A pixel of the photometric term contributes iff it is valid and its sample point lies inside the frame; the others are
@@ -292,5 +294,99 @@ extern "C" int pwc_flow_smoothness_grad_f32(const float* flow, int flow_cs, cons
     a.flow_cs = flow_cs; a.image_cs = image_cs; a.dflow_cs = dflow_cs;
     a.N = N; a.H = H; a.W = W; a.C = C; a.alpha = alpha; a.eps2 = eps * eps; a.q = q; a.accumulate = accumulate;
     hipLaunchKernelGGL(flow_smoothness_grad_kernel, pwc_loss_grad_blocks(N, H, W), dim3(256), 0, (hipStream_t)stream, a);
+    return pwc_launch_status();
+}
+
+// ------------------------------------------------------------------ smoothness term, second order
+// Centre c of a second difference along an axis (step = 1 along x, W along y; the neighbours are c - step and c + step, the
+// caller keeps them inside the row / column): the weight and the two differences l - 2 c + r.  The three fp32 values add
+// exactly in double and the difference is rounded to fp32 once -- the flow's magnitude (hundreds of px where it leaves the
+// frame) does not reach rho' through a rounding of the difference.
+__device__ __forceinline__ float smooth2_diffs(const SmoothArgs& a, size_t c, size_t step, float& du, float& dv) {
+    const float* fc = a.flow + c * a.flow_cs;
+    const float* fl = fc - step * a.flow_cs;
+    const float* fr = fc + step * a.flow_cs;
+    du = (float)(((double)fl[0] - 2.0 * (double)fc[0]) + (double)fr[0]);
+    dv = (float)(((double)fl[1] - 2.0 * (double)fc[1]) + (double)fr[1]);
+    return smooth_weight(a, c - step, c + step);
+}
+
+__global__ __launch_bounds__(256) void flow_smoothness2_partial_kernel(const SmoothArgs a) {
+    const int n = blockIdx.y;
+    const int npix = a.H * a.W;
+    float s = 0.f;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
+        const int y = p / a.W, x = p - y * a.W;
+        const size_t pix = (size_t)n * npix + p;
+        float du, dv;
+        if (x > 0 && x < a.W - 1) {
+            const float w = smooth2_diffs(a, pix, 1, du, dv);
+            s += w * (unsup_rho(du, a.eps2, a.q) + unsup_rho(dv, a.eps2, a.q));
+        }
+        if (y > 0 && y < a.H - 1) {
+            const float w = smooth2_diffs(a, pix, (size_t)a.W, du, dv);
+            s += w * (unsup_rho(du, a.eps2, a.q) + unsup_rho(dv, a.eps2, a.q));
+        }
+    }
+    pwc_loss_write_part<false>(s, 0, a.partial, nullptr);
+}
+
+// gu, gv += factor * w * rho'(the second difference centred on c)
+__device__ __forceinline__ void smooth2_gather(const SmoothArgs& a, size_t c, size_t step, float factor, float& gu, float& gv) {
+    float du, dv;
+    const float w = factor * smooth2_diffs(a, c, step, du, dv);
+    gu += w * unsup_rho_grad(du, a.eps2, a.q);
+    gv += w * unsup_rho_grad(dv, a.eps2, a.q);
+}
+
+__global__ __launch_bounds__(256) void flow_smoothness2_grad_kernel(const SmoothArgs a) {
+    const long npix = (long)a.N * a.H * a.W;
+    for (long p = blockIdx.x * 256L + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+        const PwcLossPixel px = pwc_loss_pixel(p, a.H, a.W);
+        const int x = px.x, y = px.y;
+        const size_t c = (size_t)p, row = (size_t)a.W;
+        float gu = 0.f, gv = 0.f;
+        // the up to six second differences that touch this pixel: per axis it is the right neighbour of the centre before it,
+        // the centre itself (factor -2) and the left neighbour of the centre behind it; a centre keeps 1 from both borders
+        if (x >= 2) smooth2_gather(a, c - 1, 1, 1.f, gu, gv);
+        if (x >= 1 && x <= a.W - 2) smooth2_gather(a, c, 1, -2.f, gu, gv);
+        if (x <= a.W - 3) smooth2_gather(a, c + 1, 1, 1.f, gu, gv);
+        if (y >= 2) smooth2_gather(a, c - row, row, 1.f, gu, gv);
+        if (y >= 1 && y <= a.H - 2) smooth2_gather(a, c, row, -2.f, gu, gv);
+        if (y <= a.H - 3) smooth2_gather(a, c + row, row, 1.f, gu, gv);
+        const float up = a.dsums[px.n];
+        pwc_grad_store2(a.dflow + p * a.dflow_cs, a.accumulate, 1.f, pwc_mul_rounded(up, gu), pwc_mul_rounded(up, gv));
+    }
+}
+
+extern "C" int pwc_flow_smoothness2_sums_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
+                                             float eps, float q, int N, int H, int W, float* workspace, size_t workspace_floats,
+                                             float* out_sums, pwc_stream_t stream) {
+    int rc = smooth_check(flow, flow_cs, image, image_cs, C, alpha, eps, q, N, H, W);
+    if (rc == PWC_OK) rc = pwc_loss_sums_check(N, H, W, 1, workspace_floats);
+    if (rc != PWC_OK) return rc;
+    if (!workspace || !out_sums) return PWC_EINVAL;
+    const int parts = (int)pwc_loss_parts(H, W);
+    SmoothArgs a;
+    a.flow = flow; a.image = image; a.dsums = nullptr; a.dflow = nullptr; a.partial = workspace;
+    a.flow_cs = flow_cs; a.image_cs = image_cs; a.dflow_cs = 0;
+    a.N = N; a.H = H; a.W = W; a.C = C; a.alpha = alpha; a.eps2 = eps * eps; a.q = q; a.accumulate = 0;
+    hipLaunchKernelGGL(flow_smoothness2_partial_kernel, dim3((unsigned)parts, (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
+    pwc_loss_final_launch(workspace, parts, N, out_sums, nullptr, stream);
+    return pwc_launch_status();
+}
+
+extern "C" int pwc_flow_smoothness2_grad_f32(const float* flow, int flow_cs, const float* image, int image_cs, int C, float alpha,
+                                             float eps, float q, int N, int H, int W, const float* dsums, float* dflow,
+                                             int dflow_cs, int accumulate, pwc_stream_t stream) {
+    const int rc = smooth_check(flow, flow_cs, image, image_cs, C, alpha, eps, q, N, H, W);
+    if (rc != PWC_OK) return rc;
+    if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
+    if (!dsums || !dflow || dflow_cs < 2) return PWC_EINVAL;
+    SmoothArgs a;
+    a.flow = flow; a.image = image; a.dsums = dsums; a.dflow = dflow; a.partial = nullptr;
+    a.flow_cs = flow_cs; a.image_cs = image_cs; a.dflow_cs = dflow_cs;
+    a.N = N; a.H = H; a.W = W; a.C = C; a.alpha = alpha; a.eps2 = eps * eps; a.q = q; a.accumulate = accumulate;
+    hipLaunchKernelGGL(flow_smoothness2_grad_kernel, pwc_loss_grad_blocks(N, H, W), dim3(256), 0, (hipStream_t)stream, a);
     return pwc_launch_status();
 }

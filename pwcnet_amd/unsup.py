@@ -9,6 +9,8 @@
     census_loss(...)                                    -> sums.sum() / counts.sum().clamp(min=1)
 
     fb_valid(flows_fw, flows_bw, ...)                   -> (mask_fw, mask_bw) torch.bool (N,H,W) [, counts_fw, counts_bw int32 (N,)]
+    fb_consistency_sums(flows_fw, flows_bw, ...)        -> (sums_fw, counts_fw, sums_bw, counts_bw)
+    fb_consistency_loss(...)                            -> (sums_fw.sum() + sums_bw.sum()) / (2 * (counts_fw.sum() + counts_bw.sum()).clamp(min=1))
 
 With rho(d) = (d^2 + eps^2)^q: the photometric term of a pixel is sum_c rho(images_0 - bilinear sample of images_1 at the pixel
 moved by flow_scale * flow), over the pixels that are valid (`valid`, grad_ops.mask_ptr's format, e.g. an occlusion mask of the
@@ -21,6 +23,9 @@ The census term compares the local intensity ORDER in a (2 radius + 1)^2 window 
 No double backward.
 fb_valid makes the occlusion masks that go into `valid`: the forward-backward consistency check of two flows (csrc/pwc_fbcheck.hip;
 the definition is in its docstring).  It is not differentiable: the masks are constants.
+smoothness_*(order=2) penalises the SECOND difference of the flow (a constant slope is free), and fb_consistency_* is UnFlow's
+third term: rho of f + g, the quantity fb_valid thresholds, at the pixels the masks keep, differentiable with respect to BOTH
+flows (the gradient with respect to the sampled flow is a scatter, added in 64-bit fixed point: bit reproducible).
 """
 import torch
 
@@ -93,19 +98,27 @@ def photometric_grad(images_0, images_1, flows, dsums, dflow=None, flow_scale=1.
     return dflow
 
 
-def smoothness_grad(flows, dsums, dflow=None, images=None, alpha=10.0, eps=1e-3, q=0.5, accumulate=False):
-    """dflow (+)= the gradient of (dsums * smoothness_sums(...)).sum() w.r.t. flows (pwc_flow_smoothness_grad_f32)."""
+def _check_order(order, what):
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"{what}: order must be 1 or 2, got {order!r}")
+    return int(order)
+
+
+def smoothness_grad(flows, dsums, dflow=None, images=None, alpha=10.0, eps=1e-3, q=0.5, accumulate=False, order=1):
+    """dflow (+)= the gradient of (dsums * smoothness_sums(...)).sum() w.r.t. flows (pwc_flow_smoothness_grad_f32, order 2:
+    pwc_flow_smoothness2_grad_f32)."""
+    order = _check_order(order, "smoothness_grad")
     fv, flows = as_view(flows, "flows")
     iv = None
     if images is not None:
         iv, images = as_view(images, "images")
     up = torch.empty((fv.N,), dtype=torch.float32, device=flows.device).copy_(dsums)
     dv, dflow = _dflow_view(dflow, fv, flows.device)
-    _lib.check(_lib.lib().pwc_flow_smoothness_grad_f32(_p(fv.ptr), fv.cs, _p(iv.ptr) if iv is not None else None,
-                                                       iv.cs if iv is not None else 0, iv.C if iv is not None else 0,
-                                                       float(alpha), float(eps), float(q), fv.N, fv.H, fv.W,
-                                                       _p(up.data_ptr()), _p(dv.ptr), dv.cs, 1 if accumulate else 0,
-                                                       _lib.current_stream()), "flow smoothness grad")
+    L = _lib.lib()
+    entry = L.pwc_flow_smoothness_grad_f32 if order == 1 else L.pwc_flow_smoothness2_grad_f32
+    _lib.check(entry(_p(fv.ptr), fv.cs, _p(iv.ptr) if iv is not None else None, iv.cs if iv is not None else 0,
+                     iv.C if iv is not None else 0, float(alpha), float(eps), float(q), fv.N, fv.H, fv.W, _p(up.data_ptr()),
+                     _p(dv.ptr), dv.cs, 1 if accumulate else 0, _lib.current_stream()), "flow smoothness grad")
     return dflow
 
 
@@ -220,7 +233,7 @@ class _PhotometricSums(torch.autograd.Function):
 
 class _SmoothnessSums(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, flows, images, alpha, eps, q):
+    def forward(ctx, flows, images, alpha, eps, q, order=1):
         ctx.set_materialize_grads(False)
         fv, flows = as_view(flows, "flows")
         iv = None
@@ -230,25 +243,26 @@ class _SmoothnessSums(torch.autograd.Function):
         dev = flows.device
         sums = torch.empty((fv.N,), dtype=torch.float32, device=dev)
         ws = torch.empty((max(L.pwc_flow_smoothness_workspace_floats(fv.N, fv.H, fv.W), 1),), dtype=torch.float32, device=dev)
-        _lib.check(L.pwc_flow_smoothness_sums_f32(_p(fv.ptr), fv.cs, _p(iv.ptr) if iv is not None else None,
-                                                  iv.cs if iv is not None else 0, iv.C if iv is not None else 0, alpha, eps, q,
-                                                  fv.N, fv.H, fv.W, _p(ws.data_ptr()), ws.numel(), _p(sums.data_ptr()),
-                                                  _lib.current_stream()), "flow smoothness sums")
+        entry = L.pwc_flow_smoothness_sums_f32 if order == 1 else L.pwc_flow_smoothness2_sums_f32
+        _lib.check(entry(_p(fv.ptr), fv.cs, _p(iv.ptr) if iv is not None else None, iv.cs if iv is not None else 0,
+                         iv.C if iv is not None else 0, alpha, eps, q, fv.N, fv.H, fv.W, _p(ws.data_ptr()), ws.numel(),
+                         _p(sums.data_ptr()), _lib.current_stream()), "flow smoothness sums")
         if images is None:
             ctx.save_for_backward(flows)
         else:
             ctx.save_for_backward(flows, images)
-        ctx.consts = (alpha, eps, q)
+        ctx.consts = (alpha, eps, q, order)
         return sums
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dsums):
         if dsums is None or not ctx.needs_input_grad[0]:
-            return (None,) * 5
+            return (None,) * 6
         flows, *images = ctx.saved_tensors
-        alpha, eps, q = ctx.consts
-        return smoothness_grad(flows, dsums, None, images[0] if images else None, alpha, eps, q), None, None, None, None
+        alpha, eps, q, order = ctx.consts
+        dflow = smoothness_grad(flows, dsums, None, images[0] if images else None, alpha, eps, q, order=order)
+        return dflow, None, None, None, None, None
 
 
 def photometric_sums(images_0, images_1, flows, flow_scale=1.0, valid=None, eps=1e-3, q=0.5):
@@ -275,11 +289,15 @@ def photometric_loss(images_0, images_1, flows, flow_scale=1.0, valid=None, eps=
     return sums.sum() / (images_0.shape[3] * counts.sum().clamp(min=1)).to(torch.float32)
 
 
-def smoothness_sums(flows, images=None, alpha=10.0, eps=1e-3, q=0.5):
+def smoothness_sums(flows, images=None, alpha=10.0, eps=1e-3, q=0.5, order=1):
     """sums (N,) float32: per image, sum over x < W - 1 of exp(-alpha * mean_c |images[y,x+1] - images[y,x]|) * sum_k
     rho(flows[y,x+1,k] - flows[y,x,k]) plus the same along y.  images: (N,H,W,C), C = 1..4, at the flows' resolution, a
-    constant; None: every weight is 1.  Differentiable w.r.t. flows."""
+    constant; None: every weight is 1.  Differentiable w.r.t. flows.
+    order=2 (UnFlow's second-order smoothness): sum over the centres 1 <= x <= W - 2 of exp(-alpha * mean_c |images[y,x+1] -
+    images[y,x-1]|) * sum_k rho(flows[y,x-1,k] - 2 flows[y,x,k] + flows[y,x+1,k]) plus the same along y -- a constant slope of
+    the flow is free.  W < 3 gives no x terms, H < 3 no y terms (both: 0).  Any other order: ValueError."""
     eps, q = _check_rho(eps, q, "smoothness_sums")
+    order = _check_order(order, "smoothness_sums")
     alpha = float(alpha)
     if not alpha >= 0.0:
         raise ValueError(f"smoothness_sums: alpha must be non-negative, got {alpha}")
@@ -288,12 +306,12 @@ def smoothness_sums(flows, images=None, alpha=10.0, eps=1e-3, q=0.5):
         _check_image(images, "images", flows)
         _check_gpu(flows, images=images)
     _check_gpu(flows)
-    return _SmoothnessSums.apply(flows, images, alpha, eps, q)
+    return _SmoothnessSums.apply(flows, images, alpha, eps, q, order)
 
 
-def smoothness_loss(flows, images=None, alpha=10.0, eps=1e-3, q=0.5):
-    """0-dim: smoothness_sums(...).sum() / (N * H * W)."""
-    sums = smoothness_sums(flows, images, alpha, eps, q)
+def smoothness_loss(flows, images=None, alpha=10.0, eps=1e-3, q=0.5, order=1):
+    """0-dim: smoothness_sums(...).sum() / (N * H * W), for both orders."""
+    sums = smoothness_sums(flows, images, alpha, eps, q, order)
     return sums.sum() / float(flows.shape[0] * flows.shape[1] * flows.shape[2])
 
 
@@ -367,3 +385,106 @@ def fb_valid(flows_fw, flows_bw, flow_scale=1.0, alpha1=0.01, alpha2=0.5, valid_
     if return_counts:
         return mask_fw, mask_bw, counts_fw, counts_bw
     return mask_fw, mask_bw
+
+
+def _check_fb_pair(flows_fw, flows_bw, valid_fw, valid_bw):
+    """fb_valid's tensor checks; the masks' addresses."""
+    _check_nhwc(flows_fw, "flows_fw", (2,))
+    _check_nhwc(flows_bw, "flows_bw", (2,))
+    if tuple(flows_bw.shape) != tuple(flows_fw.shape):
+        raise ValueError(f"flows_bw: expected (N,H,W) {tuple(flows_fw.shape[:3])}, flows_fw's, got {tuple(flows_bw.shape[:3])}")
+    N, H, W, _ = flows_fw.shape
+    if N <= 0 or H <= 0 or W <= 0:
+        raise ValueError(f"flows_fw: empty tensor, shape {tuple(flows_fw.shape)}")
+    vp_fw = None if valid_fw is None else mask_ptr(valid_fw, N, H, W, flows_fw.device)
+    vp_bw = None if valid_bw is None else mask_ptr(valid_bw, N, H, W, flows_fw.device)
+    _check_gpu(flows_fw, flows_bw=flows_bw)
+    return vp_fw, vp_bw
+
+
+def _upstream(dsums, N, dev):
+    """The upstream gradient of a direction as N contiguous float32 of its own; None (the sums were not used): zeros."""
+    if dsums is None:
+        return torch.zeros((N,), dtype=torch.float32, device=dev)
+    return torch.empty((N,), dtype=torch.float32, device=dev).copy_(dsums)
+
+
+def fb_consistency_grad(flows_fw, flows_bw, dsums_fw, dsums_bw, dflow_fw=None, dflow_bw=None, flow_scale=1.0, valid_fw=None,
+                        valid_bw=None, eps=1e-3, q=0.5, accumulate=False):
+    """(dflow_fw, dflow_bw) (+)= the gradient of (dsums_fw * sums_fw).sum() + (dsums_bw * sums_bw).sum() of
+    fb_consistency_sums(...) w.r.t. flows_fw and flows_bw (pwc_fb_consistency_grad_f32); dsums_*: (N,) on the GPU.  dflow_* None:
+    new tensors; accumulate: added onto them (without it every pixel is written, 0 where nothing reaches it).  Bit reproducible;
+    a contribution outside the fixed point's range or a non-finite dsums makes the dflow it reaches all NaN (include/pwc_hip.h).
+    What the autograd backward of fb_consistency_sums calls."""
+    eps, q = _check_rho(eps, q, "fb_consistency_grad")
+    vp_fw, vp_bw = _check_fb_pair(flows_fw, flows_bw, valid_fw, valid_bw)
+    fa, flows_fw = as_view(flows_fw.detach(), "flows_fw")
+    fb, flows_bw = as_view(flows_bw.detach(), "flows_bw")
+    L = _lib.lib()
+    dev = flows_fw.device
+    up_fw, up_bw = _upstream(dsums_fw, fa.N, dev), _upstream(dsums_bw, fa.N, dev)
+    da, dflow_fw = _dflow_view(dflow_fw, fa, dev)
+    db, dflow_bw = _dflow_view(dflow_bw, fa, dev)
+    ws = torch.empty((L.pwc_fb_consistency_grad_workspace_bytes(fa.N, fa.H, fa.W) // 8,), dtype=torch.int64, device=dev)
+    _lib.check(L.pwc_fb_consistency_grad_f32(_p(fa.ptr), fa.cs, _p(fb.ptr), fb.cs, float(flow_scale), vp_fw, vp_bw, fa.N, fa.H,
+                                             fa.W, eps, q, _p(up_fw.data_ptr()), _p(up_bw.data_ptr()), _p(ws.data_ptr()),
+                                             8 * ws.numel(), _p(da.ptr), da.cs, _p(db.ptr), db.cs, 1 if accumulate else 0,
+                                             _lib.current_stream()), "fb consistency grad")
+    return dflow_fw, dflow_bw
+
+
+class _FbConsistencySums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows_fw, flows_bw, flow_scale, valid_fw, valid_bw, eps, q):
+        ctx.set_materialize_grads(False)
+        N, H, W, _ = flows_fw.shape
+        vp_fw = None if valid_fw is None else mask_ptr(valid_fw, N, H, W, flows_fw.device)
+        vp_bw = None if valid_bw is None else mask_ptr(valid_bw, N, H, W, flows_fw.device)
+        fa, flows_fw = as_view(flows_fw, "flows_fw")
+        fb, flows_bw = as_view(flows_bw, "flows_bw")
+        L = _lib.lib()
+        dev = flows_fw.device
+        sums_fw, sums_bw = (torch.empty((N,), dtype=torch.float32, device=dev) for _ in range(2))
+        counts_fw, counts_bw = (torch.empty((N,), dtype=torch.int32, device=dev) for _ in range(2))
+        ws = torch.empty((max(L.pwc_fb_consistency_workspace_floats(N, H, W), 1),), dtype=torch.float32, device=dev)
+        _lib.check(L.pwc_fb_consistency_sums_f32(_p(fa.ptr), fa.cs, _p(fb.ptr), fb.cs, flow_scale, vp_fw, vp_bw, N, H, W, eps, q,
+                                                 _p(ws.data_ptr()), ws.numel(), _p(sums_fw.data_ptr()), _p(counts_fw.data_ptr()),
+                                                 _p(sums_bw.data_ptr()), _p(counts_bw.data_ptr()), _lib.current_stream()),
+                   "fb consistency sums")
+        ctx.save_for_backward(flows_fw, flows_bw)
+        ctx.valid, ctx.consts = (valid_fw, valid_bw), (flow_scale, eps, q)
+        ctx.mark_non_differentiable(counts_fw, counts_bw)
+        return sums_fw, counts_fw, sums_bw, counts_bw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dsums_fw, _dcounts_fw, dsums_bw, _dcounts_bw):
+        if (dsums_fw is None and dsums_bw is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 7
+        flows_fw, flows_bw = ctx.saved_tensors
+        flow_scale, eps, q = ctx.consts
+        dflow_fw, dflow_bw = fb_consistency_grad(flows_fw, flows_bw, dsums_fw, dsums_bw, None, None, flow_scale, ctx.valid[0],
+                                                 ctx.valid[1], eps, q)
+        return (dflow_fw if ctx.needs_input_grad[0] else None, dflow_bw if ctx.needs_input_grad[1] else None, None, None, None,
+                None, None)
+
+
+def fb_consistency_sums(flows_fw, flows_bw, flow_scale=1.0, valid_fw=None, valid_bw=None, eps=1e-3, q=0.5):
+    """(sums_fw (N,) float32, counts_fw (N,) int32, sums_bw, counts_bw): UnFlow's forward-backward consistency term.  With f =
+    flow_scale * flows_fw[p] and g = flow_scale * (flows_bw sampled bilinearly at p moved by f) -- fb_valid's f and g -- pixel p
+    contributes to the forward direction iff valid_fw[p] (where given; usually fb_valid's mask_fw) and its sample point is inside
+    the frame, and
+        sums_fw[n] = sum over the contributing pixels of rho(f0 + g0) + rho(f1 + g1),  rho(d) = (d^2 + eps^2)^q,
+    counts_fw[n] their number (exact).  The backward direction: the same with the roles swapped.  A pixel its mask rules out
+    reads no flow of its own direction.  Both sums are differentiable with respect to BOTH flows (pwc_fb_consistency_grad_f32:
+    a flow is reached where it stands and at the corners the other direction samples; bit reproducible); the masks are
+    constants and the counts carry no gradient.  No double backward."""
+    eps, q = _check_rho(eps, q, "fb_consistency_sums")
+    _check_fb_pair(flows_fw, flows_bw, valid_fw, valid_bw)
+    return _FbConsistencySums.apply(flows_fw, flows_bw, float(flow_scale), valid_fw, valid_bw, eps, q)
+
+
+def fb_consistency_loss(flows_fw, flows_bw, flow_scale=1.0, valid_fw=None, valid_bw=None, eps=1e-3, q=0.5):
+    """0-dim: the mean of rho over the contributing pixels of both directions and the two components; 0 when none contributes."""
+    sums_fw, counts_fw, sums_bw, counts_bw = fb_consistency_sums(flows_fw, flows_bw, flow_scale, valid_fw, valid_bw, eps, q)
+    return (sums_fw.sum() + sums_bw.sum()) / (2 * (counts_fw.sum() + counts_bw.sum()).clamp(min=1)).to(torch.float32)

@@ -26,6 +26,10 @@ forward-backward check) turns them into two masks -- constants, no gradient goes
 in both directions, each under its mask, plus --smooth_weight * the smoothness of both flows, each against its own first image,
 the total halved so that --smooth_weight keeps its meaning.  The step line then also prints the occluded fraction.  Validation
 is unchanged (forward flow only).
+`--smooth_order 2` penalises the second difference of the flow instead of the first (smoothness_loss(order=2): a constant slope
+is free), and `--consistency_weight W` (with --occlusion fb) adds W * fb_consistency_loss(fw, bw) under the two masks: UnFlow's
+third term, rho of the forward flow plus the backward flow sampled where it points to, with gradients into both flows; the step
+line then ends in `consistency <value>`.  Together with --photo census this is UnFlow's loss.
 Single process, constant learning rate; --gamma is Adam's weight_decay (the same gamma * l2_loss gradient).
 
 Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
@@ -130,7 +134,7 @@ def validate(args, weights, ds, val_idx, dist=None):
 def train_unsup(args, ds, train_idx, val_idx):
     """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet."""
     from pwcnet_amd import PWCDCNetModule, ckpt
-    from pwcnet_amd.unsup import census_loss, fb_valid, photometric_loss, smoothness_loss
+    from pwcnet_amd.unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss
     term = "census" if args.photo == "census" else "photometric"
 
     def data_term(i0, i1, flows, valid=None):
@@ -139,7 +143,7 @@ def train_unsup(args, ds, train_idx, val_idx):
         return photometric_loss(i0, i1, flows, valid=valid, eps=args.photo_eps, q=args.photo_q)
 
     def smooth_term(flows, images):
-        return smoothness_loss(flows, images, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q)
+        return smoothness_loss(flows, images, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q, order=args.smooth_order)
 
     model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                            use_dc=args.use_dc, output_level=args.output_level)
@@ -167,12 +171,17 @@ def train_unsup(args, ds, train_idx, val_idx):
                 smooth = 0.5 * (smooth_term(fw, images_0) + smooth_term(bw, images_1))
                 occluded = 1.0 - float(c_fw.sum() + c_bw.sum()) / float(m_fw.numel() + m_bw.numel())
                 tail = f"  occluded {occluded:.4f}"
+                if args.consistency_weight > 0:
+                    consistency = fb_consistency_loss(fw, bw, valid_fw=m_fw, valid_bw=m_bw, eps=args.photo_eps, q=args.photo_q)
             else:
                 flows_final, _ = model(images_0, images_1)
                 photo = data_term(images_0, images_1, flows_final)
                 smooth = smooth_term(flows_final, images_0)
                 tail = ""
             loss = photo + args.smooth_weight * smooth
+            if args.consistency_weight > 0:
+                loss = loss + args.consistency_weight * consistency
+                tail += f"  consistency {float(consistency.detach()):.6f}"
             loss.backward()
             opt.step()
             global_step += 1
@@ -216,6 +225,10 @@ def main():
                     help="--occlusion fb: |f + g|^2 <= alpha1 (|f|^2 + |g|^2) + alpha2 keeps a pixel [0.01]")
     ap.add_argument("--occ_alpha2", type=float, default=0.5, help="--occlusion fb: alpha2 of that check, px^2 [0.5]")
     ap.add_argument("--smooth_weight", type=float, default=0.1, help="--loss unsup: weight of the smoothness term [0.1]")
+    ap.add_argument("--smooth_order", type=int, default=1, choices=[1, 2],
+                    help="--loss unsup: the smoothness term penalises the first or the second difference of the flow [1]")
+    ap.add_argument("--consistency_weight", type=float, default=0.0,
+                    help="--occlusion fb: weight of the forward-backward consistency term, gradients into both flows [0]")
     ap.add_argument("--photo_eps", type=float, default=1e-3, help="--loss unsup: Charbonnier epsilon of both terms [1e-3]")
     ap.add_argument("--photo_q", type=float, default=0.5, help="--loss unsup: Charbonnier exponent of both terms [0.5]")
     ap.add_argument("--edge_alpha", type=float, default=10.0,
@@ -248,6 +261,12 @@ def main():
         ap.error("--occlusion fb belongs to --loss unsup (the supervised losses have ground truth and its own mask)")
     if not (args.occ_alpha1 >= 0 and args.occ_alpha2 >= 0):
         ap.error("--occ_alpha1 and --occ_alpha2 must be non-negative")
+    if not args.consistency_weight >= 0:
+        ap.error("--consistency_weight must be non-negative")
+    if args.consistency_weight > 0 and args.occlusion != "fb":
+        ap.error("--consistency_weight needs --occlusion fb (the term reads the forward and the backward flow of one forward)")
+    if args.smooth_order != 1 and args.loss != "unsup":
+        ap.error("--smooth_order belongs to --loss unsup")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
