@@ -347,7 +347,9 @@ int pwc_conv3x3_c3c16pair_supported(int N, int H0, int W0);
  * from the pixels of its plane, and four of a stage's nine tap slots carry matrix instructions -- 16 Cin products per output
  * (a strided convolution needs 9 Cin; round 4's "stride-1 launch storing every second sum" executed 36 Cin and lost to the fp32
  * kernel).  y is (N, H / 2, W / 2) at channel stride y_cs.  packed_w: pwc_conv3x3_h2_stride2_pack_f32 (same arguments as
- * pwc_conv3x3_h2_pack_f32: cin_map over the input's Cin_phys physical channels; pwc_conv3x3_h2_stride2_packed_floats floats);
+ * pwc_conv3x3_h2_pack_f32: cin_map over the input's Cin_phys physical channels; pwc_conv3x3_h2_stride2_packed_floats floats:
+ * the parity-plane image and, for Cin_phys % 32 == 0 and Cout % 16 == 0, behind it the pwc_conv3x3_sk_pack_f32 image that the
+ * strided tile kernel of csrc/conv3x3_s2.hip reads -- the entry point runs 32-channel inputs with Cout <= 128 on that kernel);
  * workspace: pwc_conv3x3_h2_stride2_workspace_floats (0: none), rules of pwc_conv3x3_h2_f32; status: the caller's status words
  * (or NULL), as pwc_conv3x3_h2_ex_f32's (PWC_STATUS_STREAMK_TIMEOUT).  Odd sizes: PWC_EUNSUPPORTED
  * (pwc_conv3x3_f32 takes them).  _supported: 1 where it is the faster kernel: inputs of up to 32 channels whose output is a
@@ -379,7 +381,9 @@ int pwc_conv3x3_h2_stride2_supported(int N, int H, int W, int Cin_phys, int Cout
  * pwc_conv3x3_sk_variant_f32: the same convolution with the workgroup tile and form GIVEN -- tile in {11, 21, 22} (fragments from
  * global memory), {31, 41, 42} (patch in the LDS) -- for tests and tuning (every tile gives the same result on every shape it
  * admits; PWC_EUNSUPPORTED where it does not: x2 tiles need Cout % 32 == 0, 3x / 4x no dilation and at most 288 (stride 2: 128)
- * input channels).  The tile is an argument of the call: the library keeps no process-wide setting. */
+ * input channels; tile 50: the strided tile kernel of csrc/conv3x3_s2.hip -- stride 2, no dilation, Cout <= 128 -- which
+ * pwc_conv3x3_sk_f32 itself launches for stride-2 layers of 192 or more 4 x 32-pixel output tiles).  The tile is an argument of
+ * the call: the library keeps no process-wide setting. */
 size_t pwc_conv3x3_sk_packed_floats(int Cin_phys, int Cout);
 int pwc_conv3x3_sk_pack_f32(const float* w_hwio, const int32_t* cin_map, int Cin, int Cin_phys, int Cout,
                             float* packed_w, pwc_stream_t stream);

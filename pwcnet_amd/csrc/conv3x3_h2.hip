@@ -687,8 +687,15 @@ extern "C" int pwc_conv3x3_h2_pack_f32(const float* w_hwio, const int32_t* cin_m
 }
 
 // Weights of the stride-2 form (pwc_conv3x3_h2_stride2_f32): Cin_phys = the input's physical channels (cin_map over them).
+// Two images: the parity-plane one of the S2 form, and behind it (where the strided tile kernel of conv3x3_s2.hip takes the
+// channel counts) the same weights in the pwc_conv3x3_sk_pack_f32 layout, which that kernel reads.
+static inline bool h2s2_has_tile_image(int Cin_phys, int Cout) { return Cin_phys > 0 && Cout > 0 && !(Cin_phys % 32) && !(Cout % 16); }
+static inline size_t h2s2_tile_image_offset(int Cin_phys, int Cout) {
+    return (pwc_conv3x3_h2_packed_floats(4 * Cin_phys, Cout) + 3) & ~(size_t)3;
+}
 extern "C" size_t pwc_conv3x3_h2_stride2_packed_floats(int Cin_phys, int Cout) {
-    return pwc_conv3x3_h2_packed_floats(4 * Cin_phys, Cout);
+    if (!h2s2_has_tile_image(Cin_phys, Cout)) return pwc_conv3x3_h2_packed_floats(4 * Cin_phys, Cout);
+    return h2s2_tile_image_offset(Cin_phys, Cout) + pwc_conv3x3_sk_packed_floats(Cin_phys, Cout);
 }
 extern "C" int pwc_conv3x3_h2_stride2_pack_f32(const float* w_hwio, const int32_t* cin_map, int Cin, int Cin_phys,
                                                int Cout, float* packed, pwc_stream_t stream) {
@@ -700,7 +707,9 @@ extern "C" int pwc_conv3x3_h2_stride2_pack_f32(const float* w_hwio, const int32_
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(conv3x3_h2_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_hwio, cin_map,
                        Cin, 4 * Cin_phys, Cout, nct, reinterpret_cast<unsigned short*>(packed), 1);
-    return pwc_launch_status();
+    if (const int rc = pwc_launch_status()) return rc;
+    if (!h2s2_has_tile_image(Cin_phys, Cout)) return PWC_OK;
+    return pwc_conv3x3_sk_pack_f32(w_hwio, cin_map, Cin, Cin_phys, Cout, packed + h2s2_tile_image_offset(Cin_phys, Cout), stream);
 }
 
 // ---------------------------------------------------------------- tile variants and the launch plan
@@ -813,6 +822,19 @@ static int h2_launch(H2Args& a, int hs, int ws, float* workspace, size_t workspa
     return pwc_launch_status();
 }
 
+// The stride-2 launches that go to the strided tile kernel of conv3x3_s2.hip instead of the parity-plane form: 32 input channels
+// (the form's 8 stages cost their fixed 5 - 6 us each at ANY size).  Measured back to back, us, strided tile kernel against the S2
+// form (profiles/s2tile_exp_ab.txt), 32 -> 64: 112 x 256 of 16 / 18 / 64 / 2 images 29.7 / 30.2 / 100.4 / 8.4 against 39.8 / 47.8 /
+// 132.5 / 19.5; 16 x 64 of 2 images (4 tiles) 7.8 against 18.9.  Neither the workspace nor the status words are touched by that
+// kernel: it has no stream-K exchange.
+static bool h2s2_tile_routed(int N, int H, int W, int x_cs, int Cin_phys, int Cout) {
+    const bool ok = h2s2_has_tile_image(Cin_phys, Cout) && pwc_conv3x3_s2_tile_admits(N, H, W, x_cs, Cin_phys, Cout);
+#ifdef PWC_HARNESS
+    if (pwc_conv3x3_s2_tile_debug_mode()) return ok && pwc_conv3x3_s2_tile_debug_mode() > 0;
+#endif
+    return ok && Cin_phys == 32;
+}
+
 // variant 0 = h2_plan's choice
 template <int ABL = 0>
 static int h2_run(const float* x, int x_cs, const float* packed_w, const float* bias, float* y, int y_cs, int N, int H, int W,
@@ -859,6 +881,9 @@ static int h2_run(const float* x, int x_cs, const float* packed_w, const float* 
     if (variant == 0) variant = h2_plan(N, a.Ho, a.Wo, a.Cin_phys, Cout, dilation, nullptr);
     if (variant < 1 || variant > 5) return PWC_EUNSUPPORTED;
     if (Cout % h2_variant(variant).couts) return PWC_EUNSUPPORTED;
+    if (s2 && h2s2_tile_routed(N, H, W, x_cs, Cin_phys, Cout))
+        return pwc_conv3x3_s2_tile_launch(x, x_cs, packed_w + h2s2_tile_image_offset(Cin_phys, Cout), bias, y, y_cs, N, H, W, Cin_phys,
+                                          Cout, apply_act, slope, stream);
     if (s2) {
         switch (variant) {
             case 1: return h2_launch<2, 2, 2, ABL, 1, true>(a, hs, ws, workspace, workspace_floats, (hipStream_t)stream);
@@ -935,7 +960,10 @@ extern "C" int pwc_conv3x3_h2_ex3_f32(const float* x, int x_cs, int Cin_a_phys, 
 //     64 -> 96 at  56 x 128: 49.4 - 50.3 / 42.9     96 -> 128 at 28 x 64:  31.7 - 32.2 / 30.5
 // A stage carries 4 taps of matrix instructions instead of 9 and costs its fixed 5 - 6 us all the same (three parts, each waiting
 // for weights that were requested one -- now nearly empty -- part earlier): with 4 C / 16 stages per tile the form pays only while
-// the channel loop is short.  So: inputs of up to 32 channels.
+// the channel loop is short.  So: inputs of up to 32 channels -- as the answer of _supported, which callers route by.  Of those,
+// the entry point runs 32-channel inputs (C_out <= 128) on the strided tile kernel of conv3x3_s2.hip, nine real taps and no stages
+// (h2s2_tile_routed): 32 -> 64 at 112 x 256 of 16 images 29.7 us against 39.8 back to back.  16-channel inputs and whatever that
+// kernel does not take stay on the S2 form.
 extern "C" int pwc_conv3x3_h2_stride2_supported(int N, int H, int W, int Cin_phys, int Cout) {
     if (H <= 0 || W <= 0 || (H & 1) || (W & 1) || Cin_phys % 16 || Cin_phys > 32) return 0;
     return pwc_conv3x3_h2_supported(N, H / 2, W / 2, 4 * Cin_phys, Cout, 1);

@@ -378,13 +378,23 @@ extern "C" int pwc_conv3x3_sk_pack_f32(const float* w_hwio, const int32_t* cin_m
 // pixels) it is level with the Winograd kernels in the forward (33.8 / 28.2 / 17.6 against 31.8 / 29.9 / 17.1 us) and loses on
 // the widest layer (28 x 64 x 224 -> 128: 48.9 against 33.4 on conv3x3_h2_kernel): every workgroup fetches its tile's weights on
 // its own, and that traffic grows with the pixel count while the tiled kernels' does not.  With fragments straight from global
-// memory (stride 2, dilation): up to 1e8 multiply-adds and 4096 output pixels, beyond that pixel count the stride-2 layers
-// (the tiled stride-2 path is the fp32 one: 25.5 against 29.7 at 28 x 64 x 96 -> 128 / 2) and thin layers.
+// memory (dilation; stride 2 below 64 or above 128 input channels): up to 1e8 multiply-adds and 4096 output pixels, beyond that
+// pixel count the stride-2 layers and thin layers.  Stride 2 with 64 ... 128 input channels (the tiled alternative is the fp32
+// kernel: 25.5 against 29.7 at 28 x 64 x 96 -> 128 / 2) has the patch in the LDS as well and is taken up to 2e8 multiply-adds; from
+// PWC_SK_S2_TILE_MIN tiles on the entry point runs it on the strided tile kernel of conv3x3_s2.hip, see there.
 #define PWC_SK_MAX_MACS 100000000L
 #define PWC_SK_THIN_MACS 32000000L
 #define PWC_SK_LP_MAX_MACS 240000000L
 #define PWC_SK_LP_MAX_PIXELS 8192L
 #define PWC_SK_S2_MAX_MACS 200000000L
+// Stride 2 from this many 4 x 32-pixel tiles on (about three quarters of the CUs): pwc_conv3x3_sk_f32 launches the strided tile
+// kernel of conv3x3_s2.hip instead.  Measured back to back, us, strided tile kernel against this file's choice
+// (profiles/s2tile_exp_ab.txt): 56 x 128 x 64 -> 96 / 2 of 16 / 18 / 64 images (224 / 252 / 896 tiles) 20.4 / 21.6 / 75.0 against
+// 38.1 / 41.6 / 124.0; 28 x 64 x 96 -> 128 / 2 of 64 images (256 tiles) 36.0 against 61.4.  Below, its workgroups are too few -- a
+// tile takes its 15 us however many there are, the kernels above deal K and output channels as well: 28 x 64 x 96 -> 128 / 2 of 16
+// images (64 tiles) 26.1 against 17.9, 56 x 128 x 64 -> 96 / 2 of 2 images (28 tiles) 15.0 against 8.3; 112 tiles (8 images) win
+// narrowly (16.1 against 19.9) and stay where they were.
+#define PWC_SK_S2_TILE_MIN 192L
 extern "C" int pwc_conv3x3_sk_supported(int N, int H, int W, int Cin_phys, int Cout, int stride, int dilation) {
     if (!sk_shape_ok(N, H, W, Cin_phys, Cout, stride, dilation)) return 0;
     int Ho, Wo, pt, pl;
@@ -394,7 +404,9 @@ extern "C" int pwc_conv3x3_sk_supported(int N, int H, int W, int Cin_phys, int C
     const long M = (long)N * Ho * Wo, macs = M * Cin_phys * Cout;
     if (stride == 1 && dilation == 1 && Cin_phys >= 96 && Cin_phys <= 288 && M <= PWC_SK_LP_MAX_PIXELS && macs <= PWC_SK_LP_MAX_MACS)
         return 1;
-    // stride 2: the tiled alternative is the fp32-pipe kernel (56 x 128 x 64 -> 96 / 2 of 16 images: 34 us against 43 - 46)
+    // stride 2: the tiled alternative is the fp32-pipe kernel (56 x 128 x 64 -> 96 / 2 of 16 images: 34 us against 43 - 46).  The
+    // entry point itself sends such a launch on to the strided tile kernel from PWC_SK_S2_TILE_MIN tiles on (20.4 us for that
+    // layer, 38.1 for conv3x3_skp_kernel): this answer does not change with it.
     if (stride == 2 && dilation == 1 && Cin_phys >= 64 && Cin_phys <= 128 && macs <= PWC_SK_S2_MAX_MACS) return 1;
     if (macs > PWC_SK_MAX_MACS) return 0;
     return (M <= 4096 || stride == 2 || macs <= PWC_SK_THIN_MACS) ? 1 : 0;
@@ -432,8 +444,8 @@ extern "C" int pwc_debug_conv3x3_sk_tile(int tile) { sk_tile_override = tile; re
 #endif
 
 // tile_req: 0 = the library's choice for the shape; 11, 21, 22 (fragments from global memory), 31, 41, 42 (patch in the LDS) = that
-// workgroup tile, PWC_EUNSUPPORTED where the shape does not admit it (x2 tiles: C_out % 32; 3x / 4x: no dilation, up to 288
-// input channels at stride 1, 128 at stride 2).
+// workgroup tile, 50 = the strided tile kernel of conv3x3_s2.hip; PWC_EUNSUPPORTED where the shape does not admit it (x2 tiles:
+// C_out % 32; 3x / 4x: no dilation, up to 288 input channels at stride 1, 128 at stride 2; 50: stride 2, no dilation, C_out <= 128).
 static int sk_run(const float* x, int x_cs, const float* packed_w, const float* bias, float* y, int y_cs,
                   int N, int H, int W, int Cin_phys, int Cout, int stride, int dilation, int apply_act,
                   float slope, int tile_req, pwc_stream_t stream) {
@@ -464,6 +476,17 @@ static int sk_run(const float* x, int x_cs, const float* packed_w, const float* 
     // stride 2 (a 9 x 17-pixel patch for 4 x 8 outputs): 28 x 64 x 96 -> 128 / 2 of 16 images 16.8 us against 22.3 direct,
     // 14 x 32 x 128 -> 192 / 2: 11.3 against 13.8; launches of up to one workgroup per CU stay direct (5.0 against 5.2)
     if (lp_ok && stride == 2 && Cin_phys >= 64 && wgs11 > 256) tile = (wgs11 <= 640 || (Cout % 32)) ? 41 : 42;
+    // Stride 2 at full-chip size: the strided tile kernel (conv3x3_s2.hip: a workgroup owns 4 x 32 pixels and all output channels).
+    // PWC_SK_S2_TILE_MIN: see the define.
+    const bool s2_ok = stride == 2 && dilation == 1 && pwc_conv3x3_s2_tile_admits(N, H, W, x_cs, Cin_phys, Cout);
+    bool s2_tile = tile_req == 50 || (!tile_req && s2_ok && pwc_conv3x3_s2_tile_count(N, H, W) >= PWC_SK_S2_TILE_MIN);
+#ifdef PWC_HARNESS
+    if (!tile_req && pwc_conv3x3_s2_tile_debug_mode()) s2_tile = s2_ok && pwc_conv3x3_s2_tile_debug_mode() > 0;
+#endif
+    if (s2_tile) {
+        if (!s2_ok) return PWC_EUNSUPPORTED;
+        return pwc_conv3x3_s2_tile_launch(x, x_cs, packed_w, bias, y, y_cs, N, H, W, Cin_phys, Cout, apply_act, slope, stream);
+    }
     if (tile_req) {
         if (tile_req != 11 && tile_req != 21 && tile_req != 22 && tile_req != 31 && tile_req != 41 && tile_req != 42) return PWC_EINVAL;
         if (((tile_req % 10) == 2 && Cout % 32) || (tile_req > 30 && !lp_ok)) return PWC_EUNSUPPORTED;

@@ -238,3 +238,17 @@ __global__ void conv3x3_c32_pack_kernel(const float* __restrict__ w, const int32
         pwc_split1(v, dst[0], dst[512]);
     }
 }
+
+// ---- the strided tile kernel (conv3x3_s2.hip) behind pwc_conv3x3_sk_f32 and pwc_conv3x3_h2_stride2_f32: stride 2, dilation 1,
+// 'SAME', weights in the pwc_conv3x3_sk_pack_f32 layout.  _admits: the shapes it handles (C_in % 32, C_out % 16, C_out <= 128, the
+// tensor behind one buffer resource); _count: its workgroups (tiles of 4 x 32 output pixels); _launch: the callers have checked
+// pointers, channel strides and alignment by their own rules.
+#define PWC_S2_TILE_ROWS 4
+#define PWC_S2_TILE_COLS 32
+bool pwc_conv3x3_s2_tile_admits(int N, int H, int W, int x_cs, int Cin_phys, int Cout);
+long pwc_conv3x3_s2_tile_count(int N, int H, int W);
+int pwc_conv3x3_s2_tile_launch(const float* x, int x_cs, const float* packed_w, const float* bias, float* y, int y_cs, int N, int H,
+                               int W, int Cin_phys, int Cout, int apply_act, float slope, pwc_stream_t stream);
+#ifdef PWC_HARNESS
+int pwc_conv3x3_s2_tile_debug_mode();
+#endif
