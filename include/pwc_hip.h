@@ -134,8 +134,9 @@ int pwc_warp_cost_volume_concat_supported(int H, int W, int C, int search_range,
  * fp32 bilinear blend of modules.py:132-135) is used as the two-term fp16 split x = h + 2^-11 m' of pwc_conv3x3_h2_f32,
  * three v_mfma_f32_16x16x32_f16 per (4x4-pixel block pair, 32 channels), fp32 accumulation -- 27 matrix instructions per
  * block where the fp32 form has 72 twice as long, and none of them stalls the vector instructions of its SIMD.  Error
- * against float64: not larger than the fp32 form's (tests).  RANGE: features below 65504 in magnitude (beyond: NaN
- * outputs, see PWC_STATUS_NONFINITE).  Same support set as the fp32 form.  Round 6: out_pad_writable = 2 (flow != NULL) puts
+ * against float64: not larger than the fp32 form's, and per output element within 16 x 2^-24 of the sum of absolute products
+ * (16 + 4 behind a warp; tests/test_gpu_f16_pipe_f64.py).  RANGE: features below 65520 in magnitude ([65504, 65520) still splits
+ * exactly; from 65520 on: NaN on the outputs that read the feature, never a finite wrong number; see PWC_STATUS_NONFINITE).  Same support set as the fp32 form.  Round 6: out_pad_writable = 2 (flow != NULL) puts
  * the pixel's flow (x, y), as read, into channels 81, 82 of its record and zero into channel 83: the record is then
  * [cv | flows_up_prev | 0] of the estimator's input (see pwc_conv3x3_h2_ex3_f32). */
 int pwc_warp_cost_volume_concat_h2_f32(const float* f0, int f0_cs, const float* f1, int f1_cs,
@@ -277,9 +278,11 @@ int pwc_conv3x3_h2_supported(int N, int H, int W, int Cin_phys, int Cout, int di
  *   status[0] & PWC_STATUS_NONFINITE        pwc_resize_bilinear_status_f32 wrote a value that is not finite.  The F16-pipe
  *                                           kernels (pwc_conv3x3_h2*, pwc_conv3x3_c16pair*, pwc_warp_cost_volume_concat_h2_f32)
  *                                           turn an operand at or beyond 65520 in magnitude into NaN outputs (inf - inf in the
- *                                           split; the band 65504-65519, which still splits exactly, is measured on the conv
- *                                           kernels h2 / sk / t32 / w32 only -- c16pair and the correlation are tested at 1e5:
- *                                           keep their operands below 65504), NaN survives every later layer of the network, so the model's LAST launch
+ *                                           split; the band 65504-65519 still splits exactly: planted operands of 65503, 65519 and
+ *                                           +-65520 are tested against float64 on every one of these kernels,
+ *                                           tests/test_gpu_forward_f64.py and tests/test_gpu_f16_pipe_f64.py).  An INTERMEDIATE of
+ *                                           pwc_conv3x3_c16pair_f32 / pwc_conv3x3_c3c16pair_f32 that reaches 65520 from in-range inputs
+ *                                           does the same to every output behind it (tested).  NaN survives every later layer of the network, so the model's LAST launch
  *                                           sees it: repeat the forward on the fp32 kernels (the reference, plain fp32, has no
  *                                           such limit).  Watching the operands inside the kernels instead was measured at 2-3 %
  *                                           of every launch (profiles/r05_timeline_range_tracking_cost.txt).
@@ -316,7 +319,9 @@ int pwc_conv3x3_h2_ex3_f32(const float* x, int x_cs, int Cin_a_phys, const float
  * behind each, in one launch (csrc/conv3x3_c16pair.hip; reference modules.py:62-67, the `fp_extractor/conv2d_1`,
  * `conv2d_2` pair of pyramid level 1): the intermediate stays in LDS instead of making a round trip through memory.
  * Arithmetic as pwc_conv3x3_h2_f32 (fp32 in / out / accumulation, exact-to-22-bit fp16 operand pairs, three products;
- * the intermediate is rounded to fp32 exactly as a tensor in memory would be; inputs below 65504).  packed comes from
+ * the intermediate is rounded to fp32 exactly as a tensor in memory would be).  RANGE: inputs, weights AND the intermediate
+ * below 65520 in magnitude; from 65520 on the outputs that read the value are NaN, never a finite wrong number
+ * (tests/test_gpu_f16_pipe_f64.py: per output element against float64, also for pwc_conv3x3_c3c16pair_f32).  packed comes from
  * pwc_conv3x3_c16pair_pack_f32 (both HWIO (3,3,16,16) kernels; pwc_conv3x3_c16pair_packed_floats floats).  x, y: NHWC
  * with channel strides x_cs, y_cs >= 16 (multiples of 4), 16-byte aligned.  _supported: 1 where the fused launch is
  * the faster way to run the pair (at least one 16 x 32-pixel tile per CU). */

@@ -9,7 +9,8 @@
 // layer.
 //
 // Arithmetic: as conv3x3_h2.hip -- x = h + 2^-11 m', three products, two fp32 accumulators (hh, cross); the intermediate is
-// rounded to fp32 once (bias, leaky-relu) and split again, exactly like an fp32 tensor read back from memory would be.
+// rounded to fp32 once (bias, leaky-relu) and split again, exactly like an fp32 tensor read back from memory would be.  Range: inputs,
+// weights and the intermediates below 65520; from 65520 on h is inf and every output behind the value is NaN (tests/test_gpu_f16_pipe_f64.py).
 // K packing of a 16x16x32 MFMA (M = couts, N = 16 pixels; lane quarter kq holds K 8 kq .. 8 kq + 7):
 //   hh, tap pair (2j, 2j+1):  A = [uh(tap 2j) ch 0-7 | ch 8-15 | uh(tap 2j+1) ch 0-7 | ch 8-15]   B = vh shifted by the quarter's tap
 //   cross, tap t:             A = [uh ch 0-7 | uh ch 8-15 | um' ch 0-7 | um' ch 8-15]              B = [vm' 0-7 | vm' 8-15 | vh 0-7 | vh 8-15]

@@ -11,7 +11,7 @@
 // x = h + 2^-11 m' (pwc_split2), and a tile of 16 P pixels x 16 Q pixels over 32 channels is three v_mfma_f32_16x16x32_f16:
 // cross = AH x BM' + AM' x BH, hh = AH x BH, result hh + 2^-11 cross (fp32 accumulators).  27 matrix instructions of 16 cycles
 // per 4 x 4-pixel block at C = 32 where the fp32 form has 72 of 32 cycles, and an F16-pipe instruction does not
-// keep the SIMD's vector instructions out.  Range of the split: |x| < 65504 (from 65520 on: NaN outputs; PWC_STATUS_NONFINITE).
+// keep the SIMD's vector instructions out.  Range of the split: |x| < 65520 (from 65520 on: NaN on the outputs that read x; PWC_STATUS_NONFINITE).
 //
 // Organisation.  A workgroup is EIGHT waves, one workgroup per CU:
 //   waves 0-3  "consumers", one per 4-pixel block column of the 16-column strip: matrix instructions, stage, copy-out.  A P block

@@ -186,7 +186,8 @@ __device__ __forceinline__ int pwc_xcd_remap(int b, int nblocks) {
 // one mixed-precision FMA per value that reads the fp16 half in place and writes its half of the pair -- the same values as
 //   h = (_Float16)x;  m' = (_Float16)fmaf((float)h, -2048.f, x * 2048.f);
 // which the compiler turns into seven.  |x| >= 65520 rounds h to inf (m' is then -inf / NaN): the range condition of these
-// kernels; [65504, 65520) still rounds h to 65504 with a finite m' (< 2^15) and stays exact (tests/test_gpu_forward_f64.py).
+// kernels; [65504, 65520) still rounds h to 65504 with a finite m' (< 2^15) and stays exact (tests/test_gpu_forward_f64.py,
+// tests/test_gpu_f16_pipe_f64.py).
 __device__ __forceinline__ void pwc_split2(const float x0, const float x1, unsigned& h_pair, unsigned& m_pair) {
     const f32x2 xs = {x0, x1};
     const pwc_f16x2 h2 = __builtin_convertvector(xs, pwc_f16x2);
