@@ -6,7 +6,9 @@ train.py:124-131 as a stand-alone tool).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --list ...
 
 pairs.txt: one pair per line, `image_0 image_1 flow_gt.flo [mask.png]`.  Images are cropped to multiples
-of 64 (reference test.py:13-17), scaled to [0,1]; the ground truth and the mask are cropped the same way.
+of 64 (reference test.py:13-17), scaled to [0,1]; the ground truth and the mask are cropped the same way.  --fit resize / pad
+evaluate the WHOLE frame instead: the frames are uploaded as uint8, resized or padded to the next multiples of 64 on the GPU, the
+flow is brought back to the frame's own grid and compared with the uncropped ground truth and mask.
 Sparse ground truth: pixels whose .flo value is the "unknown" sentinel (|u| or |v| above 1e9, or not finite) are
 left out of every number; the optional fourth column names an 8-bit mask image, non-zero = valid
 (`--mask_is_invalid`: non-zero = INVALID, Sintel's invalid/ images).  The JSON line carries the masked EPE, KITTI's
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--list", required=True)
     ap.add_argument("--resume", default=None)
@@ -32,7 +34,14 @@ def main():
     ap.add_argument("--save_dir", default=None, help="write every predicted flow as <index>.flo (rank 0, after the gather)")
     ap.add_argument("--mask_is_invalid", action="store_true",
                     help="the mask column's images mark INVALID pixels with non-zero values (Sintel's invalid/)")
-    args = ap.parse_args()
+    ap.add_argument("--fit", choices=("crop", "resize", "pad"), default="crop",
+                    help="frames whose size is no multiple of 64: crop them, ground truth and mask too (reference), or resize / "
+                         "pad them on the GPU and compare the flow on the frame's own grid [crop]")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -53,24 +62,33 @@ def main():
     if args.resume:
         model.load_weights(ckpt.load_weights(args.resume))
 
+    crop = flow_io.factor_crop if args.fit == "crop" else (lambda a: a)
+
     def load_pair(i):
         p0, p1, pf = pairs[i][:3]
-        im0 = flow_io.factor_crop(np.asarray(Image.open(p0).convert("RGB")))
-        im1 = flow_io.factor_crop(np.asarray(Image.open(p1).convert("RGB")))
+        im0 = crop(np.asarray(Image.open(p0).convert("RGB")))
+        im1 = crop(np.asarray(Image.open(p1).convert("RGB")))
         raw = flow_io.read_flo(pf)
-        gt = flow_io.factor_crop(raw)
+        gt = crop(raw)
         valid = flow_io.flow_valid(gt)                        # the .flo sentinel
         if len(pairs[i]) > 3:
             mask = np.asarray(Image.open(pairs[i][3]).convert("L")) != 0
             if mask.shape != raw.shape[:2]:
                 raise SystemExit(f"evaluate.py: mask {pairs[i][3]} is {mask.shape}, its flow {raw.shape[:2]}")
-            valid &= flow_io.factor_crop((~mask if args.mask_is_invalid else mask)[..., None])[..., 0]
+            valid &= crop((~mask if args.mask_is_invalid else mask)[..., None])[..., 0]
+        if args.fit != "crop":                                    # uint8 frames: a quarter of the upload, / 255 in the fit launch
+            if im0.shape != im1.shape or im0.shape[:2] != gt.shape[:2]:
+                raise SystemExit(f"evaluate.py: pair {i}: frames {im0.shape[:2]}, {im1.shape[:2]} and flow {gt.shape[:2]} differ in size")
+            return (torch.from_numpy(np.array(im0)), torch.from_numpy(np.array(im1)),          # (copies: PIL's buffers are read-only)
+                    torch.from_numpy(np.ascontiguousarray(gt, np.float32)), torch.from_numpy(np.ascontiguousarray(valid)))
         return (torch.from_numpy(np.ascontiguousarray(im0, np.float32) / 255.0),
                 torch.from_numpy(np.ascontiguousarray(im1, np.float32) / 255.0),
                 torch.from_numpy(np.ascontiguousarray(gt, np.float32)),
                 torch.from_numpy(np.ascontiguousarray(valid)))
 
     def forward(im0, im1):
+        if args.fit != "crop":
+            return pwcnet_amd.flow_any_size(model, im0, im1, args.fit)[0]
         return model(im0, im1)[0]
 
     torch.cuda.synchronize()

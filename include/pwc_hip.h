@@ -766,6 +766,32 @@ int pwc_fb_consistency_grad_f32(const float* flow_a, int a_cs, const float* flow
                                 float* dflow_a, int dflow_a_cs, float* dflow_b, int dflow_b_cs, int accumulate,
                                 pwc_stream_t stream);
 
+/* ---- frames of any size: fit them to the network's geometry, refit the flow to the frames' grid ----
+ * The network takes frames whose height and width are multiples of 64.  These two launches sit in front of and behind a forward on
+ * plain dense tensors; the forward itself is not involved.
+ * Resize arithmetic of one axis (`in` source samples, `out` output samples, output index d), half-pixel centres:
+ *   src = ((2 d + 1) in - out) / (2 out)   one double division of exact integers, clamped to [0, in - 1],
+ *   i0 = floor(src), f = src - i0, i1 = min(i0 + 1, in - 1);
+ * the value is (1 - fy) ((1 - fx) a + fx b) + fy ((1 - fx) c + fx d) in double, every operation rounded on its own, over the
+ * corners a = (y0, x0), b = (y0, x1), c = (y1, x0), d = (y1, x1); it is rounded to float32 once.  An axis with in == out has
+ * every weight exactly 0: the resize is a copy along it.
+ *
+ * Frames -> network geometry.  x: N x H x W x 3 dense, uint8_t (x_is_u8 != 0; value v enters as the float32 nearest v / 255) or
+ * float32.  y: N x OH x OW x 3 dense float32, OH >= H, OW >= W.  PWC_FIT_RESIZE: the bilinear above, per axis from (H, W) to
+ * (OH, OW).  PWC_FIT_PAD: y[oy, ox] = x[min(oy, H - 1), min(ox, W - 1)] (the last row and column repeated).
+ * Checks, before any launch: a null pointer, N, H, W <= 0, OH < H, OW < W, an unknown mode (PWC_EINVAL); y off a 16-byte
+ * boundary or a float32 x off a 4-byte one (PWC_EALIGN); N * OH * OW >= 2^31 (PWC_ERANGE).  One launch. */
+#define PWC_FIT_RESIZE 0
+#define PWC_FIT_PAD 1
+int pwc_fit_frames_f32(const void* x, int x_is_u8, float* y, int N, int H, int W, int OH, int OW, int mode, pwc_stream_t stream);
+
+/* Flow at network geometry -> flow on the frames' grid.  f: N x FH x FW x 2 dense float32.  y: N x H x W x 2 dense float32.
+ * PWC_FIT_RESIZE: the same bilinear from (FH, FW) to (H, W); the double value of u is multiplied by the double quotient W / FW,
+ * that of v by H / FH, and the product is rounded to float32 once.  PWC_FIT_PAD: y = f[:, :H, :W].
+ * Checks, before any launch: a null pointer, a non-positive size, an unknown mode, PWC_FIT_PAD with FH < H or FW < W
+ * (PWC_EINVAL); f or y off an 8-byte boundary (PWC_EALIGN); N * H * W or N * FH * FW >= 2^31 (PWC_ERANGE).  One launch. */
+int pwc_refit_flow_f32(const float* f, float* y, int N, int FH, int FW, int H, int W, int mode, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
 
     python infer.py --input_images frame_0.png frame_1.png [--resume model_600.ckpt] [--time]
 
-Follows reference test.py:27-65: crop both images to multiples of 64, scale to [0,1],
+Follows reference test.py:27-65: crop both images to multiples of 64 (--fit crop, the default; --fit resize / pad keep the
+whole frame: it is resized or padded to the next multiples of 64 on the GPU and flow_final comes back on the frame's own grid,
+the pyramid levels stay at the network's geometry), scale to [0,1],
 batch of one pair, default PWCDCNet(), optional checkpoint restore (TF V2 bundle, read
 without TensorFlow), optional timing loop over repeated forwards of the same pair, then
 the 5-level flow pyramid rescaled to pixels at each level (x 20 / 2^(6-l), test.py:57-60).
@@ -18,7 +20,7 @@ import numpy as np
 import torch
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--input_images", type=str, nargs=2, required=True, help="Target images (required)")
     ap.add_argument("--resume", type=str, default=None, help="Learned parameter checkpoint prefix [None]")
@@ -26,16 +28,27 @@ def main():
     ap.add_argument("--iters", type=int, default=1000, help="timed iterations with --time [1000]")
     ap.add_argument("--out", type=str, default="./test_figure")
     ap.add_argument("--gpu", type=int, default=0)
-    args = ap.parse_args()
+    ap.add_argument("--fit", choices=("crop", "resize", "pad"), default="crop",
+                    help="frames whose size is no multiple of 64: crop them (reference), or resize / pad them on the GPU and "
+                         "bring the flow back to the frame's size [crop]")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     from PIL import Image
     import pwcnet_amd
     from pwcnet_amd import ckpt, flow_io
 
     torch.cuda.set_device(args.gpu)
-    imgs = [flow_io.factor_crop(np.asarray(Image.open(p).convert("RGB"))) for p in args.input_images]
-    images = np.array(imgs, dtype=np.float32) / 255.0                      # (2, h, w, 3)
-    x = torch.from_numpy(images).cuda()
+    if args.fit == "crop":
+        imgs = [flow_io.factor_crop(np.asarray(Image.open(p).convert("RGB"))) for p in args.input_images]
+        images = np.array(imgs, dtype=np.float32) / 255.0                  # (2, h, w, 3)
+        x = torch.from_numpy(images).cuda()
+    else:                                                                  # uint8 upload; / 255 and the fit in one launch
+        x = torch.from_numpy(np.stack([np.asarray(Image.open(p).convert("RGB")) for p in args.input_images])).cuda()
+        x, info = pwcnet_amd.fit_frames(x, args.fit)
 
     model = pwcnet_amd.PWCDCNet(range_check="sync")      # results are final when a call returns (fp16-range check + fp32 repeat)
     if args.resume is not None:
@@ -52,6 +65,8 @@ def main():
             flow_final, flows = model(x[0:1], x[1:2])
         torch.cuda.synchronize()
         print(f"Inference time: {(time.time() - t0) / args.iters} sec (averaged over {args.iters} iterations)")
+    if args.fit != "crop":
+        flow_final = pwcnet_amd.refit_flow(flow_final, info)               # the frame's own size, frame pixels
 
     os.makedirs(args.out, exist_ok=True)
     flow_io.write_flo(os.path.join(args.out, "flow_final.flo"), flow_final[0].cpu().numpy())

@@ -9,7 +9,9 @@ Follows reference test_continuous.py:45-64: frames are cropped to multiples of 6
 to pixels per level (x 20 / 2^(6-l)).  Differences: consecutive pairs of equal size are run as ONE
 batch (the reference feeds them one by one), and instead of a matplotlib figure each pair gets
 <out>/<dname>/<fname>.png -- first frame and the colour-coded pyramid side by side -- plus
-<out>/<dname>/<fname>.flo with the full-resolution flow.
+<out>/<dname>/<fname>.flo with the full-resolution flow.  --fit resize / pad keep the whole frame instead of cropping it: the
+frames are uploaded as uint8, resized or padded to the next multiples of 64 on the GPU, and the .flo has the frame's own size
+(the montage's pyramid levels stay at the network's geometry).
 """
 import argparse
 import os
@@ -34,7 +36,7 @@ def pyramid_montage(image, flows):
     return np.concatenate(tiles, axis=1)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("-i", "--input_images", type=str, nargs="+", required=True, help="Target images (required)")
     ap.add_argument("-r", "--resume", type=str, default=None, help="Learned parameter checkpoint prefix [None]")
@@ -42,7 +44,14 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="pairs per forward")
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--pipeline", type=int, default=3, help="forwards in flight (pwcnet_amd.ForwardPipeline depth; 1 = one at a time)")
-    args = ap.parse_args()
+    ap.add_argument("--fit", choices=("crop", "resize", "pad"), default="crop",
+                    help="frames whose size is no multiple of 64: crop them (reference), or resize / pad them on the GPU and "
+                         "bring the flow back to the frame's size [crop]")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     paths = []
     for p in args.input_images:                      # expand wild-cards (test_continuous.py:75-78)
         paths.extend(sorted(glob(p)) if "*" in p else [p])
@@ -65,7 +74,9 @@ def main():
     else:
         print("!!! Test with un-learned model !!!")
 
-    frames = [flow_io.factor_crop(np.asarray(Image.open(p).convert("RGB"))) for p in paths]
+    frames = [np.asarray(Image.open(p).convert("RGB")) for p in paths]
+    if args.fit == "crop":
+        frames = [flow_io.factor_crop(f) for f in frames]
     # runs of consecutive pairs whose frames all have one size: one batch each
     jobs = []
     i = 0
@@ -74,7 +85,7 @@ def main():
         while j < len(frames) - 1 and j - i < args.batch and frames[j + 1].shape == frames[i].shape:
             j += 1
         if j == i:
-            raise ValueError(f"{paths[i]} and {paths[i + 1]} differ in size after cropping")
+            raise ValueError(f"{paths[i]} and {paths[i + 1]} differ in size" + (" after cropping" if args.fit == "crop" else ""))
         jobs.append((i, j))
         i = j
     num_levels = model.nets[0].num_levels
@@ -82,11 +93,17 @@ def main():
     for w0 in range(0, len(jobs), window):
         tickets = []
         for i, j in jobs[w0:w0 + window]:
-            seq = torch.from_numpy(np.stack(frames[i:j + 1]).astype(np.float32) / 255.0).cuda()
-            tickets.append((i, j, model.submit(seq[:-1].contiguous(), seq[1:].contiguous())))
+            if args.fit == "crop":
+                seq = torch.from_numpy(np.stack(frames[i:j + 1]).astype(np.float32) / 255.0).cuda()
+                info = None
+            else:                                    # uint8 upload; / 255 and the fit in one launch on the caller's stream
+                seq, info = pwcnet_amd.fit_frames(torch.from_numpy(np.stack(frames[i:j + 1])).cuda(), args.fit)
+            tickets.append((i, j, info, model.submit(seq[:-1].contiguous(), seq[1:].contiguous())))
         model.synchronize()
-        for i, j, ticket in tickets:
+        for i, j, info, ticket in tickets:
             flow_final, flows = ticket.result()
+            if info is not None:
+                flow_final = pwcnet_amd.refit_flow(flow_final, info)
             flow_final = flow_final.cpu().numpy()
             flows = [f.cpu().numpy() for f in flows]
             for k in range(j - i):
