@@ -792,6 +792,40 @@ int pwc_fit_frames_f32(const void* x, int x_is_u8, float* y, int N, int H, int W
  * (PWC_EINVAL); f or y off an 8-byte boundary (PWC_EALIGN); N * H * W or N * FH * FW >= 2^31 (PWC_ERANGE).  One launch. */
 int pwc_refit_flow_f32(const float* f, float* y, int N, int FH, int FW, int H, int W, int mode, pwc_stream_t stream);
 
+/* ---- training augmentation: affine crop of both frames, colour jitter, the flow transformed exactly ----
+ * One launch prepares a training batch from whole frames: an OH x OW window of each of the N pairs, resampled through one affine
+ * map per frame, jittered in colour, with the ground-truth flow carried into the augmented pair's geometry.
+ * im0, im1: N x H x W x 3 dense, uint8_t (im_is_u8 != 0; value v enters as the float32 nearest v / 255) or float32.
+ * flow: N x H x W x 2 dense float32 or NULL (then out_flow and out_valid are not written and may be NULL).  valid: N x H x W
+ * bytes, non-zero = labelled, or NULL (every pixel labelled).  out0, out1: N x OH x OW x 3, out_flow: N x OH x OW x 2, all float32;
+ * out_valid: N x OH x OW bytes (0 / 1).
+ * params: N records of 32 doubles IN DEVICE MEMORY, pixel centres at integer indices:
+ *    0 ..  5  M0 = (a b c; d e f): output pixel (x, y) -> frame-0 position q0 = (a x + b y + c, d x + e y + f)
+ *    6 .. 11  M1, the same map into frame 1
+ *   12 .. 17  I1, the inverse of M1, computed by the caller in double (the kernel inverts nothing)
+ *   18 .. 23  frame 0 photometric: gain r, g, b; gamma; contrast; brightness
+ *   24 .. 29  frame 1 photometric
+ *   30 .. 31  zero
+ * All arithmetic is double, every operation rounded on its own (no fused multiply-add), each output rounded to float32 once.
+ * Frames: q is clamped to [0, W - 1] x [0, H - 1] (replicate); x0 = floor(qx), fx = qx - x0, x1 = min(x0 + 1, W - 1), likewise y;
+ *   value = (1 - fy) ((1 - fx) a + fx b) + fy ((1 - fx) c + fx d) over the corners a = (y0, x0), b = (y0, x1), c = (y1, x0),
+ *   d = (y1, x1); then, unless the frame's photometric record is exactly (1, 1, 1, 1, 1, 0), per channel c
+ *   clamp((pow(clamp(value * gain_c, 0, 1), gamma) - 0.5) * contrast + 0.5 + brightness, 0, 1)  (gamma == 1: no pow).
+ *   Identity geometry with integer c, f and the identity record: the plain crop, bit for bit.
+ * Flow: (u, v) = the input flow sampled at the UN-clamped q0 -- the same bilinear, or with flow_nearest != 0 the single tap
+ *   (floor(qx + 0.5), floor(qy + 0.5)); q1 = q0 + (u, v) is where the content sits in frame 1, p1 = I1 q1 where it sits in the
+ *   augmented frame 1, out_flow(p) = p1 - p.  Zoom, rotation, mirror and a relative transform of frame 1 are all this formula.
+ * Validity: out_valid(p) = 1 iff q0 lies in [0, W - 1] x [0, H - 1] and every tap used for the flow is labelled: the single tap
+ *   in nearest mode, the four corners in bilinear mode -- a corner whose weight is exactly zero (fx == 0 or fy == 0) is not a
+ *   tap: it is not read.  Where out_valid is 0, out_flow is 0, 0: an unlabelled value (the 1e10 of .flo files) is never
+ *   blended into an output.
+ * Checks, before any launch: a null im0, im1, params, out0 or out1, a flow with a null out_flow or out_valid, a size <= 0
+ * (PWC_EINVAL); float32 frames, out0 or out1 off a 4-byte boundary, params, flow or out_flow off an 8-byte one (PWC_EALIGN);
+ * N * H * W or N * OH * OW >= 2^31, N > 65535, OH > 16 * 65535 (PWC_ERANGE).  One launch; no workspace, no atomics, no random numbers. */
+int pwc_augment_pairs_f32(const void* im0, const void* im1, int im_is_u8, const float* flow, const unsigned char* valid,
+                          const double* params, float* out0, float* out1, float* out_flow, unsigned char* out_valid,
+                          int N, int H, int W, int OH, int OW, int flow_nearest, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

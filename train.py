@@ -37,6 +37,14 @@ and-ed with <dir>/invalid/<seq>/frame_NNNN.png (non-zero = invalid, MPI-Sintel's
 the step's loss and gradient and the validation numbers (masked EPE, KITTI's Fl-all) leave the invalid pixels out.
 `--synthetic_invalid F` knocks a random fraction F of the synthetic ground truth out and writes 1e10 there.  KITTI's
 16-bit flow PNGs are not read: convert them to .flo (sentinel at the unlabelled pixels) first.
+
+`--augment geometric | full` prepares the training batches on the GPU (pwcnet_amd/augment.py, one launch per batch): the data set
+hands back WHOLE uint8 frames, flow and mask, the batch is uploaded as bytes, and every pair gets its own random zoom
+(--aug_scale), rotation (--aug_rotate), translation (--aug_translate), mirror (--aug_flip) and a small extra rotation and shift
+of the second frame (--aug_rel_rotate, --aug_rel_translate), the ground-truth flow transformed with them; `full` adds gain, gamma,
+contrast and brightness jitter.  The crop stays --crop_shape; --aug_seed seeds the draws.  The frames of a batch must have one
+size.  `--dataset synthetic` then generates its frames 32 px larger on each side than the crop.  Validation is untouched: it runs
+on the plain crops.  `--augment none` (the default) is the data path as it was: the host crop, / 255, the float32 upload.
 """
 import argparse
 import glob
@@ -63,8 +71,9 @@ class SyntheticPairs:
     the pixels (a seeded random set per pair) whose label is knocked out: mask False and ground truth 1e10, the .flo
     sentinel, so that a consumer that ignored the mask would show it at once."""
 
-    def __init__(self, n, shape, seed=0, invalid=0.0):
+    def __init__(self, n, shape, seed=0, invalid=0.0, uint8=False):
         self.n, self.shape, self.seed, self.invalid = n, shape, seed, float(invalid)
+        self.uint8 = uint8                      # frames rounded to bytes, as files hold them (--augment uploads bytes)
 
     def __len__(self):
         return self.n
@@ -83,13 +92,16 @@ class SyntheticPairs:
         if self.invalid > 0:
             valid = np.random.RandomState(self.seed + 7919 * (i + 1)).uniform(size=(h, w)) >= self.invalid
             flow[~valid] = 1e10
+        if self.uint8:
+            im0, im1 = np.rint(im0).astype(np.uint8), np.rint(im1).astype(np.uint8)
         return np.ascontiguousarray(im0), np.ascontiguousarray(im1), flow, valid
 
 
 class FilePairs:
-    def __init__(self, pairs, crop_shape, crop_type="random", seed=0):
+    def __init__(self, pairs, crop_shape, crop_type="random", seed=0, whole=False):
         self.pairs, self.crop, self.crop_type = pairs, crop_shape, crop_type
         self.rng = np.random.RandomState(seed)
+        self.whole = whole                      # --augment: whole uint8 frames, flow and mask; the crop happens on the GPU
 
     def __len__(self):
         return len(self.pairs)
@@ -98,13 +110,15 @@ class FilePairs:
         from PIL import Image
         from pwcnet_amd import flow_io
         a, b, f = self.pairs[i]
-        im0, im1 = (np.asarray(Image.open(p).convert("RGB"), np.float32) for p in (a, b))
+        im0, im1 = (np.asarray(Image.open(p).convert("RGB"), np.uint8 if self.whole else np.float32) for p in (a, b))
         flow = flow_io.read_flo(f)
         valid = flow_io.flow_valid(flow)
         inv = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(f))), "invalid",
                            os.path.basename(os.path.dirname(f)), os.path.basename(f).replace(".flo", ".png"))
         if os.path.exists(inv):
             valid &= np.asarray(Image.open(inv).convert("L")) == 0
+        if self.whole:
+            return np.ascontiguousarray(im0), np.ascontiguousarray(im1), np.ascontiguousarray(flow), np.ascontiguousarray(valid)
         ch, cw = self.crop
         H, W = im0.shape[:2]
         y0 = self.rng.randint(0, H - ch + 1) if self.crop_type == "random" else (H - ch) // 2
@@ -114,10 +128,34 @@ class FilePairs:
                 np.ascontiguousarray(valid[sl]))
 
 
-def batches(ds, idx, bs):
+def batches(ds, idx, bs, same_size=False):
     for i in range(0, len(idx) - bs + 1, bs):                       # drop_last, like the reference's loader
         items = [ds[j] for j in idx[i:i + bs]]
+        if same_size and len({it[0].shape for it in items}) > 1:    # whole frames (--augment): one launch takes one frame size
+            raise ValueError(f"train.py --augment: the frames of a batch differ in size, {sorted({it[0].shape[:2] for it in items})}; "
+                             "use a data set of one frame size or --batch_size 1")
         yield tuple(torch.from_numpy(np.stack([it[k] for it in items])) for k in range(4))
+
+
+class Augmenter:
+    """--augment: one record per pair from draw_params (seeded: --aug_seed + rank), one augment_pairs launch per batch.  Takes the
+    host batch of whole frames as batches() yields it and returns (images_0, images_1, flows_gt, valid) on the GPU: float32
+    frames in [0, 1] at --crop_shape, the transformed flow and its mask (None, None without flows)."""
+
+    def __init__(self, args, rank=0):
+        self.crop = tuple(args.crop_shape)
+        self.rng = np.random.RandomState(args.aug_seed + rank)
+        self.kw = dict(scale=tuple(args.aug_scale), rotate_deg=args.aug_rotate, translate_frac=args.aug_translate, flip=args.aug_flip,
+                       rel_rotate_deg=args.aug_rel_rotate, rel_translate_px=args.aug_rel_translate, color=args.augment == "full")
+
+    def __call__(self, images_0, images_1, flows=None, valid=None):
+        from pwcnet_amd import augment_pairs, draw_params
+        N, H, W, _ = images_0.shape
+        params = draw_params(N, (H, W), self.crop, self.rng, **self.kw)
+        if flows is not None:
+            flows = flows.cuda()
+            valid = None if valid is None or bool(valid.all()) else valid.cuda()
+        return augment_pairs(images_0.cuda(), images_1.cuda(), params, self.crop, flows=flows, valid=valid)
 
 
 def validate(args, weights, ds, val_idx, dist=None):
@@ -131,8 +169,9 @@ def validate(args, weights, ds, val_idx, dist=None):
                                    len(val_idx), batch=args.batch_size, dist=dist, device="cuda", metrics=True)
 
 
-def train_unsup(args, ds, train_idx, val_idx):
-    """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet."""
+def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
+    """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet.
+    aug (an Augmenter, --augment): `ds` holds whole frames, the batch is cut and jittered on the GPU, validation reads val_ds."""
     from pwcnet_amd import PWCDCNetModule, ckpt
     from pwcnet_amd.unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss
     term = "census" if args.photo == "census" else "photometric"
@@ -156,8 +195,11 @@ def train_unsup(args, ds, train_idx, val_idx):
         order = np.random.RandomState(1000 + e).permutation(train_idx)
         steps = len(order) // args.batch_size
         t0, loss_sum, n_steps = time.time(), 0.0, 0
-        for images_0, images_1, _, _ in batches(ds, order[:steps * args.batch_size], args.batch_size):
-            images_0, images_1 = (images_0 / 255.0).cuda(), (images_1 / 255.0).cuda()
+        for images_0, images_1, _, _ in batches(ds, order[:steps * args.batch_size], args.batch_size, same_size=aug is not None):
+            if aug is not None:
+                images_0, images_1, _, _ = aug(images_0, images_1)
+            else:
+                images_0, images_1 = (images_0 / 255.0).cuda(), (images_1 / 255.0).cuda()
             opt.zero_grad(set_to_none=True)
             if args.occlusion == "fb":
                 # both pair orders in one forward: the first N flows are 0 -> 1, the last N are 1 -> 0
@@ -188,7 +230,7 @@ def train_unsup(args, ds, train_idx, val_idx):
             n_steps += 1
             loss_sum += float(loss)
             print(f"step {global_step}: loss/unsup {float(loss):.6f}  {term} {float(photo):.6f}  smoothness {float(smooth):.6f}{tail}")
-        res = validate(args, model.tf_state_dict(), ds, val_idx)
+        res = validate(args, model.tf_state_dict(), ds if val_ds is None else val_ds, val_idx)
         dt = time.time() - t0
         print(f"epoch {e + 1}: loss/unsup {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
               f"Fl-all/val {res['fl_all']:.4f}  "
@@ -245,6 +287,20 @@ def main():
     ap.add_argument("--synthetic_pairs", type=int, default=64, help="pairs per epoch with --dataset synthetic")
     ap.add_argument("--synthetic_invalid", type=float, default=0.0,
                     help="fraction of the synthetic ground truth knocked out (mask False, flow 1e10) [0]")
+    ap.add_argument("--augment", default="none", choices=["none", "geometric", "full"],
+                    help="training batches prepared on the GPU from whole uint8 frames: geometric = random zoom, rotation, "
+                         "translation, mirror and a small relative transform of the second frame, the flow transformed with them; "
+                         "full = that and colour jitter; none = the host crop [none]")
+    ap.add_argument("--aug_scale", nargs=2, type=float, default=[0.9, 1.3], metavar=("LO", "HI"), help="--augment: zoom range [0.9 1.3]")
+    ap.add_argument("--aug_rotate", type=float, default=10.0, metavar="DEG", help="--augment: rotation within +-DEG [10]")
+    ap.add_argument("--aug_translate", type=float, default=0.1, metavar="FRAC",
+                    help="--augment: the crop's centre moves within +-FRAC of the frame's width and height [0.1]")
+    ap.add_argument("--aug_flip", type=float, default=0.5, metavar="P", help="--augment: probability of a left-right mirror [0.5]")
+    ap.add_argument("--aug_rel_rotate", type=float, default=1.0, metavar="DEG",
+                    help="--augment: extra rotation of the second frame within +-DEG [1]")
+    ap.add_argument("--aug_rel_translate", type=float, default=2.0, metavar="PX",
+                    help="--augment: extra shift of the second frame within +-PX pixels [2]")
+    ap.add_argument("--aug_seed", type=int, default=0, help="--augment: seed of the draws (+ rank) [0]")
     ap.add_argument("--val_fraction", type=float, default=0.1)
     ap.add_argument("--model_dir", type=str, default="./model")
     args = ap.parse_args()
@@ -267,6 +323,10 @@ def main():
         ap.error("--consistency_weight needs --occlusion fb (the term reads the forward and the backward flow of one forward)")
     if args.smooth_order != 1 and args.loss != "unsup":
         ap.error("--smooth_order belongs to --loss unsup")
+    if not 0 < args.aug_scale[0] <= args.aug_scale[1]:
+        ap.error("--aug_scale LO HI must satisfy 0 < LO <= HI")
+    if min(args.aug_rotate, args.aug_translate, args.aug_rel_rotate, args.aug_rel_translate) < 0 or not 0 <= args.aug_flip <= 1:
+        ap.error("--aug_rotate, --aug_translate, --aug_rel_rotate, --aug_rel_translate must be non-negative, --aug_flip in [0, 1]")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -301,11 +361,20 @@ def main():
         if not pairs:
             raise SystemExit(f"train.py: no frame pairs with flow found under {args.dataset_dir}")
         ds = FilePairs(pairs, tuple(args.crop_shape), args.crop_type)
+    aug = val_ds = None
+    if args.augment != "none":
+        # training reads whole uint8 frames and cuts them on the GPU; validation keeps the data set above
+        aug, val_ds = Augmenter(args, rank), ds
+        if args.dataset == "synthetic":
+            ds = SyntheticPairs(args.synthetic_pairs, (args.crop_shape[0] + 64, args.crop_shape[1] + 64),
+                                invalid=args.synthetic_invalid, uint8=True)
+        else:
+            ds = FilePairs(pairs, tuple(args.crop_shape), args.crop_type, whole=True)
     n_val = max(1, int(len(ds) * args.val_fraction))
     perm = np.random.RandomState(0).permutation(len(ds))
     val_idx, train_idx = perm[:n_val], perm[n_val:]
     if args.loss == "unsup":
-        return train_unsup(args, ds, train_idx, val_idx)
+        return train_unsup(args, ds, train_idx, val_idx, val_ds, aug)
 
     trainer = Trainer(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                       use_dc=args.use_dc, output_level=args.output_level, weights=args.weights, gamma=args.gamma,
@@ -324,13 +393,18 @@ def main():
             dist.all_reduce(st, op=dist.ReduceOp.MIN)
             steps = int(st.item())
         t0, loss_sum, n_steps = time.time(), 0.0, 0
-        for images_0, images_1, flows_gt, valid in batches(ds, order[lo:lo + steps * args.batch_size], args.batch_size):
+        for images_0, images_1, flows_gt, valid in batches(ds, order[lo:lo + steps * args.batch_size], args.batch_size,
+                                                           same_size=aug is not None):
             # a dense batch takes the step without a mask (the same kernels as before masks existed)
-            loss = trainer.step((images_0 / 255.0).cuda(), (images_1 / 255.0).cuda(), flows_gt.cuda(),
-                                None if bool(valid.all()) else valid.cuda())
+            if aug is not None:
+                images_0, images_1, flows_gt, valid = aug(images_0, images_1, flows_gt, valid)
+                loss = trainer.step(images_0, images_1, flows_gt, None if bool(valid.all()) else valid)
+            else:
+                loss = trainer.step((images_0 / 255.0).cuda(), (images_1 / 255.0).cuda(), flows_gt.cuda(),
+                                    None if bool(valid.all()) else valid.cuda())
             loss_sum += float(loss)
             n_steps += 1
-        res = validate(args, trainer.state_dict(), ds, val_idx, dist)
+        res = validate(args, trainer.state_dict(), ds if val_ds is None else val_ds, val_idx, dist)
         if rank == 0:
             dt = time.time() - t0
             print(f"epoch {e + 1}: loss/pwc {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
