@@ -700,6 +700,50 @@ int pwc_census_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_
                         float c1, float c2, float eps, float q, const float* dsums, float* workspace,
                         size_t workspace_floats, float* dflow, int dflow_cs, int accumulate, pwc_stream_t stream);
 
+/* SSIM term: the data term of UFlow / ARFlow (0.15 L1 + 0.85 SSIM).  x(p, c) = images_0[p, c]; y(p, c) = the photometric term's
+ * bilinear sample of images_1 at p moved by flow_scale * flow[p] -- its in-frame rule (0 <= px <= W - 1, 0 <= py <= H - 1, a
+ * non-finite flow is out of frame), floor, clipped corners and weights; sample point, weights and blend in double, rounded to
+ * fp32 once.  Per channel, over the n = (2 radius + 1)^2 pixels of the window of centre p, in double from the fp32 x and y and
+ * in the CENTRED form, so that a variance cannot go negative:
+ *   mu_x = mean x, mu_y = mean y, s_x = mean (x - mu_x)^2, s_y = mean (y - mu_y)^2, s_xy = mean (x - mu_x)(y - mu_y),
+ *   A1 = 2 mu_x mu_y + c1, A2 = 2 s_xy + c2, B1 = mu_x^2 + mu_y^2 + c1, B2 = s_x + s_y + c2,
+ *   SSIM = A1 A2 / (B1 B2),   term(p, c) = (1 - SSIM) / 2.
+ * No clamp (|SSIM| <= 1 up to rounding), no eps and no q: the term is not passed through rho.  c1 = 0.01^2, c2 = 0.03^2 for
+ * images in [0, 1]; radius 1 is the 3 x 3 window of UFlow / ARFlow.  A centre p CONTRIBUTES iff it is at least `radius` pixels
+ * from every border (no padding), (valid == NULL or valid[p] != 0), and the sample point of EVERY pixel of its window is in
+ * frame.  This differs from the census term: a zero inside an SSIM window would wreck its means and variances, so an
+ * out-of-frame or non-finite pixel switches off every window it belongs to; `valid` still selects centres only.
+ * out_sums[n] = sum over the contributing centres of sum_c term(p, c), out_counts[n] = their number (exact); H <= 2 radius or
+ * W <= 2 radius: both 0, no error.  Launches as for the census term: a per-pixel pass (the C planes of y and the in-frame byte
+ * to workspace), a windowed pass over 32 x 8 tiles of centres with a `radius` halo of x, y and the flag staged in the LDS, tile
+ * terms added in a fixed tree, the parts in index order: two calls give the same bits.
+ * workspace: at least pwc_ssim_workspace_floats(N, H, W, C, with_grad) floats, with_grad 0 for the sums and 1 for the gradient:
+ *   2 * N * parts + (with_grad ? 9 : 1) * C * N * H * W + (N * H * W + 3) / 4 + (with_grad ? 1 : 0),
+ * parts = min(256, ceil(W / 32) * ceil(H / 8)) -- the part sums and counts, the planes of y (gradient: and of its two
+ * derivatives), the in-frame bytes, and (gradient) three planes of doubles per channel behind one float of slack for their
+ * alignment.  Checks, in this order: null pointers and sizes <= 0 (PWC_EINVAL); C outside 1..4 or radius outside 1..3
+ * (PWC_EUNSUPPORTED); a channel stride below the channel count, c1 or c2 <= 0 or NaN (PWC_EINVAL); H * W >= 2^31 or N > 65535
+ * (PWC_ERANGE); a null or short workspace, null outputs (PWC_EINVAL). */
+size_t pwc_ssim_workspace_floats(int N, int H, int W, int C, int with_grad);
+int pwc_ssim_sums_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
+                      float flow_scale, const uint8_t* valid, int N, int H, int W, int C, int radius, float c1, float c2,
+                      float* workspace, size_t workspace_floats, float* out_sums, int32_t* out_counts,
+                      pwc_stream_t stream);
+/* dflow (+)= the gradient of sum_n dsums[n] * out_sums[n] w.r.t. the flow (the images are constants; floor and clip carry no
+ * gradient).  With S = SSIM, for a pixel q in the window of centre p:
+ *   dS/dy_q = (1/n) [2 mu_x A2 / (B1 B2) + 2 (x_q - mu_x) A1 / (B1 B2) - 2 S mu_y / B1 - 2 S (y_q - mu_y) / B2]
+ *           = alpha_p + beta_p x_q + gamma_p y_q,
+ * linear in x_q and y_q, so the gather splits: dL/dy(q) = -1/2 dsums[n] (sum_p alpha_p + x_q sum_p beta_p + y_q sum_p gamma_p)
+ * over the contributing centres within `radius` of q -- one per-centre pass that writes the three coefficients per channel (as
+ * doubles: they cancel), then box sums over the same tiles -- and
+ *   dflow[q] = flow_scale * sum_c dL/dy_c(q) * (d sample_c / d px, d sample_c / d py).
+ * A q that is out of frame, or has no contributing centre within `radius`, gets exactly 0 (accumulate == 0) or is left
+ * untouched (accumulate != 0).  No atomics: two calls give the same bits.  dsums: N floats on the device. */
+int pwc_ssim_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
+                      float flow_scale, const uint8_t* valid, int N, int H, int W, int C, int radius, float c1, float c2,
+                      const float* dsums, float* workspace, size_t workspace_floats, float* dflow, int dflow_cs,
+                      int accumulate, pwc_stream_t stream);
+
 /* ==== occlusion: forward-backward consistency of two flows (the `valid` masks of the data terms above, and the consistency term) ====
  * flow_a is the flow 0 -> 1, flow_b the flow 1 -> 0, both NHWC fp32 with 2 channels at channel strides a_cs, b_cs >= 2 (scalar
  * loads, no alignment asked).  For direction a, pixel p = (n, y, x): f = flow_scale * flow_a[p], (px, py) = (x + f0, y + f1);

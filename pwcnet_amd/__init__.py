@@ -7,7 +7,8 @@ from .model import PWCDCNet  # noqa: F401
 from .pipeline import ForwardPipeline  # noqa: F401
 from .autograd import PWCDCNetModule  # noqa: F401
 from .unsup import (census_grad, census_loss, census_sums, fb_consistency_grad, fb_consistency_loss,  # noqa: F401
-                    fb_consistency_sums, fb_valid, photometric_loss, photometric_sums, smoothness_loss, smoothness_sums)
+                    fb_consistency_sums, fb_valid, photometric_loss, photometric_sums, smoothness_loss, smoothness_sums,
+                    ssim_grad, ssim_loss, ssim_sums)
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
 from .augment import augment_pairs, crop_params, draw_params  # noqa: F401
 from .modules import (ContextNetwork, CostVolumeLayer, FeaturePyramidExtractor_custom,  # noqa: F401
@@ -15,6 +16,6 @@ from .modules import (ContextNetwork, CostVolumeLayer, FeaturePyramidExtractor_c
 
 __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtractor_custom", "WarpingLayer", "CostVolumeLayer",
            "OpticalFlowEstimator_custom", "ContextNetwork", "resize_bilinear", "photometric_sums", "photometric_loss",
-           "smoothness_sums", "smoothness_loss", "census_sums", "census_loss", "census_grad", "fb_valid",
+           "smoothness_sums", "smoothness_loss", "census_sums", "census_loss", "census_grad", "ssim_sums", "ssim_loss", "ssim_grad", "fb_valid",
            "fb_consistency_sums", "fb_consistency_loss", "fb_consistency_grad", "FitInfo", "fit_frames", "fit_info",
            "refit_flow", "flow_any_size", "draw_params", "crop_params", "augment_pairs"]

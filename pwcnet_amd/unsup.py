@@ -8,6 +8,9 @@
     census_sums(images_0, images_1, flows, ...)        -> (sums (N,), counts (N,) int32)
     census_loss(...)                                    -> sums.sum() / counts.sum().clamp(min=1)
 
+    ssim_sums(images_0, images_1, flows, ...)          -> (sums (N,), counts (N,) int32)
+    ssim_loss(...)                                      -> sums.sum() / (C * counts.sum().clamp(min=1))
+
     fb_valid(flows_fw, flows_bw, ...)                   -> (mask_fw, mask_bw) torch.bool (N,H,W) [, counts_fw, counts_bw int32 (N,)]
     fb_consistency_sums(flows_fw, flows_bw, ...)        -> (sums_fw, counts_fw, sums_bw, counts_bw)
     fb_consistency_loss(...)                            -> (sums_fw.sum() + sums_bw.sum()) / (2 * (counts_fw.sum() + counts_bw.sum()).clamp(min=1))
@@ -20,6 +23,8 @@ rho(d flow) over the forward differences along x and y (include/pwc_hip.h, "self
 reproducible), so the losses compose with PWCDCNetModule; the images are constants -- an image that requires grad is refused.
 The census term compares the local intensity ORDER in a (2 radius + 1)^2 window of the grey images instead of the intensities
 (csrc/pwc_census.hip; the formulas are in census_sums' docstring), so a brightness change between the frames does not pull the flow.
+The SSIM term is (1 - SSIM) / 2 of images_0 and the warped images_1 in the same windows, per channel (csrc/pwc_ssim.hip; ssim_sums'
+docstring): the data term of UFlow / ARFlow, 0.15 * photometric_loss(q=0.5) + 0.85 * ssim_loss.
 No double backward.
 fb_valid makes the occlusion masks that go into `valid`: the forward-backward consistency check of two flows (csrc/pwc_fbcheck.hip;
 the definition is in its docstring).  It is not differentiable: the masks are constants.
@@ -198,6 +203,70 @@ class _CensusSums(torch.autograd.Function):
         return dflow, None, None, None, None, None
 
 
+def _check_ssim(radius, c1, c2, what):
+    if isinstance(radius, bool) or not isinstance(radius, int) or radius not in (1, 2, 3):
+        raise ValueError(f"{what}: radius must be 1, 2 or 3, got {radius!r}")
+    c1, c2 = float(c1), float(c2)
+    for name, v in (("c1", c1), ("c2", c2)):
+        if not v > 0.0:
+            raise ValueError(f"{what}: {name} must be positive, got {v}")
+    return radius, c1, c2
+
+
+def ssim_grad(images_0, images_1, flows, dsums, dflow=None, flow_scale=1.0, valid=None, radius=1, c1=1e-4, c2=9e-4,
+              accumulate=False):
+    """dflow (+)= the gradient of (dsums * ssim_sums(...)[0]).sum() w.r.t. flows (pwc_ssim_grad_f32); dsums: (N,) on the GPU.
+    dflow None: a new tensor; accumulate: added onto dflow, pixels that are out of frame or have no contributing centre within
+    `radius` are left alone (without it they get 0).  Returns dflow.  What the autograd backward of ssim_sums calls."""
+    radius, c1, c2 = _check_ssim(radius, c1, c2, "ssim_grad")
+    _check_census_tensors(images_0, images_1, flows, valid)
+    vp = None if valid is None else mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+    fv, flows = as_view(flows, "flows")
+    v0, images_0 = as_view(images_0, "images_0")
+    v1, images_1 = as_view(images_1, "images_1")
+    L = _lib.lib()
+    up = torch.empty((fv.N,), dtype=torch.float32, device=flows.device).copy_(dsums)       # contiguous float32, its own
+    dv, dflow = _dflow_view(dflow, fv, flows.device)
+    ws = torch.empty((max(L.pwc_ssim_workspace_floats(fv.N, fv.H, fv.W, v0.C, 1), 1),), dtype=torch.float32, device=flows.device)
+    _lib.check(L.pwc_ssim_grad_f32(_p(v0.ptr), v0.cs, _p(v1.ptr), v1.cs, _p(fv.ptr), fv.cs, float(flow_scale), vp, fv.N, fv.H,
+                                   fv.W, v0.C, radius, c1, c2, _p(up.data_ptr()), _p(ws.data_ptr()), ws.numel(), _p(dv.ptr), dv.cs,
+                                   1 if accumulate else 0, _lib.current_stream()), "ssim grad")
+    return dflow
+
+
+class _SsimSums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, images_0, images_1, flow_scale, valid, consts):
+        ctx.set_materialize_grads(False)
+        radius, c1, c2 = consts
+        vp = None if valid is None else mask_ptr(valid, flows.shape[0], flows.shape[1], flows.shape[2], flows.device)
+        fv, flows = as_view(flows, "flows")
+        v0, images_0 = as_view(images_0, "images_0")
+        v1, images_1 = as_view(images_1, "images_1")
+        L = _lib.lib()
+        dev = flows.device
+        sums = torch.empty((fv.N,), dtype=torch.float32, device=dev)
+        counts = torch.empty((fv.N,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(L.pwc_ssim_workspace_floats(fv.N, fv.H, fv.W, v0.C, 0), 1),), dtype=torch.float32, device=dev)
+        _lib.check(L.pwc_ssim_sums_f32(_p(v0.ptr), v0.cs, _p(v1.ptr), v1.cs, _p(fv.ptr), fv.cs, flow_scale, vp, fv.N, fv.H, fv.W,
+                                       v0.C, radius, c1, c2, _p(ws.data_ptr()), ws.numel(), _p(sums.data_ptr()),
+                                       _p(counts.data_ptr()), _lib.current_stream()), "ssim sums")
+        ctx.save_for_backward(flows, images_0, images_1)
+        ctx.valid, ctx.consts = valid, (flow_scale,) + tuple(consts)
+        ctx.mark_non_differentiable(counts)
+        return sums, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dsums, _dcounts):
+        if dsums is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        flows, images_0, images_1 = ctx.saved_tensors
+        flow_scale, radius, c1, c2 = ctx.consts
+        dflow = ssim_grad(images_0, images_1, flows, dsums, None, flow_scale, ctx.valid, radius, c1, c2)
+        return dflow, None, None, None, None, None
+
+
 class _PhotometricSums(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flows, images_0, images_1, flow_scale, valid, eps, q):
@@ -337,6 +406,32 @@ def census_loss(images_0, images_1, flows, flow_scale=1.0, valid=None, radius=3,
     """0-dim: the mean of rho(h) over the contributing pixels; 0 when no pixel contributes."""
     sums, counts = census_sums(images_0, images_1, flows, flow_scale, valid, radius, scale, c1, c2, eps, q)
     return sums.sum() / counts.sum().clamp(min=1).to(torch.float32)
+
+
+def ssim_sums(images_0, images_1, flows, flow_scale=1.0, valid=None, radius=1, c1=1e-4, c2=9e-4):
+    """(sums (N,) float32, counts (N,) int32) of the SSIM term, the data term of UFlow / ARFlow.  x = images_0, y = images_1
+    sampled at the pixel moved by flow_scale * flows (photometric_sums' sample and in-frame rule; a flow that is not finite is
+    out of frame).  Per channel, over the n = (2 radius + 1)^2 pixels of the window of centre p, in double and centred:
+        mu_x = mean x,  mu_y = mean y,  s_x = mean (x - mu_x)^2,  s_y = mean (y - mu_y)^2,  s_xy = mean (x - mu_x)(y - mu_y),
+        SSIM = (2 mu_x mu_y + c1)(2 s_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(s_x + s_y + c2)),  term(p, c) = (1 - SSIM) / 2,
+    no clamp, no eps and no q (the term is not passed through rho).  sums[n] = the sum of term(p, c) over the contributing
+    centres and the channels, counts[n] the number of contributing centres.  A centre contributes when it is at least `radius`
+    pixels from every border (no padding), valid[p] is set (valid: (N,H,W) torch.bool / torch.uint8, None = all), and every
+    pixel of the window must be in frame: UNLIKE census_sums, where a neighbour is always read, one out-of-frame or non-finite
+    pixel switches off every window it belongs to (a zero inside a window would wreck its means and variances).  `valid` still
+    selects centres only, so the images must hold numbers at masked pixels.  H <= 2 radius or W <= 2 radius: counts and sums
+    are 0, no error.  images: (N,H,W,C), C = 1..4, nominally in [0, 1] (c1 = 0.01^2, c2 = 0.03^2 are SSIM's constants for that
+    range); radius: 1 (the 3 x 3 window of UFlow / ARFlow), 2 or 3.  sums is differentiable w.r.t. flows (pwc_ssim_grad_f32: a
+    gather, bit reproducible); the images are constants."""
+    consts = _check_ssim(radius, c1, c2, "ssim_sums")
+    _check_census_tensors(images_0, images_1, flows, valid)
+    return _SsimSums.apply(flows, images_0, images_1, float(flow_scale), valid, consts)
+
+
+def ssim_loss(images_0, images_1, flows, flow_scale=1.0, valid=None, radius=1, c1=1e-4, c2=9e-4):
+    """0-dim: the mean of (1 - SSIM) / 2 over the contributing centres and the channels; 0 when no centre contributes."""
+    sums, counts = ssim_sums(images_0, images_1, flows, flow_scale, valid, radius, c1, c2)
+    return sums.sum() / (images_0.shape[3] * counts.sum().clamp(min=1)).to(torch.float32)
 
 
 def fb_valid(flows_fw, flows_bw, flow_scale=1.0, alpha1=0.01, alpha2=0.5, valid_fw=None, valid_bw=None, return_counts=False):

@@ -20,6 +20,11 @@ smoothness_loss(flows_final, images_0) (pwcnet_amd/unsup.py: images_1 warped by 
 edge-aware first-order smoothness of the flow).  Ground truth, where the data set has it, is used for the validation line only.
 `--photo census` replaces the data term by census_loss(flows_final, radius=--census_radius): the soft census (ternary) term on the
 local intensity order, which a brightness change between the frames does not move.
+`--ssim_weight W` (0 <= W <= 1) blends the SSIM term into the data term: (1 - W) * <the --photo term> + W * ssim_loss(flows_final,
+radius=--ssim_radius), (1 - SSIM) / 2 per channel over the (2r+1)^2 windows every pixel of which is in frame -- in both directions and
+under the masks with --occlusion fb.  The step line then prints `ssim <value>` after the base term's value; W = 1 computes and
+prints no base term, W = 0 (the default) no SSIM: the run as it was.  `--photo charbonnier --ssim_weight 0.85` is ARFlow's
+first-stage data term (0.15 L1 + 0.85 SSIM, 3 x 3 windows); UFlow and ARFlow's second stage add the census term.
 `--occlusion fb` leaves occluded pixels out of the data term: ONE module forward on the pairs in both orders stacked along the
 batch axis (batch 2N) gives the forward and the backward flow, fb_valid (pwcnet_amd/unsup.py; --occ_alpha1, --occ_alpha2, UnFlow's
 forward-backward check) turns them into two masks -- constants, no gradient goes through them -- and the loss is the data term
@@ -173,13 +178,18 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
     """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet.
     aug (an Augmenter, --augment): `ds` holds whole frames, the batch is cut and jittered on the GPU, validation reads val_ds."""
     from pwcnet_amd import PWCDCNetModule, ckpt
-    from pwcnet_amd.unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss
+    from pwcnet_amd.unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss, ssim_loss
     term = "census" if args.photo == "census" else "photometric"
 
     def data_term(i0, i1, flows, valid=None):
         if args.photo == "census":
             return census_loss(i0, i1, flows, valid=valid, radius=args.census_radius)
         return photometric_loss(i0, i1, flows, valid=valid, eps=args.photo_eps, q=args.photo_q)
+
+    def ssim_term(i0, i1, flows, valid=None):
+        return ssim_loss(i0, i1, flows, valid=valid, radius=args.ssim_radius)
+
+    w_ssim = args.ssim_weight                 # 0: the --photo term alone (the run as it was), 1: SSIM alone, no base term
 
     def smooth_term(flows, images):
         return smoothness_loss(flows, images, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q, order=args.smooth_order)
@@ -209,7 +219,10 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
                 with torch.no_grad():
                     m_fw, m_bw, c_fw, c_bw = fb_valid(fw.detach(), bw.detach(), alpha1=args.occ_alpha1, alpha2=args.occ_alpha2,
                                                       return_counts=True)
-                photo = 0.5 * (data_term(images_0, images_1, fw, m_fw) + data_term(images_1, images_0, bw, m_bw))
+                if w_ssim < 1:
+                    photo = 0.5 * (data_term(images_0, images_1, fw, m_fw) + data_term(images_1, images_0, bw, m_bw))
+                if w_ssim > 0:
+                    ssim = 0.5 * (ssim_term(images_0, images_1, fw, m_fw) + ssim_term(images_1, images_0, bw, m_bw))
                 smooth = 0.5 * (smooth_term(fw, images_0) + smooth_term(bw, images_1))
                 occluded = 1.0 - float(c_fw.sum() + c_bw.sum()) / float(m_fw.numel() + m_bw.numel())
                 tail = f"  occluded {occluded:.4f}"
@@ -217,10 +230,14 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
                     consistency = fb_consistency_loss(fw, bw, valid_fw=m_fw, valid_bw=m_bw, eps=args.photo_eps, q=args.photo_q)
             else:
                 flows_final, _ = model(images_0, images_1)
-                photo = data_term(images_0, images_1, flows_final)
+                if w_ssim < 1:
+                    photo = data_term(images_0, images_1, flows_final)
+                if w_ssim > 0:
+                    ssim = ssim_term(images_0, images_1, flows_final)
                 smooth = smooth_term(flows_final, images_0)
                 tail = ""
-            loss = photo + args.smooth_weight * smooth
+            data = photo if w_ssim == 0 else ssim if w_ssim == 1 else (1.0 - w_ssim) * photo + w_ssim * ssim
+            loss = data + args.smooth_weight * smooth
             if args.consistency_weight > 0:
                 loss = loss + args.consistency_weight * consistency
                 tail += f"  consistency {float(consistency.detach()):.6f}"
@@ -229,7 +246,8 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
             global_step += 1
             n_steps += 1
             loss_sum += float(loss)
-            print(f"step {global_step}: loss/unsup {float(loss):.6f}  {term} {float(photo):.6f}  smoothness {float(smooth):.6f}{tail}")
+            terms = (f"  {term} {float(photo):.6f}" if w_ssim < 1 else "") + (f"  ssim {float(ssim):.6f}" if w_ssim > 0 else "")
+            print(f"step {global_step}: loss/unsup {float(loss):.6f}{terms}  smoothness {float(smooth):.6f}{tail}")
         res = validate(args, model.tf_state_dict(), ds if val_ds is None else val_ds, val_idx)
         dt = time.time() - t0
         print(f"epoch {e + 1}: loss/unsup {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
@@ -260,6 +278,11 @@ def main():
                     help="--loss unsup: the data term, Charbonnier on intensities or soft census on their local order [charbonnier]")
     ap.add_argument("--census_radius", type=int, default=3, choices=[1, 2, 3],
                     help="--photo census: window radius, (2r+1)^2 - 1 neighbours [3]")
+    ap.add_argument("--ssim_weight", type=float, default=0.0, metavar="W",
+                    help="--loss unsup: the data term becomes (1 - W) * <the --photo term> + W * SSIM term, W in [0, 1]; "
+                         "--photo charbonnier --ssim_weight 0.85 is ARFlow's 0.15 L1 + 0.85 SSIM [0]")
+    ap.add_argument("--ssim_radius", type=int, default=1, choices=[1, 2, 3],
+                    help="--ssim_weight: window radius, (2r+1)^2 pixels; 1 is the 3 x 3 window of UFlow / ARFlow [1]")
     ap.add_argument("--occlusion", default="none", choices=["none", "fb"],
                     help="--loss unsup: none, or fb: forward-backward consistency masks on the data term, both directions "
                          "trained from one forward at batch 2N [none]")
@@ -321,6 +344,10 @@ def main():
         ap.error("--consistency_weight must be non-negative")
     if args.consistency_weight > 0 and args.occlusion != "fb":
         ap.error("--consistency_weight needs --occlusion fb (the term reads the forward and the backward flow of one forward)")
+    if not 0.0 <= args.ssim_weight <= 1.0:
+        ap.error("--ssim_weight must be in [0, 1]")
+    if args.ssim_weight > 0 and args.loss != "unsup":
+        ap.error("--ssim_weight belongs to --loss unsup")
     if args.smooth_order != 1 and args.loss != "unsup":
         ap.error("--smooth_order belongs to --loss unsup")
     if not 0 < args.aug_scale[0] <= args.aug_scale[1]:
