@@ -810,6 +810,53 @@ int pwc_fb_consistency_grad_f32(const float* flow_a, int a_cs, const float* flow
                                 float* dflow_a, int dflow_a_cs, float* dflow_b, int dflow_b_cs, int accumulate,
                                 pwc_stream_t stream);
 
+/* ==== forward splatting: the pixels of a frame moved to where the flow sends them (a scatter; range-map occlusion) ====
+ * x: N x H x W records of x_cs >= C floats, C of them used (C == 0: x may be NULL, only the coverage is computed); flow: NHWC fp32
+ * with 2 channels at channel stride flow_cs >= 2; w: N x H x W floats, the weight of each SOURCE pixel, or NULL (1); valid:
+ * N x H x W bytes, the source mask, or NULL (every pixel).  Scalar loads, no alignment asked of them.
+ * Source pixel p = (n, y, x) has the target point px = x + flow_scale * flow[p,0], py = y + flow_scale * flow[p,1], formed in
+ * double (flow_scale is a float: the product is exact).  It CONTRIBUTES iff its mask passes and px > -1, px < W, py > -1, py < H
+ * (a NaN or Inf fails the test).  x0 = floor(px), wx = px - x0, likewise y; corner (y0 + dy, x0 + dx), dx, dy in {0, 1}, carries
+ * b = (dx ? wx : 1 - wx) * (dy ? wy : 1 - wy) in double, and EACH corner receives b * w * x[p,c] on its own iff it lies inside the
+ * frame: a point half a pixel outside still splats onto the border (UFlow's range map, softmax splatting).  Nothing is clamped.
+ *   out[t,c] = sum of b * w * x[p,c] over the contributions that reach t;  coverage[t] = sum of b * w  (the splatted w).
+ * normalize != 0: out[t,c] = that sum / coverage's sum, formed in double and rounded once, where the coverage's sum is > 0, and 0
+ * elsewhere (average splatting; w = exp(alpha z): softmax splatting).  coverage is written either way; with w NULL it is the
+ * RANGE MAP of the flow (the number of source pixels that land on t, bilinearly).
+ * Several sources share a target, so the sums are 64-bit FIXED-POINT integers of 2^-36 steps in `workspace` -- N * H * W * C
+ * numerators, N * H * W denominators, one poison word -- added by integer atomics: the order in which they land cannot change a
+ * bit, two calls give the same bits.  Three steps on the stream: the accumulators are zeroed, one launch over the source pixels
+ * scatters, one launch over the target pixels converts every accumulator once ((double)v * 2^-36).  RANGE: a contribution below
+ * 2^-37 vanishes; one that is not finite or reaches 2^26 raises the poison word, and EVERY element of out and coverage is then
+ * NaN (a flag, no fault); an element whose sum reaches 2^61 is NaN.  No host synchronisation, no process-wide state.
+ * workspace: 8-byte aligned, at least pwc_splat_workspace_bytes(N, H, W, C) = 8 * (N * H * W * (C + 1) + 1) bytes (0 for sizes
+ * that are refused).  It holds the accumulators after the call: pwc_splat_grad_f32 reads them when normalize != 0.
+ * Checks, all before any launch, in this order: a null flow, N, H, W <= 0, C < 0, a null x with C > 0 (PWC_EINVAL); C > 64
+ * (PWC_EUNSUPPORTED); flow_cs < 2, x_cs < C (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); a null coverage, with C > 0
+ * a null out or out_cs < C (PWC_EINVAL); a null workspace (PWC_EINVAL), one off an 8-byte boundary (PWC_EALIGN), a short one
+ * (PWC_EINVAL). */
+size_t pwc_splat_workspace_bytes(int N, int H, int W, int C);
+int pwc_splat_f32(const float* x, int x_cs, const float* flow, int flow_cs, float flow_scale, const float* w,
+                  const uint8_t* valid, int N, int H, int W, int C, int normalize, void* workspace, size_t workspace_bytes,
+                  float* out, int out_cs, float* coverage, pwc_stream_t stream);
+/* dx, dw, dflow (+)= the gradient of sum g_out * out + sum g_cov * coverage with respect to x, w and flow; any of the three may
+ * be NULL (not all), g_out and g_cov may be NULL (zeros).  The transpose of the scatter is a GATHER: no atomics, no fixed point.
+ * Each contributing source pixel re-derives its corners and weights and forms over its in-frame corners k
+ *   S_c = sum_k b_k g[k,c],   dx[p,c] = w S_c,   dw[p] = sum_c x[p,c] S_c + sum_k b_k g_cov[k],
+ *   dflow[p,0] = flow_scale * w * (sum_c x[p,c] sum_k (db_k/dpx) g[k,c] + sum_k (db_k/dpx) g_cov[k]),  db/dpx = -+(1 - wy), -+wy,
+ *   dflow[p,1] likewise with db/dpy = -+(1 - wx), -+wx,
+ * each value in double, rounded once; floor carries no gradient.  A pixel that does not contribute gets exact zeros
+ * (accumulate == 0) or is left alone (accumulate != 0); accumulate adds exactly what a plain call writes.
+ * normalize != 0: g[k,c] above is g_out[k,c] / den_k and g_cov[k] is joined by -sum_c out[k,c] g_out[k,c] / den_k, both 0 where
+ * den_k is not positive -- with den and out = num / den read in double from `workspace`, which must hold what pwc_splat_f32 left
+ * there for the same inputs; a poisoned forward makes every gradient element NaN.  normalize == 0: workspace is not read.
+ * Checks as pwc_splat_f32's first four; then all three outputs NULL, g_cs < C with g_out, dx_cs < C with dx, dflow_cs < 2 with
+ * dflow (PWC_EINVAL); with normalize the workspace as above.  One launch. */
+int pwc_splat_grad_f32(const float* x, int x_cs, const float* flow, int flow_cs, float flow_scale, const float* w,
+                       const uint8_t* valid, int N, int H, int W, int C, int normalize, const float* g_out, int g_cs,
+                       const float* g_cov, const void* workspace, size_t workspace_bytes, float* dx, int dx_cs, float* dw,
+                       float* dflow, int dflow_cs, int accumulate, pwc_stream_t stream);
+
 /* ---- frames of any size: fit them to the network's geometry, refit the flow to the frames' grid ----
  * The network takes frames whose height and width are multiples of 64.  These two launches sit in front of and behind a forward on
  * plain dense tensors; the forward itself is not involved.

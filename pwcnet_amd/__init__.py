@@ -9,6 +9,7 @@ from .autograd import PWCDCNetModule  # noqa: F401
 from .unsup import (census_grad, census_loss, census_sums, fb_consistency_grad, fb_consistency_loss,  # noqa: F401
                     fb_consistency_sums, fb_valid, photometric_loss, photometric_sums, smoothness_loss, smoothness_sums,
                     ssim_grad, ssim_loss, ssim_sums)
+from .splat import forward_splat, range_map, range_valid, splat_grad  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
 from .augment import augment_pairs, crop_params, draw_params  # noqa: F401
 from .modules import (ContextNetwork, CostVolumeLayer, FeaturePyramidExtractor_custom,  # noqa: F401
@@ -17,5 +18,5 @@ from .modules import (ContextNetwork, CostVolumeLayer, FeaturePyramidExtractor_c
 __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtractor_custom", "WarpingLayer", "CostVolumeLayer",
            "OpticalFlowEstimator_custom", "ContextNetwork", "resize_bilinear", "photometric_sums", "photometric_loss",
            "smoothness_sums", "smoothness_loss", "census_sums", "census_loss", "census_grad", "ssim_sums", "ssim_loss", "ssim_grad", "fb_valid",
-           "fb_consistency_sums", "fb_consistency_loss", "fb_consistency_grad", "FitInfo", "fit_frames", "fit_info",
+           "fb_consistency_sums", "fb_consistency_loss", "fb_consistency_grad", "forward_splat", "splat_grad", "range_map", "range_valid", "FitInfo", "fit_frames", "fit_info",
            "refit_flow", "flow_any_size", "draw_params", "crop_params", "augment_pairs"]

@@ -35,6 +35,12 @@ is unchanged (forward flow only).
 is free), and `--consistency_weight W` (with --occlusion fb) adds W * fb_consistency_loss(fw, bw) under the two masks: UnFlow's
 third term, rho of the forward flow plus the backward flow sampled where it points to, with gradients into both flows; the step
 line then ends in `consistency <value>`.  Together with --photo census this is UnFlow's loss.
+`--occlusion range` is the same stacked 2N forward with range-map masks in place of the forward-backward check (Wang et al. 2018,
+UFlow's default for Chairs and Sintel): range_valid (pwcnet_amd/splat.py) splats a 1 from every pixel of frame 1 along the backward
+flow, and a frame-0 pixel is kept when at least --occ_min_range (0.5: a choice, nobody has trained with it yet) lands on it; the
+backward mask likewise from the forward flow.  The check of fb cannot tell "occluded" from "the flow is still wrong" and masks
+out most of the frame early in training; the range map of a poor flow still covers most of it.  The occluded fraction on the step
+line is counted from the masks, and --consistency_weight goes with either mode.
 Single process, constant learning rate; --gamma is Adam's weight_decay (the same gamma * l2_loss gradient).
 
 Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
@@ -178,6 +184,7 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
     """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet.
     aug (an Augmenter, --augment): `ds` holds whole frames, the batch is cut and jittered on the GPU, validation reads val_ds."""
     from pwcnet_amd import PWCDCNetModule, ckpt
+    from pwcnet_amd.splat import range_valid
     from pwcnet_amd.unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss, ssim_loss
     term = "census" if args.photo == "census" else "photometric"
 
@@ -211,14 +218,18 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
             else:
                 images_0, images_1 = (images_0 / 255.0).cuda(), (images_1 / 255.0).cuda()
             opt.zero_grad(set_to_none=True)
-            if args.occlusion == "fb":
+            if args.occlusion != "none":
                 # both pair orders in one forward: the first N flows are 0 -> 1, the last N are 1 -> 0
                 N = images_0.shape[0]
                 flows_final, _ = model(torch.cat([images_0, images_1]), torch.cat([images_1, images_0]))
                 fw, bw = flows_final[:N], flows_final[N:]
                 with torch.no_grad():
-                    m_fw, m_bw, c_fw, c_bw = fb_valid(fw.detach(), bw.detach(), alpha1=args.occ_alpha1, alpha2=args.occ_alpha2,
-                                                      return_counts=True)
+                    if args.occlusion == "fb":
+                        m_fw, m_bw, c_fw, c_bw = fb_valid(fw.detach(), bw.detach(), alpha1=args.occ_alpha1,
+                                                          alpha2=args.occ_alpha2, return_counts=True)
+                    else:
+                        m_fw, m_bw = range_valid(fw.detach(), bw.detach(), min_range=args.occ_min_range)
+                        c_fw, c_bw = m_fw.sum(), m_bw.sum()
                 if w_ssim < 1:
                     photo = 0.5 * (data_term(images_0, images_1, fw, m_fw) + data_term(images_1, images_0, bw, m_bw))
                 if w_ssim > 0:
@@ -283,9 +294,12 @@ def main():
                          "--photo charbonnier --ssim_weight 0.85 is ARFlow's 0.15 L1 + 0.85 SSIM [0]")
     ap.add_argument("--ssim_radius", type=int, default=1, choices=[1, 2, 3],
                     help="--ssim_weight: window radius, (2r+1)^2 pixels; 1 is the 3 x 3 window of UFlow / ARFlow [1]")
-    ap.add_argument("--occlusion", default="none", choices=["none", "fb"],
+    ap.add_argument("--occlusion", default="none", choices=["none", "fb", "range"], metavar="{none,fb}|range",
                     help="--loss unsup: none, or fb: forward-backward consistency masks on the data term, both directions "
-                         "trained from one forward at batch 2N [none]")
+                         "trained from one forward at batch 2N; range: the same forward, range-map masks (a pixel is kept when "
+                         "enough of the other frame lands on it under the opposite flow) [none]")
+    ap.add_argument("--occ_min_range", type=float, default=0.5,
+                    help="--occlusion range: a pixel is kept when its range map is at least this [0.5]")
     ap.add_argument("--occ_alpha1", type=float, default=0.01,
                     help="--occlusion fb: |f + g|^2 <= alpha1 (|f|^2 + |g|^2) + alpha2 keeps a pixel [0.01]")
     ap.add_argument("--occ_alpha2", type=float, default=0.5, help="--occlusion fb: alpha2 of that check, px^2 [0.5]")
@@ -337,13 +351,16 @@ def main():
     if not 0.0 <= args.synthetic_invalid < 1.0:
         ap.error("--synthetic_invalid must be in [0, 1)")
     if args.occlusion != "none" and args.loss != "unsup":
-        ap.error("--occlusion fb belongs to --loss unsup (the supervised losses have ground truth and its own mask)")
+        ap.error(f"--occlusion {args.occlusion} belongs to --loss unsup (the supervised losses have ground truth and its own mask)")
     if not (args.occ_alpha1 >= 0 and args.occ_alpha2 >= 0):
         ap.error("--occ_alpha1 and --occ_alpha2 must be non-negative")
+    if not args.occ_min_range >= 0:
+        ap.error("--occ_min_range must be non-negative")
     if not args.consistency_weight >= 0:
         ap.error("--consistency_weight must be non-negative")
-    if args.consistency_weight > 0 and args.occlusion != "fb":
-        ap.error("--consistency_weight needs --occlusion fb (the term reads the forward and the backward flow of one forward)")
+    if args.consistency_weight > 0 and args.occlusion == "none":
+        ap.error("--consistency_weight needs --occlusion fb or range (the term reads the forward and the backward flow of one "
+                 "forward)")
     if not 0.0 <= args.ssim_weight <= 1.0:
         ap.error("--ssim_weight must be in [0, 1]")
     if args.ssim_weight > 0 and args.loss != "unsup":
