@@ -917,6 +917,40 @@ int pwc_augment_pairs_f32(const void* im0, const void* im1, int im_is_u8, const 
                           const double* params, float* out0, float* out1, float* out_flow, unsigned char* out_valid,
                           int N, int H, int W, int OH, int OW, int flow_nearest, pwc_stream_t stream);
 
+/* ---- frame and mask pyramids: every level of a multi-scale loss from one launch ----
+ * The label-free data terms take `flow_scale` = 20 / 2^level and frames "the caller has downsampled"; these two launches are that
+ * caller.  factors: n_levels (1 .. 6) DISTINCT values out of 2, 4, 8, 16, 32, 64, in any order; outs[i] belongs to factors[i].
+ * H and W must be multiples of the largest factor given (not of 64).
+ *
+ * Frames.  x: N x H x W x C dense, C = 1 .. 4, uint8_t (x_is_u8 != 0; value v enters as the float32 nearest v / 255, as in
+ * the fit entry points above) or float32.  outs[i]: N x H/f x W/f x C dense float32, f = factors[i]:
+ *   outs[i][n, y, x, c] = (sum of x[n, f y .. f y + f - 1, f x .. f x + f - 1, c], in double) / f^2, rounded to float32 once.
+ * The order of a cell's sum is fixed by the cell: the cells of the smallest factor f0 are summed rows top to bottom, pixels left
+ * to right; every larger cell is ((a + b) + c) + d over the 2 x 2 cells of half its size, a, b the upper pair.  It does not
+ * depend on N, on the other images, or on how the launch is cut into workgroups: two calls give the same bits, an image gives
+ * the same bits alone and in a batch.  For uint8 frames every sum is exact (each summand is a multiple of 2^-31 and a sum is at
+ * most 4096: 43 bits), so the result is the correctly rounded mean whatever the order.  Every input element is read from memory
+ * once; coarser levels are built inside the workgroup from the finer sums (registers, then LDS in doubles); no atomics, no
+ * workspace, no status word.  A NaN or Inf makes the cells that contain it non-finite by plain arithmetic, and nothing else.
+ * The loads are 16 bytes wide where x, the row pitch W * C * (1 or 4) and the piece a lane loads are multiples of 16 bytes,
+ * else 4 bytes, else single bytes: the host decides, no alignment is asked of uint8 frames.
+ * Checks, before any launch, in this order: a null x or outs, N, H, W <= 0 (PWC_EINVAL); C outside 1 .. 4 (PWC_EUNSUPPORTED); a
+ * null factors, n_levels outside 1 .. 6 (PWC_EINVAL); a factor that is not one of the six (PWC_EUNSUPPORTED); a factor given
+ * twice, H or W not a multiple of the largest factor, a null outs[i] (PWC_EINVAL); a float32 x or an outs[i] off a 4-byte
+ * boundary (PWC_EALIGN); N * H * W * C >= 2^31 (PWC_ERANGE).  One launch. */
+int pwc_frame_pyramid_f32(const void* x, int x_is_u8, int N, int H, int W, int C, const int* factors, float* const* outs,
+                          int n_levels, pwc_stream_t stream);
+
+/* Masks.  valid: N x H x W bytes, non-zero = valid (the masks of the loss entry points above).  For factors[i] = f the launch
+ * counts, in integers, the non-zero bytes of every f x f block; outs[i]: N x H/f x W/f bytes, 1 where the count is at least
+ * need[i] and 0 elsewhere (need[i] = f^2: a min-pool, need[i] = 1: a max-pool); counts: NULL, or n_levels pointers each of
+ * which is NULL or N x H/f x W/f int32 that receives the counts.  The same kernel and tiles as the frames, with C = 1.
+ * Checks, in this order: a null valid, outs or need, N, H, W <= 0 (PWC_EINVAL); the factors as above; H or W not a multiple of
+ * the largest factor, a null outs[i], need[i] outside 1 .. f^2 (PWC_EINVAL); a counts[i] off a 4-byte boundary (PWC_EALIGN);
+ * N * H * W >= 2^31 (PWC_ERANGE).  One launch. */
+int pwc_mask_pyramid_u8(const unsigned char* valid, int N, int H, int W, const int* factors, const int* need,
+                        unsigned char* const* outs, int* const* counts, int n_levels, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

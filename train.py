@@ -41,6 +41,16 @@ flow, and a frame-0 pixel is kept when at least --occ_min_range (0.5: a choice, 
 backward mask likewise from the forward flow.  The check of fb cannot tell "occluded" from "the flow is still wrong" and masks
 out most of the frame early in training; the range map of a poor flow still covers most of it.  The occluded fraction on the step
 line is counted from the masks, and --consistency_weight goes with either mode.
+`--level_weights W0 W1 W2 W3 W4` (one weight per flows_pyramid entry, coarse -> fine: 1/64 .. 1/4 of the frame) puts the loss on every
+pyramid level as well, as UnFlow, DDFlow and ARFlow train PWC-Net: frame_pyramid (pwcnet_amd/pyramid.py, one launch per frame
+batch, on what the step holds after --augment) gives the block means of both frames at the five sizes, and the step adds
+sum_l W_l * (data term at level l + --smooth_weight * smoothness at level l) -- the same data, SSIM and smoothness terms on the
+level frames and flows_pyramid[l], with flow_scale = level_flow_scale (20 / 2^level: the level's own pixels; the smoothness terms
+take the flow already multiplied by it).  With --occlusion fb | range both directions are added and halved as above, under
+mask_pyramid of the two masks: a level pixel is kept when at least --occ_pool (0.5: a choice, nobody has trained with it yet) of
+its block is.  The consistency term stays on flows_final.  The step line then ends in `levels <v0> <v1> <v2> <v3> <v4>`, the
+unweighted data value of each level; a level too small for a term (a window of --census_radius 3 on a 1 x 2 level) prints nan and
+adds nothing.  Absent or all zeros: the run as it was, no pyramid launch, the same step lines.
 Single process, constant learning rate; --gamma is Adam's weight_decay (the same gamma * l2_loss gradient).
 
 Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
@@ -188,18 +198,56 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
     from pwcnet_amd.unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss, ssim_loss
     term = "census" if args.photo == "census" else "photometric"
 
-    def data_term(i0, i1, flows, valid=None):
+    def data_term(i0, i1, flows, valid=None, flow_scale=1.0):
         if args.photo == "census":
-            return census_loss(i0, i1, flows, valid=valid, radius=args.census_radius)
-        return photometric_loss(i0, i1, flows, valid=valid, eps=args.photo_eps, q=args.photo_q)
+            return census_loss(i0, i1, flows, flow_scale=flow_scale, valid=valid, radius=args.census_radius)
+        return photometric_loss(i0, i1, flows, flow_scale=flow_scale, valid=valid, eps=args.photo_eps, q=args.photo_q)
 
-    def ssim_term(i0, i1, flows, valid=None):
-        return ssim_loss(i0, i1, flows, valid=valid, radius=args.ssim_radius)
+    def ssim_term(i0, i1, flows, valid=None, flow_scale=1.0):
+        return ssim_loss(i0, i1, flows, flow_scale=flow_scale, valid=valid, radius=args.ssim_radius)
 
     w_ssim = args.ssim_weight                 # 0: the --photo term alone (the run as it was), 1: SSIM alone, no base term
 
     def smooth_term(flows, images):
         return smoothness_loss(flows, images, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q, order=args.smooth_order)
+
+    # --level_weights: None (absent or all zeros) is the run as it was, no pyramid launch
+    level_w = args.level_weights if args.level_weights and any(w != 0 for w in args.level_weights) else None
+
+    def level_terms(images_0, images_1, flows_pyramid, masks):
+        """(what the levels add to the loss, the unweighted data value per level).  masks: None, or (m_fw, m_bw) with
+        flows_pyramid from the stacked 2N forward."""
+        from pwcnet_amd.pyramid import frame_pyramid, level_flow_scale, mask_pyramid
+        N, H, W, _ = images_0.shape
+        factors = tuple(W // f.shape[2] for f in flows_pyramid)
+        pyr0, pyr1 = frame_pyramid(images_0, factors), frame_pyramid(images_1, factors)
+        if masks is not None:
+            mp_fw, mp_bw = (mask_pyramid(m, factors, min_fraction=args.occ_pool) for m in masks)
+        added, values = 0.0, []
+        for l, (wl, fl) in enumerate(zip(level_w, flows_pyramid)):
+            h, w = fl.shape[1:3]
+            scale = level_flow_scale(fl, (H, W))
+            if masks is None:
+                ways = [(pyr0[l], pyr1[l], fl, None)]
+            else:
+                ways = [(pyr0[l], pyr1[l], fl[:N], mp_fw[l]), (pyr1[l], pyr0[l], fl[N:], mp_bw[l])]
+            # a window that does not fit the level: the term would be an empty mean
+            if (w_ssim < 1 and args.photo == "census" and min(h, w) <= 2 * args.census_radius) or \
+                    (w_ssim > 0 and min(h, w) <= 2 * args.ssim_radius):
+                values.append(float("nan"))
+                continue
+            p = s = None
+            if w_ssim < 1:
+                p = sum(data_term(i0, i1, f, m, flow_scale=scale) for i0, i1, f, m in ways) / len(ways)
+            if w_ssim > 0:
+                s = sum(ssim_term(i0, i1, f, m, flow_scale=scale) for i0, i1, f, m in ways) / len(ways)
+            d = p if w_ssim == 0 else s if w_ssim == 1 else (1.0 - w_ssim) * p + w_ssim * s
+            values.append(float(d.detach()))
+            if wl != 0:
+                # the smoothness terms have no flow_scale: the flow goes in in level pixels, autograd carries the factor
+                sm = sum(smooth_term(scale * f, i0) for i0, _, f, _ in ways) / len(ways)
+                added = added + wl * (d + args.smooth_weight * sm)
+        return added, values
 
     model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                            use_dc=args.use_dc, output_level=args.output_level)
@@ -221,7 +269,7 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
             if args.occlusion != "none":
                 # both pair orders in one forward: the first N flows are 0 -> 1, the last N are 1 -> 0
                 N = images_0.shape[0]
-                flows_final, _ = model(torch.cat([images_0, images_1]), torch.cat([images_1, images_0]))
+                flows_final, flows_pyramid = model(torch.cat([images_0, images_1]), torch.cat([images_1, images_0]))
                 fw, bw = flows_final[:N], flows_final[N:]
                 with torch.no_grad():
                     if args.occlusion == "fb":
@@ -240,7 +288,7 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
                 if args.consistency_weight > 0:
                     consistency = fb_consistency_loss(fw, bw, valid_fw=m_fw, valid_bw=m_bw, eps=args.photo_eps, q=args.photo_q)
             else:
-                flows_final, _ = model(images_0, images_1)
+                flows_final, flows_pyramid = model(images_0, images_1)
                 if w_ssim < 1:
                     photo = data_term(images_0, images_1, flows_final)
                 if w_ssim > 0:
@@ -252,6 +300,11 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
             if args.consistency_weight > 0:
                 loss = loss + args.consistency_weight * consistency
                 tail += f"  consistency {float(consistency.detach()):.6f}"
+            if level_w is not None:
+                added, values = level_terms(images_0, images_1, flows_pyramid,
+                                            (m_fw, m_bw) if args.occlusion != "none" else None)
+                loss = loss + added
+                tail += "  levels " + " ".join(f"{v:.6f}" for v in values)
             loss.backward()
             opt.step()
             global_step += 1
@@ -308,6 +361,13 @@ def main():
                     help="--loss unsup: the smoothness term penalises the first or the second difference of the flow [1]")
     ap.add_argument("--consistency_weight", type=float, default=0.0,
                     help="--occlusion fb: weight of the forward-backward consistency term, gradients into both flows [0]")
+    ap.add_argument("--level_weights", nargs=5, type=float, default=None, metavar=("W0", "W1", "W2", "W3", "W4"),
+                    help="--loss unsup: the data and smoothness terms on every flows_pyramid level as well, one weight per level, "
+                         "coarse -> fine (1/64 .. 1/4 of the frame), on block-mean frame pyramids; absent or all zeros: the "
+                         "loss on flows_final alone [absent]")
+    ap.add_argument("--occ_pool", type=float, default=0.5, metavar="F",
+                    help="--level_weights with --occlusion: a level pixel is kept when at least this fraction of its block "
+                         "is, in (0, 1]; 1 is a min-pool (0.5 is a choice, nobody has trained with it yet) [0.5]")
     ap.add_argument("--photo_eps", type=float, default=1e-3, help="--loss unsup: Charbonnier epsilon of both terms [1e-3]")
     ap.add_argument("--photo_q", type=float, default=0.5, help="--loss unsup: Charbonnier exponent of both terms [0.5]")
     ap.add_argument("--edge_alpha", type=float, default=10.0,
@@ -367,6 +427,15 @@ def main():
         ap.error("--ssim_weight belongs to --loss unsup")
     if args.smooth_order != 1 and args.loss != "unsup":
         ap.error("--smooth_order belongs to --loss unsup")
+    if args.level_weights is not None:
+        if args.loss != "unsup":
+            ap.error("--level_weights belongs to --loss unsup (the supervised losses weigh the levels with --weights)")
+        if min(args.level_weights) < 0:
+            ap.error("--level_weights must be non-negative")
+        if args.output_level != 4:
+            ap.error("--level_weights takes one weight per flows_pyramid entry: five, with --output_level 4")
+    if not 0.0 < args.occ_pool <= 1.0:
+        ap.error("--occ_pool must be in (0, 1]")
     if not 0 < args.aug_scale[0] <= args.aug_scale[1]:
         ap.error("--aug_scale LO HI must satisfy 0 < LO <= HI")
     if min(args.aug_rotate, args.aug_translate, args.aug_rel_rotate, args.aug_rel_translate) < 0 or not 0 <= args.aug_flip <= 1:
