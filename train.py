@@ -193,61 +193,13 @@ def validate(args, weights, ds, val_idx, dist=None):
 def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
     """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet.
     aug (an Augmenter, --augment): `ds` holds whole frames, the batch is cut and jittered on the GPU, validation reads val_ds."""
-    from pwcnet_amd import PWCDCNetModule, ckpt
-    from pwcnet_amd.splat import range_valid
-    from pwcnet_amd.unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss, ssim_loss
-    term = "census" if args.photo == "census" else "photometric"
-
-    def data_term(i0, i1, flows, valid=None, flow_scale=1.0):
-        if args.photo == "census":
-            return census_loss(i0, i1, flows, flow_scale=flow_scale, valid=valid, radius=args.census_radius)
-        return photometric_loss(i0, i1, flows, flow_scale=flow_scale, valid=valid, eps=args.photo_eps, q=args.photo_q)
-
-    def ssim_term(i0, i1, flows, valid=None, flow_scale=1.0):
-        return ssim_loss(i0, i1, flows, flow_scale=flow_scale, valid=valid, radius=args.ssim_radius)
-
-    w_ssim = args.ssim_weight                 # 0: the --photo term alone (the run as it was), 1: SSIM alone, no base term
-
-    def smooth_term(flows, images):
-        return smoothness_loss(flows, images, alpha=args.edge_alpha, eps=args.photo_eps, q=args.photo_q, order=args.smooth_order)
-
-    # --level_weights: None (absent or all zeros) is the run as it was, no pyramid launch
-    level_w = args.level_weights if args.level_weights and any(w != 0 for w in args.level_weights) else None
-
-    def level_terms(images_0, images_1, flows_pyramid, masks):
-        """(what the levels add to the loss, the unweighted data value per level).  masks: None, or (m_fw, m_bw) with
-        flows_pyramid from the stacked 2N forward."""
-        from pwcnet_amd.pyramid import frame_pyramid, level_flow_scale, mask_pyramid
-        N, H, W, _ = images_0.shape
-        factors = tuple(W // f.shape[2] for f in flows_pyramid)
-        pyr0, pyr1 = frame_pyramid(images_0, factors), frame_pyramid(images_1, factors)
-        if masks is not None:
-            mp_fw, mp_bw = (mask_pyramid(m, factors, min_fraction=args.occ_pool) for m in masks)
-        added, values = 0.0, []
-        for l, (wl, fl) in enumerate(zip(level_w, flows_pyramid)):
-            h, w = fl.shape[1:3]
-            scale = level_flow_scale(fl, (H, W))
-            if masks is None:
-                ways = [(pyr0[l], pyr1[l], fl, None)]
-            else:
-                ways = [(pyr0[l], pyr1[l], fl[:N], mp_fw[l]), (pyr1[l], pyr0[l], fl[N:], mp_bw[l])]
-            # a window that does not fit the level: the term would be an empty mean
-            if (w_ssim < 1 and args.photo == "census" and min(h, w) <= 2 * args.census_radius) or \
-                    (w_ssim > 0 and min(h, w) <= 2 * args.ssim_radius):
-                values.append(float("nan"))
-                continue
-            p = s = None
-            if w_ssim < 1:
-                p = sum(data_term(i0, i1, f, m, flow_scale=scale) for i0, i1, f, m in ways) / len(ways)
-            if w_ssim > 0:
-                s = sum(ssim_term(i0, i1, f, m, flow_scale=scale) for i0, i1, f, m in ways) / len(ways)
-            d = p if w_ssim == 0 else s if w_ssim == 1 else (1.0 - w_ssim) * p + w_ssim * s
-            values.append(float(d.detach()))
-            if wl != 0:
-                # the smoothness terms have no flow_scale: the flow goes in in level pixels, autograd carries the factor
-                sm = sum(smooth_term(scale * f, i0) for i0, _, f, _ in ways) / len(ways)
-                added = added + wl * (d + args.smooth_weight * sm)
-        return added, values
+    from pwcnet_amd import PWCDCNetModule, UnsupObjective, ckpt
+    objective = UnsupObjective(photo=args.photo, census_radius=args.census_radius, photo_eps=args.photo_eps, photo_q=args.photo_q,
+                               ssim_weight=args.ssim_weight, ssim_radius=args.ssim_radius, smooth_weight=args.smooth_weight,
+                               smooth_order=args.smooth_order, edge_alpha=args.edge_alpha, occlusion=args.occlusion,
+                               occ_alpha1=args.occ_alpha1, occ_alpha2=args.occ_alpha2, occ_min_range=args.occ_min_range,
+                               consistency_weight=args.consistency_weight, level_weights=args.level_weights,
+                               occ_pool=args.occ_pool)
 
     model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                            use_dc=args.use_dc, output_level=args.output_level)
@@ -268,50 +220,23 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
             opt.zero_grad(set_to_none=True)
             if args.occlusion != "none":
                 # both pair orders in one forward: the first N flows are 0 -> 1, the last N are 1 -> 0
-                N = images_0.shape[0]
                 flows_final, flows_pyramid = model(torch.cat([images_0, images_1]), torch.cat([images_1, images_0]))
-                fw, bw = flows_final[:N], flows_final[N:]
-                with torch.no_grad():
-                    if args.occlusion == "fb":
-                        m_fw, m_bw, c_fw, c_bw = fb_valid(fw.detach(), bw.detach(), alpha1=args.occ_alpha1,
-                                                          alpha2=args.occ_alpha2, return_counts=True)
-                    else:
-                        m_fw, m_bw = range_valid(fw.detach(), bw.detach(), min_range=args.occ_min_range)
-                        c_fw, c_bw = m_fw.sum(), m_bw.sum()
-                if w_ssim < 1:
-                    photo = 0.5 * (data_term(images_0, images_1, fw, m_fw) + data_term(images_1, images_0, bw, m_bw))
-                if w_ssim > 0:
-                    ssim = 0.5 * (ssim_term(images_0, images_1, fw, m_fw) + ssim_term(images_1, images_0, bw, m_bw))
-                smooth = 0.5 * (smooth_term(fw, images_0) + smooth_term(bw, images_1))
-                occluded = 1.0 - float(c_fw.sum() + c_bw.sum()) / float(m_fw.numel() + m_bw.numel())
-                tail = f"  occluded {occluded:.4f}"
-                if args.consistency_weight > 0:
-                    consistency = fb_consistency_loss(fw, bw, valid_fw=m_fw, valid_bw=m_bw, eps=args.photo_eps, q=args.photo_q)
             else:
                 flows_final, flows_pyramid = model(images_0, images_1)
-                if w_ssim < 1:
-                    photo = data_term(images_0, images_1, flows_final)
-                if w_ssim > 0:
-                    ssim = ssim_term(images_0, images_1, flows_final)
-                smooth = smooth_term(flows_final, images_0)
-                tail = ""
-            data = photo if w_ssim == 0 else ssim if w_ssim == 1 else (1.0 - w_ssim) * photo + w_ssim * ssim
-            loss = data + args.smooth_weight * smooth
-            if args.consistency_weight > 0:
-                loss = loss + args.consistency_weight * consistency
-                tail += f"  consistency {float(consistency.detach()):.6f}"
-            if level_w is not None:
-                added, values = level_terms(images_0, images_1, flows_pyramid,
-                                            (m_fw, m_bw) if args.occlusion != "none" else None)
-                loss = loss + added
-                tail += "  levels " + " ".join(f"{v:.6f}" for v in values)
+            loss, terms = objective(images_0, images_1, flows_final, flows_pyramid)
             loss.backward()
             opt.step()
             global_step += 1
             n_steps += 1
             loss_sum += float(loss)
-            terms = (f"  {term} {float(photo):.6f}" if w_ssim < 1 else "") + (f"  ssim {float(ssim):.6f}" if w_ssim > 0 else "")
-            print(f"step {global_step}: loss/unsup {float(loss):.6f}{terms}  smoothness {float(smooth):.6f}{tail}")
+            line = "".join(f"  {k} {float(terms[k]):.6f}" for k in (objective.term, "ssim", "smoothness") if k in terms)
+            if "occluded" in terms:
+                line += f"  occluded {terms['occluded']:.4f}"
+            if "consistency" in terms:
+                line += f"  consistency {float(terms['consistency']):.6f}"
+            if "levels" in terms:
+                line += "  levels " + " ".join(f"{v:.6f}" for v in terms["levels"])
+            print(f"step {global_step}: loss/unsup {float(loss):.6f}{line}")
         res = validate(args, model.tf_state_dict(), ds if val_ds is None else val_ds, val_idx)
         dt = time.time() - t0
         print(f"epoch {e + 1}: loss/unsup {loss_sum / max(n_steps, 1):.4f}  EPE/val {res['epe']:.4f}  "
