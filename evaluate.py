@@ -37,6 +37,9 @@ def build_parser():
     ap.add_argument("--fit", choices=("crop", "resize", "pad"), default="crop",
                     help="frames whose size is no multiple of 64: crop them, ground truth and mask too (reference), or resize / "
                          "pad them on the GPU and compare the flow on the frame's own grid [crop]")
+    ap.add_argument("--normalize_features", action="store_true",
+                    help="correlate layer-normalised feature maps (PWCDCNet(normalize_features=True)).  A checkpoint carries no marker for this: pass it exactly when the weights were trained with it")
+    ap.add_argument("--norm_eps", type=float, default=1e-16, help="--normalize_features: epsilon under the square root [1e-16]")
     return ap
 
 
@@ -58,7 +61,7 @@ def main():
     from pwcnet_amd import ckpt, flow_io, sharding
 
     pairs = [ln.split() for ln in open(args.list) if ln.strip() and not ln.startswith("#")]
-    model = pwcnet_amd.PWCDCNet(range_check="sync")      # results are final when a call returns (fp16-range check + fp32 repeat)
+    model = pwcnet_amd.PWCDCNet(range_check="sync", normalize_features=args.normalize_features, norm_eps=args.norm_eps)      # results are final when a call returns (fp16-range check + fp32 repeat)
     if args.resume:
         model.load_weights(ckpt.load_weights(args.resume))
 

@@ -951,6 +951,40 @@ int pwc_frame_pyramid_f32(const void* x, int x_is_u8, int N, int H, int W, int C
 int pwc_mask_pyramid_u8(const unsigned char* valid, int N, int H, int W, const int* factors, const int* need,
                         unsigned char* const* outs, int* const* counts, int n_levels, pwc_stream_t stream);
 
+/* ==== feature normalisation: one layer norm over the two feature maps of a pair, in front of the cost volume ====
+ * (pwc_featnorm.hip; semantics, bounds and launch plan in DESIGN.md.)  f0, f1: N x H x W records of f0_cs / f1_cs floats, C
+ * used -- the halves of a stacked 2N tensor, or one tensor and itself shifted by a frame.  For pair n, over the M = 2 H W C
+ * values of f0[n] and f1[n]:
+ *   mean = sum x / M,  var = sum (x - mean)^2 / M (biased),  rstd = 1 / sqrt(var + eps),
+ *   y = float32(((double)x - mean) * rstd),  stats[n] = {mean, rstd} (doubles).
+ * Every quantity is a double, every output is rounded once.  The variance comes from ONE pass over sums shifted by the pair's
+ * first value K = f0[n][0] (d = x - K: mean = K + sum d / M, var = sum d^2 / M - (sum d / M)^2, clamped at 0): the cancellation
+ * is (|mean - K| rstd)^2 ulps of a double, not (|mean| rstd)^2, and a constant pair has var == 0 exactly.
+ * The sums are cut by pwc_feature_norm_parts(H, W, C) -- never by N -- and added in a fixed order: two calls give the same
+ * bits, a pair gives the same bits alone and in a batch, with 16-byte accesses (C % 4 == 0, strides % 4 == 0, pointers on 16-byte
+ * boundaries) and without.  A NaN or Inf makes its own pair non-finite and no other.  No atomics, no host synchronisation.
+ * Launches: one where parts == 1 (H W C <= 4096: a workgroup per pair sums and applies), else two.
+ * workspace: pwc_feature_norm_workspace_bytes(N, H, W, C) = 16 * N * parts bytes, 0 where parts == 1 (then it may be NULL);
+ * 8-byte aligned.  The gradient needs the same amount; it may be the same memory.
+ * Checks, before any launch, in this order: null f0, f1, y0, y1 or stats, N, H, W, C <= 0 (PWC_EINVAL); a channel stride below
+ * C, eps negative or NaN (PWC_EINVAL); a float pointer off a 4-byte boundary (PWC_EALIGN); H * W * C >= 2^31 or N > 65535
+ * (PWC_ERANGE); stats off an 8-byte boundary (PWC_EALIGN); where the workspace is needed a null one (PWC_EINVAL), one off an
+ * 8-byte boundary (PWC_EALIGN), a short one (PWC_EINVAL). */
+size_t pwc_feature_norm_workspace_bytes(int N, int H, int W, int C);
+int pwc_feature_norm_parts(int H, int W, int C);   /* 0 for sizes the entry points refuse */
+int pwc_feature_norm_f32(const float* f0, int f0_cs, const float* f1, int f1_cs, int N, int H, int W, int C, double eps,
+                         void* workspace, size_t workspace_bytes, float* y0, int y0_cs, float* y1, int y1_cs, double* stats,
+                         pwc_stream_t stream);
+/* Its gradient.  g0, g1: upstream gradients of y0, y1; stats: what the forward wrote.  With xh = ((double)x - mean) * rstd
+ * recomputed from x (never read from the rounded y), a = sum g / M, b = sum g xh / M over the pair:
+ *   d = float32(rstd * (g - a - xh * b)), written, or (accumulate) added to what d0 / d1 hold (d + v, one rounding).
+ * The sums as above (same parts, same order).  d0 / d1 must not overlap the inputs.  Checks as above, with g0, g1, d0, d1 in
+ * place of y0, y1 and no eps.  One launch where parts == 1, else two. */
+int pwc_feature_norm_grad_f32(const float* f0, int f0_cs, const float* f1, int f1_cs, const float* g0, int g0_cs,
+                              const float* g1, int g1_cs, const double* stats, int N, int H, int W, int C, void* workspace,
+                              size_t workspace_bytes, float* d0, int d0_cs, float* d1, int d1_cs, int accumulate,
+                              pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,9 @@ def build_parser():
     ap.add_argument("--fit", choices=("crop", "resize", "pad"), default="crop",
                     help="frames whose size is no multiple of 64: crop them (reference), or resize / pad them on the GPU and "
                          "bring the flow back to the frame's size [crop]")
+    ap.add_argument("--normalize_features", action="store_true",
+                    help="correlate layer-normalised feature maps (PWCDCNet(normalize_features=True)).  A checkpoint carries no marker for this: pass it exactly when the weights were trained with it")
+    ap.add_argument("--norm_eps", type=float, default=1e-16, help="--normalize_features: epsilon under the square root [1e-16]")
     return ap
 
 
@@ -50,7 +53,7 @@ def main():
         x = torch.from_numpy(np.stack([np.asarray(Image.open(p).convert("RGB")) for p in args.input_images])).cuda()
         x, info = pwcnet_amd.fit_frames(x, args.fit)
 
-    model = pwcnet_amd.PWCDCNet(range_check="sync")      # results are final when a call returns (fp16-range check + fp32 repeat)
+    model = pwcnet_amd.PWCDCNet(range_check="sync", normalize_features=args.normalize_features, norm_eps=args.norm_eps)      # results are final when a call returns (fp16-range check + fp32 repeat)
     if args.resume is not None:
         print(f"Loading learned model from checkpoint {args.resume}")
         model.load_weights(ckpt.load_weights(args.resume))

@@ -47,6 +47,9 @@ def build_parser():
     ap.add_argument("--fit", choices=("crop", "resize", "pad"), default="crop",
                     help="frames whose size is no multiple of 64: crop them (reference), or resize / pad them on the GPU and "
                          "bring the flow back to the frame's size [crop]")
+    ap.add_argument("--normalize_features", action="store_true",
+                    help="correlate layer-normalised feature maps (PWCDCNet(normalize_features=True)).  A checkpoint carries no marker for this: pass it exactly when the weights were trained with it")
+    ap.add_argument("--norm_eps", type=float, default=1e-16, help="--normalize_features: epsilon under the square root [1e-16]")
     return ap
 
 
@@ -67,7 +70,7 @@ def main():
     # hardware queues of their own) the launch-bound coarse levels of one batch run under the matrix-bound launches of another.
     # Results are read behind pipeline.synchronize(): every forward has then passed its fp16-range check (a flagged one has been
     # repeated on the fp32 kernels), which is what range_check="sync" gave the one-forward-at-a-time loop.
-    model = pwcnet_amd.ForwardPipeline(depth=args.pipeline)
+    model = pwcnet_amd.ForwardPipeline(depth=args.pipeline, normalize_features=args.normalize_features, norm_eps=args.norm_eps)
     if args.resume is not None:
         print(f"Loading learned model from checkpoint {args.resume}")
         model.load_weights(ckpt.load_weights(args.resume))

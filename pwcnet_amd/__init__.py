@@ -14,7 +14,7 @@ from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noq
 from .augment import augment_pairs, crop_params, draw_params  # noqa: F401
 from .pyramid import frame_pyramid, level_flow_scale, mask_pyramid  # noqa: F401
 from .objective import UnsupObjective  # noqa: F401
-from .modules import (ContextNetwork, CostVolumeLayer, FeaturePyramidExtractor_custom,  # noqa: F401
+from .modules import (ContextNetwork, CostVolumeLayer, FeatureNormLayer, FeaturePyramidExtractor_custom,  # noqa: F401
                       OpticalFlowEstimator_custom, WarpingLayer, resize_bilinear)
 
 __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtractor_custom", "WarpingLayer", "CostVolumeLayer",
@@ -22,4 +22,4 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "smoothness_sums", "smoothness_loss", "census_sums", "census_loss", "census_grad", "ssim_sums", "ssim_loss", "ssim_grad", "fb_valid",
            "fb_consistency_sums", "fb_consistency_loss", "fb_consistency_grad", "forward_splat", "splat_grad", "range_map", "range_valid", "FitInfo", "fit_frames", "fit_info",
            "refit_flow", "flow_any_size", "draw_params", "crop_params", "augment_pairs", "frame_pyramid", "mask_pyramid", "level_flow_scale",
-           "UnsupObjective"]
+           "UnsupObjective", "FeatureNormLayer"]

@@ -73,7 +73,8 @@ class PWCDCNetModule(torch.nn.Module):
     units of PWCDCNet.__call__.  Gradients reach `flat` (every variable) and, when they require grad, both images."""
 
     def __init__(self, num_levels=6, search_range=4, warp_type="bilinear", use_dc=False, output_level=4,
-                 name="pwcdcnet", f16x2=True, f16x2_dgrad=False, seed=0, device="cuda"):
+                 name="pwcdcnet", f16x2=True, f16x2_dgrad=False, seed=0, device="cuda", normalize_features=False,
+                 norm_eps=1e-16):
         super().__init__()
         if warp_type != "bilinear":
             raise ValueError(f"PWCDCNetModule: warp_type {warp_type!r} has no flow gradient; use 'bilinear'")
@@ -82,7 +83,8 @@ class PWCDCNetModule(torch.nn.Module):
         if not 0 <= output_level < num_levels or 2 ** (num_levels - output_level) > 4:
             raise ValueError(f"PWCDCNetModule: output_level {output_level} not supported: flows_final's resize factor "
                              f"2^{num_levels - output_level} is above 4 (output_level 4 or 5)")
-        self._net = _Net(num_levels, search_range, warp_type, use_dc, output_level, name, f16x2, f16x2_dgrad, device)
+        self._net = _Net(num_levels, search_range, warp_type, use_dc, output_level, name, f16x2, f16x2_dgrad, device,
+                         normalize_features, norm_eps)
         self.flat = torch.nn.Parameter(self._net.params)
         self.load_weights(init_weights(self._net.specs, seed=seed))
         G._lib.lib()                                    # fail loudly without the HIP library

@@ -148,6 +148,22 @@ def cost_volume_grad(f0, f1w, cv, dcv, df0=None, df1w=None, accumulate=False, se
         1 if accumulate else 0, f0.N, f0.H, f0.W, f0.C, int(search_range), float(slope), _s()), "cost_volume_grad")
 
 
+def feature_norm_grad(f0, f1, g0, g1, stats, d0, d1, accumulate=False):
+    """Gradient of modules.FeatureNormLayer: d0 / d1 (+)= rstd * (g - a - xh * b) from the raw maps f0 / f1, the upstream
+    gradients g0 / g1 of the normalised maps and the forward's `stats` ((N, 2) float64: mean, rstd); a = sum g / M,
+    b = sum g xh / M over the pair, in doubles, in a fixed order (bit-reproducible).  accumulate adds exactly what the plain
+    call writes.  All maps are Views over one pixel grid; d0 / d1 must not overlap the inputs."""
+    assert f0[2:] == f1[2:] == g0[2:] == g1[2:] == d0[2:] == d1[2:], (f0, f1, g0, g1, d0, d1)
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 2 * f0.N
+    L = _L()
+    need = L.pwc_feature_norm_workspace_bytes(f0.N, f0.H, f0.W, f0.C)
+    ws = _ws(stats.device, (need + 3) // 4) if need else None          # (torch allocations are 8-byte aligned)
+    _lib.check(L.pwc_feature_norm_grad_f32(
+        _p(f0.ptr), f0.cs, _p(f1.ptr), f1.cs, _p(g0.ptr), g0.cs, _p(g1.ptr), g1.cs, _p(stats.data_ptr()),
+        f0.N, f0.H, f0.W, f0.C, _p(ws.data_ptr()) if ws is not None else None, ws.numel() * 4 if ws is not None else 0,
+        _p(d0.ptr), d0.cs, _p(d1.ptr), d1.cs, 1 if accumulate else 0, _s()), "feature_norm_grad")
+
+
 def mask_ptr(valid, N, GH, GW, device=None):
     """Address of a validity mask for the masked kernels: a torch.bool or torch.uint8 tensor of shape (N, GH, GW), one
     byte per ground-truth pixel, non-zero = valid; contiguous and on the GPU (`device`: the flows').  TypeError for another

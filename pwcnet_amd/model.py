@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from . import modules as _m
-from .modules import (ContextNetwork, CostVolumeLayer, FeaturePyramidExtractor_custom, LaunchPlan,
+from .modules import (ContextNetwork, CostVolumeLayer, FeatureNormLayer, FeaturePyramidExtractor_custom, LaunchPlan,
                       OpticalFlowEstimator_custom, VariableStore, View, WarpingLayer, _copy_channels,
                       _keep, _resize, as_view, sub_view, variable_scope)
 from .weights import ChannelLayout, SCALES, conv_specs
@@ -94,7 +94,7 @@ class PWCDCNet(object):
     def __init__(self, num_levels=6, search_range=4, warp_type="bilinear", use_dc=False,
                  output_level=4, name="pwcdcnet", seed=0, fuse_warp=False, use_plans=True, winograd=True,
                  coarse_cv=True, persistent_outputs=False, max_plans=4, streams=None, concat_cv=True, winograd4=True, f16x2=True,
-                 range_check="lazy", track_max=False):
+                 range_check="lazy", track_max=False, normalize_features=False, norm_eps=1e-16):
         self.num_levels = num_levels
         self.s_range = search_range
         self.warp_type = warp_type
@@ -109,6 +109,11 @@ class PWCDCNet(object):
         self.fp_extractor = FeaturePyramidExtractor_custom(self.num_levels)
         self.warp_layer = WarpingLayer(self.warp_type)
         self.cv_layer = CostVolumeLayer(search_range)
+        # normalize_features: each level correlates layer-normalised COPIES of its two feature maps (one norm over the pair,
+        # FeatureNormLayer; DESIGN.md "Feature normalisation"); the estimator, the context network and with_features keep the
+        # raw maps.  Not in the reference; a checkpoint carries no marker for it: infer with the setting the weights were trained with.
+        self.normalize_features = bool(normalize_features)
+        self.norm_layer = FeatureNormLayer(norm_eps)
         self.of_estimators = [OpticalFlowEstimator_custom(use_dc=self.use_dc, name=f"optflow_{l}")
                               for l in range(self.num_levels)]
         self.context = ContextNetwork(name="context")
@@ -569,6 +574,9 @@ class PWCDCNet(object):
                 _, h, w, C = F.shape
                 f0 = View(F.data_ptr(), C, N, h, w, C)
                 f1 = View(F.data_ptr() + 4 * f1_off * h * w * C, C, N, h, w, C)
+                # what the level correlates: the maps, or their normalised copies (`hold` owns those until the level's launches
+                # are enqueued: the eager forward keeps no other reference)
+                c0, c1, hold = self._corr_operands(f0, f1, dev)
                 est = self.of_estimators[l]
                 is_out = (l == self.output_level)
 
@@ -578,7 +586,7 @@ class PWCDCNet(object):
                     # Round 6: [cv | flows_up_prev | 0] as a dense tensor of 84-channel records written by the correlation launch,
                     # features_0 where it is, features_up_prev as a dense tensor: the first conv takes the three of them
                     cvx, flow_v, fu_v = inp["cvx"], inp["flow"], inp["feat_up"]
-                    self.cv_layer._run(f0, f1, View(cvx.ptr, cvx.cs, N, h, w, (2 * self.s_range + 1) ** 2), flow=flow_v,
+                    self.cv_layer._run(c0, c1, View(cvx.ptr, cvx.cs, N, h, w, (2 * self.s_range + 1) ** 2), flow=flow_v,
                                        flow_scale=self.scales[l], concat=True, out_pad_writable=2)
                     E = None
                 else:
@@ -591,7 +599,14 @@ class PWCDCNet(object):
                     cv_out = sub_view(E, lay.offset("cv"), (2 * self.s_range + 1) ** 2)
                     f0_dst = sub_view(E, lay.offset("f0"), C) if f0_ext is None else None
                     flow_v = sub_view(E, lay.offset("flow"), 2) if l > 0 else None
-                    self._corr_level(l, f0, f1, flow_v, cv_out, f0_dst, E, dev)
+                    if c0 is f0:
+                        self._corr_level(l, f0, f1, flow_v, cv_out, f0_dst, E, dev)
+                    else:
+                        # the correlation launches copy THEIR first operand into the estimator buffer: the raw map goes there
+                        # in a launch of its own
+                        self._corr_level(l, c0, c1, flow_v, cv_out, None, E, dev)
+                        if f0_dst is not None:
+                            _copy_channels(f0, f0_dst, C)
 
                 def run_est(flows_out, feat_out=None):
                     if inp["three"]:
@@ -644,6 +659,22 @@ class PWCDCNet(object):
                     return flows_final, flows_pyramid, pyramid_0
                 else:
                     return flows_final, flows_pyramid
+
+    def _corr_operands(self, f0, f1, dev):
+        """(f0, f1, None), or with normalize_features Views of their normalised copies (a 2N tensor of the forward's own; two
+        launches, one at the coarse levels) and the tensors behind them.  The pair statistics are not kept beyond that: the
+        inference forward has no backward."""
+        if not self.normalize_features:
+            return f0, f1, None
+        N, h, w, C = f0.N, f0.H, f0.W, f0.C
+        y_t = torch.empty((2 * N, h, w, C), dtype=torch.float32, device=dev)
+        stats = torch.empty((N, 2), dtype=torch.float64, device=dev)
+        ws = self.norm_layer.workspace(N, h, w, C, dev)
+        _keep(y_t, stats, ws)
+        y0 = View(y_t.data_ptr(), C, N, h, w, C)
+        y1 = View(y_t.data_ptr() + 4 * N * h * w * C, C, N, h, w, C)
+        self.norm_layer._run(f0, f1, y0, y1, stats, ws)
+        return y0, y1, (y_t, stats, ws)
 
     def _level_input(self, l, N, h, w, C, fu_map, dev, is_out):
         """The estimator input of level l (fu_map: physical -> logical map of features_up_prev, None at level 0): a dict with

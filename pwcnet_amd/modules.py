@@ -844,6 +844,52 @@ class CostVolumeLayer(_Module):
         return out
 
 
+# ---------------------------------------------------------------- feature normalisation
+
+class FeatureNormLayer(_Module):
+    """One layer norm over the two feature maps of a pair, in front of the cost volume (DESIGN.md, "Feature normalisation";
+    not part of the reference): y = (x - mean) * rstd with mean and the biased variance over the 2 h w C values of
+    features_0[n] and features_1[n] together, rstd = 1 / sqrt(var + eps), in doubles, rounded once."""
+
+    def __init__(self, eps=1e-16, name="feature_norm"):
+        super().__init__(name)
+        eps = float(eps)
+        if not eps >= 0.0:
+            raise ValueError(f"FeatureNormLayer: eps must be >= 0, got {eps}")
+        self.eps = eps
+
+    @staticmethod
+    def workspace(N, H, W, C, device):
+        """The scratch of one call (None where the op needs none): the caller owns it until the launches have run."""
+        need = _lib.lib().pwc_feature_norm_workspace_bytes(N, H, W, C)
+        return torch.empty(((need + 7) // 8,), dtype=torch.float64, device=device) if need else None
+
+    def _run(self, f0, f1, y0, y1, stats, ws=None):
+        """f0, f1 -> y0, y1 (Views over one pixel grid); stats: (N, 2) float64 tensor that receives {mean, rstd} per pair;
+        ws: workspace(...)'s tensor.  One launch where the pair is small, else two."""
+        assert f0[2:] == f1[2:] == y0[2:] == y1[2:], "feature maps must have equal shapes"
+        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 2 * f0.N
+        npix = f0.N * f0.H * f0.W
+        _launch(_lib.lib().pwc_feature_norm_f32,
+                (_p(f0.ptr), f0.cs, _p(f1.ptr), f1.cs, f0.N, f0.H, f0.W, f0.C, self.eps,
+                 _p(ws.data_ptr()) if ws is not None else None, ws.numel() * 8 if ws is not None else 0,
+                 _p(y0.ptr), y0.cs, _p(y1.ptr), y1.cs, _p(stats.data_ptr()), _lib.current_stream()),
+                "feature_norm", "featnorm_kernel", 0.0, 4.0 * npix * f0.C * 6)      # both maps read twice, written once
+
+    def __call__(self, features_0, features_1, with_stats=False):
+        """(y0, y1[, stats]): the normalised maps as new tensors; stats (N, 2) float64 = {mean, rstd} per pair."""
+        f0, features_0 = as_view(features_0, "features_0")
+        f1, features_1 = as_view(features_1, "features_1")
+        assert f0[2:] == f1[2:], "feature maps must have equal shapes"
+        dev = features_0.device
+        y = torch.empty((2, f0.N, f0.H, f0.W, f0.C), dtype=torch.float32, device=dev)
+        stats = torch.empty((f0.N, 2), dtype=torch.float64, device=dev)
+        ws = self.workspace(f0.N, f0.H, f0.W, f0.C, dev)
+        _keep(y, stats, ws)
+        self._run(f0, f1, View(y[0].data_ptr(), f0.C, *f0[2:]), View(y[1].data_ptr(), f0.C, *f0[2:]), stats, ws)
+        return (y[0], y[1], stats) if with_stats else (y[0], y[1])
+
+
 # ---------------------------------------------------------------- flow estimator (a4)
 
 class OpticalFlowEstimator_custom(_Module):

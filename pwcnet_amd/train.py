@@ -69,7 +69,11 @@ class _Net:
     _Tape; the backward runs from a tape and per-level flow gradients into a caller-given flat gradient buffer."""
 
     def __init__(self, num_levels=6, search_range=4, warp_type="bilinear", use_dc=False, output_level=4, name="pwcdcnet",
-                 f16x2=True, f16x2_dgrad=False, device="cuda"):
+                 f16x2=True, f16x2_dgrad=False, device="cuda", normalize_features=False, norm_eps=1e-16):
+        # normalize_features: every level correlates layer-normalised copies of its feature maps (one norm over the pair,
+        # modules.FeatureNormLayer; the estimator's concat keeps the raw features_0), as PWCDCNet(normalize_features=True)
+        self.normalize_features = bool(normalize_features)
+        self.norm_layer = M.FeatureNormLayer(norm_eps)
         # the F16-pipe convolution kernels (operands as fp16 pairs) in the forward / in the data gradient: grad_ops.F16X2,
         # grad_ops.F16X2_DGRAD (the reasons for the defaults are there); applied at every forward and backward
         self.f16x2, self.f16x2_dgrad = bool(f16x2), bool(f16x2_dgrad)
@@ -174,18 +178,32 @@ class _Net:
             E_t = torch.zeros((N, h, w, lay.n_phys), dtype=torch.float32, device=dev)
             E = View(E_t.data_ptr(), lay.n_phys, N, h, w, lay.n_phys)
             L = dict(l=l, fc=fc, f0=f0, f1=f1, lay=lay, E_t=E_t, E=E, C=C, nfeat=nfeat)
+            # c0, c1: what the level warps and correlates -- the maps, or their normalised copies (kept with the pair
+            # statistics for the backward)
+            c0, c1 = f0, f1
+            if self.normalize_features:
+                y_t = torch.empty((2 * N, h, w, C), dtype=torch.float32, device=dev)
+                stats = torch.empty((N, 2), dtype=torch.float64, device=dev)
+                ws = self.norm_layer.workspace(N, h, w, C, dev)
+                c0 = View(y_t.data_ptr(), C, N, h, w, C)
+                c1 = View(y_t.data_ptr() + 4 * N * h * w * C, C, N, h, w, C)
+                self.norm_layer._run(f0, f1, c0, c1, stats, ws)
+                if ws is not None:
+                    keep.append(ws)
+                L.update(y_t=y_t, stats=stats)
+            L.update(c0=c0, c1=c1)
             if l > 0:
                 # x2 upsampling of the previous level's flows and features into this level's buffer (modules.py:282-285)
                 M._resize(prev["flows_v"], sub_view(E, lay.offset("flow"), 2))
                 M._resize(prev["feat"], sub_view(E, lay.offset("feat_up"), nfeat))
                 f1w_t = torch.empty((N, h, w, C), dtype=torch.float32, device=dev)
                 f1w = View(f1w_t.data_ptr(), C, N, h, w, C)
-                M.WarpingLayer("bilinear")._run(f1, sub_view(E, lay.offset("flow"), 2), f1w, flow_scale=SCALES[l])
+                M.WarpingLayer("bilinear")._run(c1, sub_view(E, lay.offset("flow"), 2), f1w, flow_scale=SCALES[l])
                 L["f1w_t"], L["f1w"] = f1w_t, f1w
             else:
-                L["f1w"] = f1
+                L["f1w"] = c1
             cv_v = sub_view(E, lay.offset("cv"), 81)
-            M.CostVolumeLayer(self.s_range)._run(f0, L["f1w"], cv_v)
+            M.CostVolumeLayer(self.s_range)._run(c0, L["f1w"], cv_v)
             M._copy_channels(f0, sub_view(E, lay.offset("f0"), C), C)
             convs = []
             xin, start = E, lay.offset("cv")
@@ -333,14 +351,21 @@ class _Net:
             dF1 = View(dF[l].data_ptr() + 4 * N * h * w * C, C, N, h, w, C)
             G.add_(sub_view(dE, lay.offset("f0"), C), dF0)                              # features_0 part of the concat
             cv_v = sub_view(E, lay.offset("cv"), 81)
+            # d0, d1: where the gradients of the correlated maps go -- dF0 / dF1 themselves, or with normalize_features a
+            # zeroed pair of their own (dy), which the norm's backward then ADDS into dF0 / dF1
+            d0, d1 = dF0, dF1
+            if self.normalize_features:
+                dy_t = torch.zeros((2 * N, h, w, C), dtype=torch.float32, device=dev)
+                d0 = View(dy_t.data_ptr(), C, N, h, w, C)
+                d1 = View(dy_t.data_ptr() + 4 * N * h * w * C, C, N, h, w, C)
             if l > 0:
                 dflow = sub_view(dE, lay.offset("flow"), 2)
                 G.add_(View(d_est.data_ptr(), 2, N, h, w, 2), dflow)                     # residual flows += flows_up_prev
                 df1w_t = torch.empty((N, h, w, C), dtype=torch.float32, device=dev)
                 df1w = View(df1w_t.data_ptr(), C, N, h, w, C)
-                G.cost_volume_grad(L["f0"], L["f1w"], cv_v, sub_view(dE, lay.offset("cv"), 81), dF0, None, accumulate=True)
-                G.cost_volume_grad(L["f0"], L["f1w"], cv_v, sub_view(dE, lay.offset("cv"), 81), None, df1w, accumulate=False)
-                G.warp_grad(L["f1"], sub_view(E, lay.offset("flow"), 2), SCALES[l], df1w, dF1, dflow, dflow_accumulate=True)
+                G.cost_volume_grad(L["c0"], L["f1w"], cv_v, sub_view(dE, lay.offset("cv"), 81), d0, None, accumulate=True)
+                G.cost_volume_grad(L["c0"], L["f1w"], cv_v, sub_view(dE, lay.offset("cv"), 81), None, df1w, accumulate=False)
+                G.warp_grad(L["c1"], sub_view(E, lay.offset("flow"), 2), SCALES[l], df1w, d1, dflow, dflow_accumulate=True)
                 # x2 resizes into this level's buffer: back to the previous level's flows and features
                 P = tape.levels[l - 1]
                 ph, pw, nfeat = P["f0"].H, P["f0"].W, L["nfeat"]
@@ -349,7 +374,10 @@ class _Net:
                 G.resize_grad(sub_view(dE, lay.offset("feat_up"), nfeat), View(dfeat_next.data_ptr(), nfeat, N, ph, pw, nfeat))
                 keep += [df1w_t]
             else:
-                G.cost_volume_grad(L["f0"], L["f1w"], cv_v, sub_view(dE, lay.offset("cv"), 81), dF0, dF1, accumulate=True)
+                G.cost_volume_grad(L["c0"], L["f1w"], cv_v, sub_view(dE, lay.offset("cv"), 81), d0, d1, accumulate=True)
+            if self.normalize_features:
+                G.feature_norm_grad(L["f0"], L["f1"], d0, d1, L["stats"], dF0, dF1, accumulate=True)
+                keep.append(dy_t)
             keep += [dE_t, dfeat]
         # extractor, deep -> shallow; level index in tape.ext order is shallow -> deep
         carry = None
@@ -379,9 +407,11 @@ class Trainer(_Net):
 
     def __init__(self, num_levels=6, search_range=4, warp_type="bilinear", use_dc=False, output_level=4,
                  name="pwcdcnet", weights=(0.32, 0.08, 0.02, 0.01, 0.005), gamma=0.0004, lr=1e-4, lr_scheduling=True,
-                 seed=0, device="cuda", dist=None, loss="multiscale", epsilon=0.01, q=0.4, f16x2=True, f16x2_dgrad=False):
+                 seed=0, device="cuda", dist=None, loss="multiscale", epsilon=0.01, q=0.4, f16x2=True, f16x2_dgrad=False,
+                 normalize_features=False, norm_eps=1e-16):
         assert loss in ("multiscale", "robust"), loss
-        super().__init__(num_levels, search_range, warp_type, use_dc, output_level, name, f16x2, f16x2_dgrad, device)
+        super().__init__(num_levels, search_range, warp_type, use_dc, output_level, name, f16x2, f16x2_dgrad, device,
+                         normalize_features, norm_eps)
         self.loss, self.epsilon, self.q = loss, float(epsilon), float(q)
         self.loss_weights, self.gamma, self.lr, self.lr_scheduling = list(weights), gamma, lr, lr_scheduling
         self.dist = dist

@@ -183,7 +183,8 @@ def validate(args, weights, ds, val_idx, dist=None):
     """EPE / Fl-all of flows_final over the validation pairs (reference train.py:77,124-131), sharded over the ranks."""
     from pwcnet_amd import PWCDCNet, sharding
     net = PWCDCNet(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
-                   use_dc=args.use_dc, output_level=args.output_level)
+                   use_dc=args.use_dc, output_level=args.output_level, normalize_features=args.normalize_features,
+                   norm_eps=args.norm_eps)
     net.load_weights(weights)
     return sharding.evaluate_pairs(lambda a, b: net(a / 255.0, b / 255.0)[0],
                                    lambda i: tuple(torch.from_numpy(x) for x in ds[val_idx[i]]),
@@ -202,7 +203,8 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
                                occ_pool=args.occ_pool)
 
     model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
-                           use_dc=args.use_dc, output_level=args.output_level)
+                           use_dc=args.use_dc, output_level=args.output_level, normalize_features=args.normalize_features,
+                           norm_eps=args.norm_eps)
     if args.resume is not None:
         print(f"Loading learned model from checkpoint {args.resume}")
         model.load_weights(ckpt.load_weights(args.resume))
@@ -261,6 +263,11 @@ def main():
     ap.add_argument("--no-dc", dest="use_dc", action="store_false")
     ap.set_defaults(use_dc=False)
     ap.add_argument("--output_level", type=int, default=4)
+    ap.add_argument("--normalize_features", action="store_true",
+                    help="correlate layer-normalised feature maps: one norm over the two maps of a pair at every level, the "
+                         "estimator keeps the raw ones.  A checkpoint carries no marker for this: infer.py, infer_continuous.py "
+                         "and evaluate.py must be given the flag the weights were trained with")
+    ap.add_argument("--norm_eps", type=float, default=1e-16, help="--normalize_features: epsilon under the square root [1e-16]")
     ap.add_argument("--loss", default="multiscale", choices=["multiscale", "robust", "unsup"],
                     help="multiscale | robust: supervised (Trainer); unsup: photometric + smoothness, no labels [multiscale]")
     ap.add_argument("--photo", default="charbonnier", choices=["charbonnier", "census"],
@@ -417,7 +424,8 @@ def main():
     trainer = Trainer(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                       use_dc=args.use_dc, output_level=args.output_level, weights=args.weights, gamma=args.gamma,
                       lr=args.lr, lr_scheduling=args.lr_scheduling, device=f"cuda:{local_rank}", dist=dist,
-                      loss=args.loss, epsilon=args.epsilon, q=args.q)
+                      loss=args.loss, epsilon=args.epsilon, q=args.q, normalize_features=args.normalize_features,
+                      norm_eps=args.norm_eps)
     if args.resume is not None:
         print(f"Loading learned model from checkpoint {args.resume}")
         trainer.load_weights(ckpt.load_weights(args.resume))
