@@ -985,6 +985,38 @@ int pwc_feature_norm_grad_f32(const float* f0, int f0_cs, const float* f1, int f
                               size_t workspace_bytes, float* d0, int d0_cs, float* d1, int d1_cs, int accumulate,
                               pwc_stream_t stream);
 
+/* ==== flow distillation: a student flow against a teacher flow read through a window (self-supervision) ====
+ * (pwc_distill.hip; semantics, bounds and launch plan in DESIGN.md.)  student: N x h x w records of s_cs >= 2 floats, teacher:
+ * N x H x W records of t_cs >= 2 floats, 2 used of each; 0 <= y0, y0 + h <= H, 0 <= x0, x0 + w <= W.  The teacher and
+ * teacher_valid are read IN PLACE through the window: student pixel p = (y, x) pairs with teacher pixel P = (y + y0, x + x0).
+ * teacher_valid: N x H x W bytes or NULL (every pixel); exclude: N x h x w bytes or NULL (none).  Pixel p CONTRIBUTES iff
+ * teacher_valid is non-zero at P, exclude is zero at p, both teacher components at P are finite with |.| <= 1e9 (the .flo
+ * sentinel rule) and both student components at p are finite.
+ *   sums[n] = sum over the contributing p of rho(student[p,0] - teacher[P,0]) + rho(student[p,1] - teacher[P,1]),
+ *   rho(d) = (d^2 + eps^2)^q,  counts[n] = the number of contributing p (exact).
+ * Every pixel's value is a double, the sums are taken in double -- cut into parts by (h, w) alone, never by N, and added in a
+ * fixed order -- and rounded to float32 once: two calls give the same bits, an image gives the same bits alone and in a batch,
+ * with 8-byte accesses (even channel strides, pointers on 8-byte boundaries) and without.  A pixel that does not contribute adds
+ * exactly 0; a mask that rules it out keeps its flows from being read.  No atomics, no host synchronisation.  Two launches.
+ * workspace: pwc_flow_distill_workspace_bytes(N, h, w) = 12 * N * parts bytes (0 for sizes that are refused), 8-byte aligned.
+ * Checks, before any launch, in this order: a null student or teacher, N, h, w, H, W < 1, a channel stride below 2, a window
+ * that is not inside the teacher, eps not positive, q outside (0, 1] (PWC_EINVAL); h * w or H * W >= 2^31, N > 65535
+ * (PWC_ERANGE); a flow off a 4-byte boundary (PWC_EALIGN); a null sums, counts or workspace (PWC_EINVAL), a workspace off an
+ * 8-byte boundary (PWC_EALIGN), a short one (PWC_EINVAL). */
+size_t pwc_flow_distill_workspace_bytes(int N, int h, int w);
+int pwc_flow_distill_sums_f32(const float* student, int s_cs, const float* teacher, int t_cs, int N, int h, int w, int H, int W,
+                              int y0, int x0, const uint8_t* teacher_valid, const uint8_t* exclude, double eps, double q,
+                              float* sums, int32_t* counts, void* workspace, size_t workspace_bytes, pwc_stream_t stream);
+/* dstudent (+)= the gradient of sum_n dsums[n] sums[n] with respect to the student; the teacher is a constant.  A contributing
+ * pixel gets float32(dsums[n] * 2 q d (d^2 + eps^2)^(q - 1)) per component, formed in double and rounded once; any other pixel
+ * gets 0 (accumulate == 0) or is left alone (accumulate != 0); accumulate adds exactly what a plain call writes.  A gather:
+ * one lane per student pixel, no scatter, no atomics, no workspace.  dsums: N floats on the device.  dstudent: N x h x w
+ * records of ds_cs >= 2 floats; it must not overlap the inputs.  Checks as above up to the flows' alignment, then a null dsums
+ * or dstudent, ds_cs < 2 (PWC_EINVAL), dsums or dstudent off a 4-byte boundary (PWC_EALIGN).  One launch. */
+int pwc_flow_distill_grad_f32(const float* student, int s_cs, const float* teacher, int t_cs, int N, int h, int w, int H, int W,
+                              int y0, int x0, const uint8_t* teacher_valid, const uint8_t* exclude, double eps, double q,
+                              const float* dsums, float* dstudent, int ds_cs, int accumulate, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,12 +24,16 @@ level with weight 0 adds nothing and is still reported.
 "smoothness", "occluded" (the share of the 2 N H W pixels the masks rule out; with occlusion), "consistency" (with
 consistency_weight > 0), 0-dim detached tensors but for "occluded", a float; "levels": a list of floats, the unweighted data
 value per level (with level weights).
+
+selfsup_term (train.py --selfsup_weight) is not part of the call: it compares the flows of a second, narrower pass with this
+pass's flows, and the trainer adds it with a backward of its own.
 """
 import torch
 
 from .pyramid import frame_pyramid, level_flow_scale, mask_pyramid
 from .splat import range_valid
-from .unsup import census_loss, fb_consistency_loss, fb_valid, photometric_loss, smoothness_loss, ssim_loss
+from .unsup import (census_loss, fb_consistency_loss, fb_valid, flow_distill_sums, photometric_loss, smoothness_loss,
+                    ssim_loss)
 
 
 class UnsupObjective:
@@ -37,7 +41,7 @@ class UnsupObjective:
 
     def __init__(self, photo="charbonnier", census_radius=3, photo_eps=1e-3, photo_q=0.5, ssim_weight=0.0, ssim_radius=1,
                  smooth_weight=0.1, smooth_order=1, edge_alpha=10.0, occlusion="none", occ_alpha1=0.01, occ_alpha2=0.5,
-                 occ_min_range=0.5, consistency_weight=0.0, level_weights=None, occ_pool=0.5):
+                 occ_min_range=0.5, consistency_weight=0.0, level_weights=None, occ_pool=0.5, selfsup_mask=None):
         if photo not in ("charbonnier", "census"):
             raise ValueError(f"UnsupObjective: photo must be 'charbonnier' or 'census', got {photo!r}")
         if occlusion not in ("none", "fb", "range"):
@@ -60,6 +64,13 @@ class UnsupObjective:
                              "the backward flow of one forward)")
         if not 0.0 < float(occ_pool) <= 1.0:
             raise ValueError(f"UnsupObjective: occ_pool must be in (0, 1], got {occ_pool}")
+        if selfsup_mask is None:
+            selfsup_mask = "all" if occlusion == "none" else "occluded"
+        if selfsup_mask not in ("occluded", "teacher", "all"):
+            raise ValueError(f"UnsupObjective: selfsup_mask must be 'occluded', 'teacher' or 'all', got {selfsup_mask!r}")
+        if selfsup_mask != "all" and occlusion == "none":
+            raise ValueError(f"UnsupObjective: selfsup_mask {selfsup_mask!r} needs occlusion 'fb' or 'range' (it reads the "
+                             "occlusion masks); without them use 'all'")
         if level_weights is not None:
             level_weights = tuple(float(w) for w in level_weights)
             if not level_weights or min(level_weights) < 0 or not all(w == w for w in level_weights):
@@ -69,6 +80,7 @@ class UnsupObjective:
         self.smooth_weight, self.smooth_order, self.edge_alpha = smooth_weight, smooth_order, edge_alpha
         self.occlusion, self.occ_alpha1, self.occ_alpha2, self.occ_min_range = occlusion, occ_alpha1, occ_alpha2, occ_min_range
         self.consistency_weight, self.occ_pool = consistency_weight, occ_pool
+        self.selfsup_mask = selfsup_mask
         # None (absent or all zeros) is the loss on flows_final alone, no pyramid launch
         self.level_weights = level_weights if level_weights and any(w != 0 for w in level_weights) else None
         self.term = "census" if photo == "census" else "photometric"
@@ -132,6 +144,28 @@ class UnsupObjective:
                 sm = sum(self.smooth_term(scale * f, i0) for i0, _, f, _ in ways) / len(ways)
                 added = added + wl * (d + self.smooth_weight * sm)
         return added, values
+
+    def selfsup_term(self, student_final, teacher_final, offset, teacher_masks=None, student_masks=None, return_counts=False):
+        """The self-supervision term, 0-dim: flow_distill_loss of the student pass's flows_final against the teacher pass's, the
+        student view being the window of the teacher view at offset = (y0, x0); eps and q are the objective's photo_eps and
+        photo_q.  Flows: (N, ...), or with occlusion (2N, ...) stacked fw / bw as everywhere here -- the two directions are one
+        batch, so both run in ONE launch and the value is the mean over both.  teacher_masks / student_masks: the (m_fw, m_bw)
+        pairs of the two passes (self.masks), concatenated the same way.  selfsup_mask "occluded" (UFlow): a pixel contributes
+        where the teacher's own check passed and the student's failed; "teacher": where the teacher's passed; "all": no masks
+        (what is passed is not read).  The teacher carries no gradient.  return_counts: (term, counts (batch,) int32)."""
+        tv = ex = None
+        if self.selfsup_mask != "all":
+            if teacher_masks is None or len(teacher_masks) != 2:
+                raise ValueError(f"UnsupObjective: selfsup_mask {self.selfsup_mask!r} needs teacher_masks = (m_fw, m_bw)")
+            tv = torch.cat([teacher_masks[0], teacher_masks[1]])
+        if self.selfsup_mask == "occluded":
+            if student_masks is None or len(student_masks) != 2:
+                raise ValueError("UnsupObjective: selfsup_mask 'occluded' needs student_masks = (m_fw, m_bw)")
+            ex = torch.cat([student_masks[0], student_masks[1]])
+        sums, counts = flow_distill_sums(student_final, teacher_final, offset, teacher_valid=tv, exclude=ex, eps=self.photo_eps,
+                                         q=self.photo_q)
+        term = sums.sum() / (2 * counts.sum().clamp(min=1)).to(torch.float32)
+        return (term, counts) if return_counts else term
 
     # ------------------------------------------------------------------ the objective
     def _check(self, images_0, images_1, flows_final, flows_pyramid, masks):

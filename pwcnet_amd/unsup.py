@@ -15,6 +15,9 @@
     fb_consistency_sums(flows_fw, flows_bw, ...)        -> (sums_fw, counts_fw, sums_bw, counts_bw)
     fb_consistency_loss(...)                            -> (sums_fw.sum() + sums_bw.sum()) / (2 * (counts_fw.sum() + counts_bw.sum()).clamp(min=1))
 
+    flow_distill_sums(student, teacher, offset, ...)    -> (sums (N,), counts (N,) int32)
+    flow_distill_loss(...)                              -> sums.sum() / (2 * counts.sum().clamp(min=1))
+
 With rho(d) = (d^2 + eps^2)^q: the photometric term of a pixel is sum_c rho(images_0 - bilinear sample of images_1 at the pixel
 moved by flow_scale * flow), over the pixels that are valid (`valid`, grad_ops.mask_ptr's format, e.g. an occlusion mask of the
 caller's) and whose sample point lies inside the frame; the smoothness term is the sum of exp(-alpha * mean_c |d image|) *
@@ -31,6 +34,8 @@ the definition is in its docstring).  It is not differentiable: the masks are co
 smoothness_*(order=2) penalises the SECOND difference of the flow (a constant slope is free), and fb_consistency_* is UnFlow's
 third term: rho of f + g, the quantity fb_valid thresholds, at the pixels the masks keep, differentiable with respect to BOTH
 flows (the gradient with respect to the sampled flow is a scatter, added in 64-bit fixed point: bit reproducible).
+flow_distill_* is the self-supervision term: rho of a student flow minus a teacher flow of the same direction, the teacher a
+wider field read in place through a window (csrc/pwc_distill.hip), differentiable with respect to the student only.
 """
 import torch
 
@@ -583,3 +588,122 @@ def fb_consistency_loss(flows_fw, flows_bw, flow_scale=1.0, valid_fw=None, valid
     """0-dim: the mean of rho over the contributing pixels of both directions and the two components; 0 when none contributes."""
     sums_fw, counts_fw, sums_bw, counts_bw = fb_consistency_sums(flows_fw, flows_bw, flow_scale, valid_fw, valid_bw, eps, q)
     return (sums_fw.sum() + sums_bw.sum()) / (2 * (counts_fw.sum() + counts_bw.sum()).clamp(min=1)).to(torch.float32)
+
+
+def _check_distill_mask(mask, what, shape, like):
+    """dtype (TypeError), shape and layout (ValueError) of a mask of the distillation term, named after its argument."""
+    if mask is None:
+        return
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{what}: expected a torch.bool or torch.uint8 tensor, got "
+                        f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask)}")
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected shape {tuple(shape)}, {like}'s (N, H, W), got {tuple(mask.shape)}")
+    if not mask.is_contiguous():
+        raise ValueError(f"{what}: the mask must be contiguous")
+
+
+def _check_distill(student, teacher, offset, teacher_valid, exclude):
+    """The tensor checks of the distillation term, the device last; (y0, x0)."""
+    _check_nhwc(student, "student", (2,))
+    _check_nhwc(teacher, "teacher", (2,))
+    N, h, w, _ = student.shape
+    if N <= 0 or h <= 0 or w <= 0:
+        raise ValueError(f"student: empty tensor, shape {tuple(student.shape)}")
+    if teacher.shape[0] != N:
+        raise ValueError(f"teacher: expected a batch of {N}, the student's, got shape {tuple(teacher.shape)}")
+    try:
+        y0, x0 = offset
+    except (TypeError, ValueError):
+        raise ValueError(f"offset: expected a pair (y0, x0) of integers, got {offset!r}") from None
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (y0, x0)):
+        raise ValueError(f"offset: expected a pair (y0, x0) of integers, got {offset!r}")
+    H, W = teacher.shape[1:3]
+    if y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"offset: the {h} x {w} student at {(y0, x0)} does not lie inside the {H} x {W} teacher")
+    _check_distill_mask(teacher_valid, "teacher_valid", (N, H, W), "the teacher")
+    _check_distill_mask(exclude, "exclude", (N, h, w), "the student")
+    for what, t in (("student", student), ("teacher", teacher), ("teacher_valid", teacher_valid), ("exclude", exclude)):
+        if t is not None and (not t.is_cuda or t.device != student.device):
+            raise ValueError(f"{what}: the tensor is on {t.device}; pwcnet_amd runs on the GPU only, all arguments on one device")
+    return y0, x0
+
+
+def _distill_call(entry, student, teacher, y0, x0, teacher_valid, exclude, eps, q, *tail):
+    sv, student = as_view(student, "student")
+    tv, teacher = as_view(teacher, "teacher")
+    rc = entry(_p(sv.ptr), sv.cs, _p(tv.ptr), tv.cs, sv.N, sv.H, sv.W, tv.H, tv.W, y0, x0,
+               None if teacher_valid is None else _p(teacher_valid.data_ptr()),
+               None if exclude is None else _p(exclude.data_ptr()), eps, q, *tail, _lib.current_stream())
+    return rc, sv, student, teacher
+
+
+def flow_distill_grad(student, teacher, dsums, dstudent=None, offset=(0, 0), teacher_valid=None, exclude=None, eps=1e-3, q=0.5,
+                      accumulate=False):
+    """dstudent (+)= the gradient of (dsums * flow_distill_sums(...)[0]).sum() w.r.t. student (pwc_flow_distill_grad_f32); dsums:
+    (N,) on the GPU.  dstudent None: a new tensor; a (N,h,w,2) tensor or channel slice of a wider buffer is written in place;
+    accumulate: added onto dstudent, pixels that do not contribute are left alone (without it they get 0).  Returns dstudent.
+    What the autograd backward of flow_distill_sums calls."""
+    eps, q = _check_rho(eps, q, "flow_distill_grad")
+    y0, x0 = _check_distill(student, teacher, offset, teacher_valid, exclude)
+    student, teacher = student.detach(), teacher.detach()
+    sv = as_view(student, "student")[0]
+    up = torch.empty((sv.N,), dtype=torch.float32, device=student.device).copy_(dsums)       # contiguous float32, its own
+    dv, dstudent = _dflow_view(dstudent, sv, student.device)
+    rc = _distill_call(_lib.lib().pwc_flow_distill_grad_f32, student, teacher, y0, x0, teacher_valid, exclude, eps, q,
+                       _p(up.data_ptr()), _p(dv.ptr), dv.cs, 1 if accumulate else 0)[0]
+    _lib.check(rc, "flow distill grad")
+    return dstudent
+
+
+class _FlowDistillSums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, student, teacher, offset, teacher_valid, exclude, eps, q):
+        ctx.set_materialize_grads(False)
+        L = _lib.lib()
+        dev = student.device
+        N, h, w, _ = student.shape
+        sums = torch.empty((N,), dtype=torch.float32, device=dev)
+        counts = torch.empty((N,), dtype=torch.int32, device=dev)
+        ws = torch.empty(((L.pwc_flow_distill_workspace_bytes(N, h, w) + 7) // 8 + 1,), dtype=torch.float64, device=dev)
+        rc, _, student, teacher = _distill_call(L.pwc_flow_distill_sums_f32, student, teacher, offset[0], offset[1], teacher_valid,
+                                                exclude, eps, q, _p(sums.data_ptr()), _p(counts.data_ptr()), _p(ws.data_ptr()),
+                                                8 * ws.numel())
+        _lib.check(rc, "flow distill sums")
+        ctx.save_for_backward(student, teacher)
+        ctx.masks, ctx.consts = (teacher_valid, exclude), (offset, eps, q)
+        ctx.mark_non_differentiable(counts)
+        return sums, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dsums, _dcounts):
+        if dsums is None or not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        student, teacher = ctx.saved_tensors
+        offset, eps, q = ctx.consts
+        dstudent = flow_distill_grad(student, teacher, dsums, None, offset, ctx.masks[0], ctx.masks[1], eps, q)
+        return dstudent, None, None, None, None, None, None
+
+
+def flow_distill_sums(student, teacher, offset=(0, 0), teacher_valid=None, exclude=None, eps=1e-3, q=0.5):
+    """(sums (N,) float32, counts (N,) int32) of the self-supervision (distillation) term of DDFlow / SelFlow / UFlow / ARFlow:
+    the flow of a narrow view, `student` (N,h,w,2), against the flow the network gave on a wider view, `teacher` (N,H,W,2), read
+    in place through the h x w window at offset = (y0, x0): student pixel p = (y, x) pairs with teacher pixel P = (y + y0, x + x0)
+    -- nothing is cropped or copied, channel slices of wider buffers are read where they are.  p contributes iff teacher_valid[P]
+    (where given: (N,H,W) torch.bool / torch.uint8, read through the same window), not exclude[p] (where given: (N,h,w)), both
+    teacher components are finite with |.| <= 1e9 (flow_io.flow_valid's rule) and both student components are finite;
+        sums[n] = sum over the contributing pixels of rho(student[p,0] - teacher[P,0]) + rho(student[p,1] - teacher[P,1]),
+    rho(d) = (d^2 + eps^2)^q, every pixel in double, the sum in double and rounded once; counts[n] their number (exact).  Both
+    flows in the same unit: the window moves no flow vector.  sums is differentiable w.r.t. student (pwc_flow_distill_grad_f32: a
+    gather, bit reproducible); the teacher is detached here, whatever it carries, and the masks are constants.  No double
+    backward."""
+    eps, q = _check_rho(eps, q, "flow_distill_sums")
+    y0, x0 = _check_distill(student, teacher, offset, teacher_valid, exclude)
+    return _FlowDistillSums.apply(student, teacher.detach(), (y0, x0), teacher_valid, exclude, eps, q)
+
+
+def flow_distill_loss(student, teacher, offset=(0, 0), teacher_valid=None, exclude=None, eps=1e-3, q=0.5):
+    """0-dim: the mean of rho over the contributing pixels and the two components; 0 when no pixel contributes."""
+    sums, counts = flow_distill_sums(student, teacher, offset, teacher_valid, exclude, eps, q)
+    return sums.sum() / (2 * counts.sum().clamp(min=1)).to(torch.float32)

@@ -51,6 +51,16 @@ mask_pyramid of the two masks: a level pixel is kept when at least --occ_pool (0
 its block is.  The consistency term stays on flows_final.  The step line then ends in `levels <v0> <v1> <v2> <v3> <v4>`, the
 unweighted data value of each level; a level too small for a term (a window of --census_radius 3 on a 1 x 2 level) prints nan and
 adds nothing.  Absent or all zeros: the run as it was, no pyramid launch, the same step lines.
+`--selfsup_weight W` adds the self-supervision term of DDFlow, SelFlow, UFlow and ARFlow: after the step's forward and backward at
+--crop_shape, the same network runs on the centre window of the same frames (--selfsup_crop C pixels removed per side, cut on the
+GPU by augment_pairs(crop_params(N, C, C)), the plain crop), and W * flow_distill_loss (pwcnet_amd/unsup.py) pulls that student
+flow to the first pass's detached flow read through the window: a pixel that leaves the narrow frame has no photometric signal
+there, and the wide pass often still sees where it goes.  The wide pass is the one that is trained and the teacher (UFlow's
+arrangement): two forwards and two backwards per step, one optimiser step.  --selfsup_mask occluded (the default with --occlusion
+fb | range) takes the pixels where the wide pass's occlusion check passed and the student's own check, with the same settings,
+failed; teacher: where the wide pass's passed; all (the default without occlusion): every pixel.  --selfsup_after K starts the term
+and its forward at global step K.  The step line then ends in `selfsup <value>  selfsup_share <the share of the student pixels
+that contributed>`, and loss/unsup includes W * the term.  W = 0 (the default): the step as it was, no second forward.
 Single process, constant learning rate; --gamma is Adam's weight_decay (the same gamma * l2_loss gradient).
 
 Sparse ground truth: every pair comes with a validity mask -- the .flo "unknown" sentinel (|u| or |v| above 1e9),
@@ -191,6 +201,45 @@ def validate(args, weights, ds, val_idx, dist=None):
                                    len(val_idx), batch=args.batch_size, dist=dist, device="cuda", metrics=True)
 
 
+def unsup_step(model, objective, images_0, images_1, selfsup_weight=0.0, selfsup_crop=64):
+    """The forwards and backwards of one label-free step (the caller zeroes the gradients before and steps the optimiser after):
+    (loss, terms), both detached.  selfsup_weight > 0 adds the self-supervision pass; 0 is the step without it, launch for launch."""
+    stacked = objective.occlusion != "none"
+    if stacked:
+        # both pair orders in one forward: the first N flows are 0 -> 1, the last N are 1 -> 0
+        flows_final, flows_pyramid = model(torch.cat([images_0, images_1]), torch.cat([images_1, images_0]))
+    else:
+        flows_final, flows_pyramid = model(images_0, images_1)
+    N, H, W, _ = images_0.shape
+    teacher_masks = None
+    if selfsup_weight > 0 and objective.selfsup_mask != "all":
+        # the wide pass is also the teacher: its masks are made here once and handed to the objective
+        teacher_masks = objective.masks(flows_final[:N], flows_final[N:])[:2]
+    loss, terms = objective(images_0, images_1, flows_final, flows_pyramid, masks=teacher_masks)
+    loss.backward()
+    if not selfsup_weight > 0:
+        return loss.detach(), terms
+    # the first tape is spent (one tape of the module alive at a time).  The student is the same network on the centre window of
+    # the same frames; its flow is pulled to the wide pass's, read through the window, where that one saw more
+    from pwcnet_amd import augment_pairs, crop_params
+    C = selfsup_crop
+    teacher, loss = flows_final.detach(), loss.detach()
+    del flows_final, flows_pyramid
+    small_0, small_1, _, _ = augment_pairs(images_0, images_1, crop_params(N, C, C), (H - 2 * C, W - 2 * C))
+    if stacked:
+        student, _ = model(torch.cat([small_0, small_1]), torch.cat([small_1, small_0]))
+    else:
+        student, _ = model(small_0, small_1)
+    student_masks = None
+    if objective.selfsup_mask == "occluded":
+        student_masks = objective.masks(student[:N], student[N:])[:2]
+    term, counts = objective.selfsup_term(student, teacher, (C, C), teacher_masks, student_masks, return_counts=True)
+    (selfsup_weight * term).backward()
+    terms["selfsup"] = term.detach()
+    terms["selfsup_share"] = float(counts.sum()) / float(student.shape[0] * student.shape[1] * student.shape[2])
+    return loss + selfsup_weight * term.detach(), terms
+
+
 def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
     """--loss unsup: no ground truth reaches the step; checkpoints through tf_state_dict(), so they load into PWCDCNet.
     aug (an Augmenter, --augment): `ds` holds whole frames, the batch is cut and jittered on the GPU, validation reads val_ds."""
@@ -200,7 +249,7 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
                                smooth_order=args.smooth_order, edge_alpha=args.edge_alpha, occlusion=args.occlusion,
                                occ_alpha1=args.occ_alpha1, occ_alpha2=args.occ_alpha2, occ_min_range=args.occ_min_range,
                                consistency_weight=args.consistency_weight, level_weights=args.level_weights,
-                               occ_pool=args.occ_pool)
+                               occ_pool=args.occ_pool, selfsup_mask=args.selfsup_mask)
 
     model = PWCDCNetModule(num_levels=args.num_levels, search_range=args.search_range, warp_type=args.warp_type,
                            use_dc=args.use_dc, output_level=args.output_level, normalize_features=args.normalize_features,
@@ -220,13 +269,8 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
             else:
                 images_0, images_1 = (images_0 / 255.0).cuda(), (images_1 / 255.0).cuda()
             opt.zero_grad(set_to_none=True)
-            if args.occlusion != "none":
-                # both pair orders in one forward: the first N flows are 0 -> 1, the last N are 1 -> 0
-                flows_final, flows_pyramid = model(torch.cat([images_0, images_1]), torch.cat([images_1, images_0]))
-            else:
-                flows_final, flows_pyramid = model(images_0, images_1)
-            loss, terms = objective(images_0, images_1, flows_final, flows_pyramid)
-            loss.backward()
+            selfsup = args.selfsup_weight if global_step + 1 >= args.selfsup_after else 0.0
+            loss, terms = unsup_step(model, objective, images_0, images_1, selfsup, args.selfsup_crop)
             opt.step()
             global_step += 1
             n_steps += 1
@@ -238,6 +282,8 @@ def train_unsup(args, ds, train_idx, val_idx, val_ds=None, aug=None):
                 line += f"  consistency {float(terms['consistency']):.6f}"
             if "levels" in terms:
                 line += "  levels " + " ".join(f"{v:.6f}" for v in terms["levels"])
+            if "selfsup" in terms:
+                line += f"  selfsup {float(terms['selfsup']):.6f}  selfsup_share {terms['selfsup_share']:.4f}"
             print(f"step {global_step}: loss/unsup {float(loss):.6f}{line}")
         res = validate(args, model.tf_state_dict(), ds if val_ds is None else val_ds, val_idx)
         dt = time.time() - t0
@@ -300,6 +346,18 @@ def main():
     ap.add_argument("--occ_pool", type=float, default=0.5, metavar="F",
                     help="--level_weights with --occlusion: a level pixel is kept when at least this fraction of its block "
                          "is, in (0, 1]; 1 is a min-pool (0.5 is a choice, nobody has trained with it yet) [0.5]")
+    ap.add_argument("--selfsup_weight", type=float, default=0.0, metavar="W",
+                    help="--loss unsup: weight of the self-supervision term -- a second forward on the centre window of the "
+                         "batch, its flow against the first forward's through the window; 0: no second forward [0]")
+    ap.add_argument("--selfsup_crop", type=int, default=64, metavar="C",
+                    help="--selfsup_weight: pixels removed per side for the student view; --crop_shape - 2 C must be a "
+                         "positive multiple of 64 in both axes [64]")
+    ap.add_argument("--selfsup_after", type=int, default=0, metavar="K",
+                    help="--selfsup_weight: the term and its forward start at global step K [0]")
+    ap.add_argument("--selfsup_mask", default=None, choices=["occluded", "teacher", "all"],
+                    help="--selfsup_weight: the pixels of the term -- occluded: the wide pass's occlusion check passed and the "
+                         "student's failed (UFlow); teacher: the wide pass's passed; all: every pixel "
+                         "[occluded with --occlusion fb | range, else all]")
     ap.add_argument("--photo_eps", type=float, default=1e-3, help="--loss unsup: Charbonnier epsilon of both terms [1e-3]")
     ap.add_argument("--photo_q", type=float, default=0.5, help="--loss unsup: Charbonnier exponent of both terms [0.5]")
     ap.add_argument("--edge_alpha", type=float, default=10.0,
@@ -368,6 +426,20 @@ def main():
             ap.error("--level_weights takes one weight per flows_pyramid entry: five, with --output_level 4")
     if not 0.0 < args.occ_pool <= 1.0:
         ap.error("--occ_pool must be in (0, 1]")
+    if not args.selfsup_weight >= 0:
+        ap.error("--selfsup_weight must be non-negative")
+    if args.selfsup_weight > 0 and args.loss != "unsup":
+        ap.error("--selfsup_weight belongs to --loss unsup")
+    if args.selfsup_crop <= 0:
+        ap.error("--selfsup_crop must be positive (the student view is narrower than the batch's)")
+    if args.selfsup_after < 0:
+        ap.error("--selfsup_after must be non-negative")
+    if args.selfsup_weight > 0 and any(v - 2 * args.selfsup_crop < 64 or (v - 2 * args.selfsup_crop) % 64 for v in args.crop_shape):
+        ap.error(f"--selfsup_crop {args.selfsup_crop}: --crop_shape minus twice the crop must be a positive multiple of 64 in both "
+                 f"axes (the student view goes through the network), got "
+                 f"{args.crop_shape[0] - 2 * args.selfsup_crop} x {args.crop_shape[1] - 2 * args.selfsup_crop}")
+    if args.selfsup_mask in ("occluded", "teacher") and args.occlusion == "none":
+        ap.error(f"--selfsup_mask {args.selfsup_mask} reads the occlusion masks: it needs --occlusion fb or range")
     if not 0 < args.aug_scale[0] <= args.aug_scale[1]:
         ap.error("--aug_scale LO HI must satisfy 0 < LO <= HI")
     if min(args.aug_rotate, args.aug_translate, args.aug_rel_rotate, args.aug_rel_translate) < 0 or not 0 <= args.aug_flip <= 1:
