@@ -1017,6 +1017,52 @@ int pwc_flow_distill_grad_f32(const float* student, int s_cs, const float* teach
                               int y0, int x0, const uint8_t* teacher_valid, const uint8_t* exclude, double eps, double q,
                               const float* dsums, float* dstudent, int ds_cs, int accumulate, pwc_stream_t stream);
 
+/* ==== flow composition: the flow a -> c from the flows a -> b and b -> c (long-range flow from consecutive pairs) ====
+ * (pwc_compose.hip; semantics, bounds and launch plan in DESIGN.md.)  flow_ab, flow_bc, flow_ac: N x H x W records of ab_cs,
+ * bc_cs, ac_cs >= 2 floats, 2 used of each; valid_ab, valid_bc: N x H x W bytes or NULL (every pixel); valid_ac: N x H x W bytes.
+ * For pixel p = (n, y, x), f = flow_ab[p], q = (x + f0, y + f1) in double, x0 = floor(qx), x1 = min(x0 + 1, W - 1),
+ * wx = qx - x0, likewise in y (pwc_fb_valid_u8's sample):
+ *   flow_ac[p,k] = float32(f_k + S_k),  S_k = the sum over the four corners c of b_c flow_bc[c,k],
+ *   b_c = (wx | 1 - wx)(wy | 1 - wy), everything in double, rounded once.
+ * p is VALID iff valid_ab is non-zero at p, both f components are finite with |.| <= 1e9 (the .flo sentinel rule),
+ * 0 <= qx <= W - 1 and 0 <= qy <= H - 1, and at EACH of the four clamped corners valid_bc is non-zero and both flow_bc
+ * components are finite with |.| <= 1e9 -- whatever the corner's weight.  valid_ac[p] = 1 / 0 is that decision; an invalid
+ * pixel's flow_ac is exactly (1e10f, 1e10f), the .flo sentinel.  Selection is by branch: a pixel valid_ab rules out reads no
+ * flow, one whose f fails reads no corner, a NaN in a place the rule excludes reaches no output.  A gather, no workspace; with
+ * 8-byte accesses (even channel strides, pointers on 8-byte boundaries) and without, the bits are the same.  flow_ac must not
+ * overlap the inputs.  Checks, before the launch, in this order: a null flow_ab, flow_bc, flow_ac or valid_ac, N, H, W < 1, a
+ * channel stride below 2 (PWC_EINVAL); H * W >= 2^31, N > 65535 (PWC_ERANGE); a flow off a 4-byte boundary (PWC_EALIGN).
+ * One launch. */
+int pwc_flow_compose_f32(const float* flow_ab, int ab_cs, const float* flow_bc, int bc_cs, const uint8_t* valid_ab,
+                         const uint8_t* valid_bc, int N, int H, int W, float* flow_ac, int ac_cs, uint8_t* valid_ac,
+                         pwc_stream_t stream);
+/* (dflow_ab, dflow_bc) (+)= the gradient of the sum over the VALID p and k of g[p,k] flow_ac[p,k] with respect to both flows;
+ * the masks are constants, floor and clamp carry no gradient, g at an invalid pixel is not read.  g: N x H x W records of
+ * g_cs >= 2 floats.
+ *   dflow_ab[p,j] = float32(g[p,j] + sum_k g[p,k] dS_k/dq_j) at a valid p (a gather, in double, rounded once),
+ *     dS_k/dqx = (1 - wy)(B[y0,x1] - B[y0,x0]) + wy (B[y1,x1] - B[y1,x0]), B = flow_bc[.,k] -- 0 where the clamp made x1 = x0 --
+ *     likewise in y; an invalid p gets 0 (accumulate == 0) or is left alone;
+ *   dflow_bc[c,k] = the sum over the valid p and their corners c of b_c g[p,k] (a scatter).
+ * The scatter's sums are 64-bit fixed-point integers added by integer atomics, with a step RELATIVE to the image: a first
+ * launch forms m_n = max |g[p,k]| over the valid pixels of image n (order independent, on the device), contributions are
+ * multiplied by the exact power of two 2^-e_n, m_n <= 2^e_n < 2 m_n, and rounded to 2^-36; the finish converts each accumulator
+ * once and multiplies by 2^e_n.  So: two calls give the same bits, an image gives the same bits alone and in a batch, g times
+ * a power of two gives the gradients times that power of two (short of underflow), m_n == 0 gives exact zeros, and each
+ * contribution is off by at most 2^-37 2^e_n < 2^-36 m_n.  A non-finite g at a valid pixel of image n makes every element of
+ * dflow_bc[n] NaN (whatever accumulate holds; other images are untouched) and reaches dflow_ab by plain arithmetic; a cell
+ * whose sum reaches 2^25 2^e_n is NaN.  accumulate adds exactly what a plain call writes.  dflow_ab, dflow_bc: N x H x W
+ * records of dab_cs, dbc_cs >= 2 floats; they must not overlap the inputs or each other.
+ * workspace: pwc_flow_compose_grad_workspace_bytes(N, H, W) = 8 * (2 N H W + N) bytes (0 for sizes that are refused), 8-byte
+ * aligned.  Checks, before any launch, in this order: a null flow_ab, flow_bc, g, dflow_ab or dflow_bc, N, H, W < 1, a channel
+ * stride below 2 (PWC_EINVAL); H * W >= 2^31, N > 65535 (PWC_ERANGE); a flow or gradient off a 4-byte boundary (PWC_EALIGN); a
+ * null workspace (PWC_EINVAL), one off an 8-byte boundary (PWC_EALIGN), a short one (PWC_EINVAL).  A memset and three
+ * launches: per-image maximum, scatter (with the gather into dflow_ab), finish. */
+size_t pwc_flow_compose_grad_workspace_bytes(int N, int H, int W);
+int pwc_flow_compose_grad_f32(const float* flow_ab, int ab_cs, const float* flow_bc, int bc_cs, const uint8_t* valid_ab,
+                              const uint8_t* valid_bc, int N, int H, int W, const float* g, int g_cs, void* workspace,
+                              size_t workspace_bytes, float* dflow_ab, int dab_cs, float* dflow_bc, int dbc_cs, int accumulate,
+                              pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

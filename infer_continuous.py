@@ -12,6 +12,10 @@ batch (the reference feeds them one by one), and instead of a matplotlib figure 
 <out>/<dname>/<fname>.flo with the full-resolution flow.  --fit resize / pad keep the whole frame instead of cropping it: the
 frames are uploaded as uint8, resized or padded to the next multiples of 64 on the GPU, and the .flo has the frame's own size
 (the montage's pyramid levels stay at the network's geometry).
+--chain K also writes, for every frame i whose K successors have its size, <out>/<dname>/<fname>_plus<K>.flo: the flow from frame i
+to frame i + K, chained on the GPU from the K consecutive full-resolution flows (pwcnet_amd.chain_flows, across batch
+boundaries; after the refit where --fit is not crop).  A pixel whose chain leaves the frame or meets an unknown flow holds the
+.flo sentinel (flow_io.flow_valid).
 """
 import argparse
 import os
@@ -50,16 +54,64 @@ def build_parser():
     ap.add_argument("--normalize_features", action="store_true",
                     help="correlate layer-normalised feature maps (PWCDCNet(normalize_features=True)).  A checkpoint carries no marker for this: pass it exactly when the weights were trained with it")
     ap.add_argument("--norm_eps", type=float, default=1e-16, help="--normalize_features: epsilon under the square root [1e-16]")
+    ap.add_argument("--chain", type=int, default=0, metavar="K",
+                    help="also write <fname>_plus<K>.flo, the flow from frame i to frame i + K chained from the consecutive flows "
+                         "on the GPU; unknown pixels hold the .flo sentinel [0: off]")
     return ap
 
 
+def out_stem(path):
+    """(dname, fname) of a frame's outputs under --out."""
+    parts = re.split("[/.]", path)
+    return parts[-3:-1] if len(parts) >= 3 else ("", parts[-2])
+
+
+class Chainer:
+    """--chain K: takes the full-resolution flows i -> i + 1 as they come, batch after batch, keeps the last ones on the GPU and
+    writes <fname>_plus<K>.flo for every frame i whose K successors have its size as soon as its K flows are there."""
+
+    def __init__(self, span, frames, paths, out):
+        self.span, self.frames, self.paths, self.out = span, frames, paths, out
+        self.held = {}                               # pair index i -> its (H,W,2) flow on the GPU
+        self.next = 0                                # the first frame whose chain is not written yet
+
+    def add(self, first, flows):
+        """flows: (n,H,W,2) on the GPU, the flows of the pairs first, first + 1, ..."""
+        import pwcnet_amd
+        from pwcnet_amd import flow_io
+        K = self.span
+        for k in range(flows.shape[0]):
+            self.held[first + k] = flows[k]
+        last = first + flows.shape[0] - 1            # every pair up to here is held or done
+        while self.next + K - 1 <= last:
+            i0 = self.next
+            if any(self.frames[i0 + d].shape != self.frames[i0].shape for d in range(1, K + 1)):
+                self.next += 1
+                continue
+            i1 = i0                                  # frames i0 .. i1 start a chain over frames of one size
+            while i1 + K <= last and self.frames[i1 + K + 1].shape == self.frames[i0].shape:
+                i1 += 1
+            seq = torch.stack([self.held[i] for i in range(i0, i1 + K)])
+            chained = pwcnet_amd.chain_flows(seq, span=K)[0].cpu().numpy()
+            for i in range(i0, i1 + 1):
+                dname, fname = out_stem(self.paths[i])
+                os.makedirs(os.path.join(self.out, dname), exist_ok=True)
+                flow_io.write_flo(os.path.join(self.out, dname, f"{fname}_plus{K}.flo"), chained[i - i0])
+            self.next = i1 + 1
+        for i in [i for i in self.held if i < self.next]:
+            del self.held[i]
+
+
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
     paths = []
     for p in args.input_images:                      # expand wild-cards (test_continuous.py:75-78)
         paths.extend(sorted(glob(p)) if "*" in p else [p])
     if len(paths) < 2:
         raise ValueError("# of input images must be >= 2")
+    if args.chain < 0 or args.chain >= len(paths):
+        ap.error(f"--chain must be at least 0 and below the number of frames ({len(paths)}), got {args.chain}")
 
     from PIL import Image
     import pwcnet_amd
@@ -92,6 +144,7 @@ def main():
         jobs.append((i, j))
         i = j
     num_levels = model.nets[0].num_levels
+    chainer = Chainer(args.chain, frames, paths, args.out) if args.chain > 0 else None
     window = 2 * max(1, args.pipeline)               # batches submitted before the first one is read back
     for w0 in range(0, len(jobs), window):
         tickets = []
@@ -107,11 +160,12 @@ def main():
             flow_final, flows = ticket.result()
             if info is not None:
                 flow_final = pwcnet_amd.refit_flow(flow_final, info)
+            if chainer is not None:
+                chainer.add(i, flow_final.clone())   # (the replica writes its result buffer again at its next forward)
             flow_final = flow_final.cpu().numpy()
             flows = [f.cpu().numpy() for f in flows]
             for k in range(j - i):
-                parts = re.split("[/.]", paths[i + k])
-                dname, fname = (parts[-3:-1] if len(parts) >= 3 else ("", parts[-2]))
+                dname, fname = out_stem(paths[i + k])
                 os.makedirs(os.path.join(args.out, dname), exist_ok=True)
                 pyr = [f[k] * (20.0 / 2 ** (num_levels - l)) for l, f in enumerate(flows)]
                 Image.fromarray(pyramid_montage(frames[i + k], pyr)).save(os.path.join(args.out, dname, fname + ".png"))

@@ -10,6 +10,7 @@ from .unsup import (census_grad, census_loss, census_sums, fb_consistency_grad, 
                     fb_consistency_sums, fb_valid, flow_distill_grad, flow_distill_loss, flow_distill_sums, photometric_loss,
                     photometric_sums, smoothness_loss, smoothness_sums, ssim_grad, ssim_loss, ssim_sums)
 from .splat import forward_splat, range_map, range_valid, splat_grad  # noqa: F401
+from .compose import chain_flows, compose_flows, compose_grad  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
 from .augment import augment_pairs, crop_params, draw_params  # noqa: F401
 from .pyramid import frame_pyramid, level_flow_scale, mask_pyramid  # noqa: F401
@@ -22,4 +23,5 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "smoothness_sums", "smoothness_loss", "census_sums", "census_loss", "census_grad", "ssim_sums", "ssim_loss", "ssim_grad", "fb_valid",
            "fb_consistency_sums", "fb_consistency_loss", "fb_consistency_grad", "forward_splat", "splat_grad", "range_map", "range_valid", "FitInfo", "fit_frames", "fit_info",
            "refit_flow", "flow_any_size", "draw_params", "crop_params", "augment_pairs", "frame_pyramid", "mask_pyramid", "level_flow_scale",
-           "UnsupObjective", "FeatureNormLayer", "flow_distill_sums", "flow_distill_loss", "flow_distill_grad"]
+           "UnsupObjective", "FeatureNormLayer", "flow_distill_sums", "flow_distill_loss", "flow_distill_grad",
+           "compose_flows", "compose_grad", "chain_flows"]
