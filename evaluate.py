@@ -16,6 +16,10 @@ Fl-all, the 1/3/5-px error rates and the EPE by motion magnitude (pwcnet_amd.los
 16-bit flow PNGs are not read here: convert them to .flo plus a mask image first.
 Pairs are sharded contiguously over the ranks (one process per GPU, RCCL only for the final
 all-gather of the statistics / flows); rank 0 prints one JSON line.
+--save_dir D --save_vis also writes, per index, D/<index>.png and D/<index>_gt.png -- prediction and ground truth colour-coded
+with ONE radius, the ground truth's largest magnitude over its valid pixels, so the two compare side by side -- and
+D/<index>_err.png, the error on the log colour scale of KITTI's development kit (blue: below the Fl-all threshold, red: an
+outlier, black: no ground truth), all made on the GPU (pwcnet_amd.vis).
 """
 import argparse
 import json
@@ -32,6 +36,9 @@ def build_parser():
     ap.add_argument("--resume", default=None)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--save_dir", default=None, help="write every predicted flow as <index>.flo (rank 0, after the gather)")
+    ap.add_argument("--save_vis", action="store_true",
+                    help="with --save_dir: also write <index>.png and <index>_gt.png (the flows colour-coded with the ground truth's "
+                         "largest valid magnitude) and <index>_err.png (KITTI's log-scale error map), made on the GPU")
     ap.add_argument("--mask_is_invalid", action="store_true",
                     help="the mask column's images mark INVALID pixels with non-zero values (Sintel's invalid/)")
     ap.add_argument("--fit", choices=("crop", "resize", "pad"), default="crop",
@@ -44,7 +51,10 @@ def build_parser():
 
 
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    if args.save_vis and not args.save_dir:
+        ap.error("--save_vis requires --save_dir")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -105,6 +115,19 @@ def main():
             os.makedirs(args.save_dir, exist_ok=True)
             for i, f in enumerate(res["flows"].cpu().numpy()):
                 flow_io.write_flo(os.path.join(args.save_dir, f"{i:06d}.flo"), f)
+            if args.save_vis:                                     # in batches: three pictures per index, only uint8 comes back
+                for b0 in range(0, len(pairs), args.batch):
+                    idx = range(b0, min(b0 + args.batch, len(pairs)))
+                    loaded = [load_pair(i)[2:] for i in idx]
+                    gt = torch.stack([g for g, _ in loaded]).to(dev)
+                    valid = torch.stack([v for _, v in loaded]).to(dev)
+                    pred = res["flows"][b0:b0 + len(idx)]
+                    rad = pwcnet_amd.flow_max_radius(gt, valid)
+                    pictures = {"": pwcnet_amd.flow_to_color(pred, rad), "_gt": pwcnet_amd.flow_to_color(gt, rad, valid),
+                                "_err": pwcnet_amd.flow_error_color(pred, gt, valid)}
+                    for tag, batch in pictures.items():
+                        for i, picture in zip(idx, batch.cpu().numpy()):
+                            Image.fromarray(picture).save(os.path.join(args.save_dir, f"{i:06d}{tag}.png"))
         out = {"epe": res["epe"], "pairs": res["pairs"], "seconds": dt, "n_gpus": world}
         out.update({k: res[k] for k in ("fl_all", "px1", "px3", "px5", "epe_s0_10", "epe_s10_40", "epe_s40", "valid_px")})
         out["per_pair_epe"] = res["per_pair_epe"]

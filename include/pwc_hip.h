@@ -1063,6 +1063,61 @@ int pwc_flow_compose_grad_f32(const float* flow_ab, int ab_cs, const float* flow
                               size_t workspace_bytes, float* dflow_ab, int dab_cs, float* dflow_bc, int dbc_cs, int accumulate,
                               pwc_stream_t stream);
 
+/* ==== flow visualisation: Middlebury colour coding, frame tiles and KITTI's log-scale error map as RGB bytes ====
+ * (pwc_flowvis.hip; semantics, bounds and bytes in DESIGN.md 16.)  Every value is formed in double from the float32 inputs, as
+ * the sequence of IEEE operations flow_io.flow_to_color performs: no fused multiply-add, correctly rounded division and square
+ * root; atan2 is the only operation that may differ from numpy's.  A flow's scale is ONE float32 product per component, applied
+ * first; a pixel is KNOWN iff both products are finite with |.| <= 1e9 (the .flo sentinel rule, flow_io.flow_valid).
+ *
+ * max_rad[n] = the largest sqrt(u u + v v) over the pixels of image n that are known and, where valid is given, non-zero in
+ * it; 0 where there is none.  flow: N x H x W records of flow_cs >= 2 floats, 2 used; valid: N x H x W bytes or NULL;
+ * max_rad: N doubles, zeroed by the call itself.  A workgroup's maximum is added with one 64-bit integer atomic max on the bits
+ * (non-negative doubles order as their bits do): two calls give the same bits, an image gives the same bits alone and in a
+ * batch, and the value equals numpy's bit for bit.  Checks, before the memset, in this order: a null flow or max_rad, N, H,
+ * W < 1, flow_cs < 2 (PWC_EINVAL); H * W >= 2^31, N > 65535 (PWC_ERANGE); flow off a 4-byte or max_rad off an 8-byte boundary
+ * (PWC_EALIGN).  A memset and one launch. */
+int pwc_flow_max_radius_f64(const float* flow, int flow_cs, const uint8_t* valid, int N, int H, int W, float flow_scale,
+                            double* max_rad, pwc_stream_t stream);
+/* A tile of an output picture: what fills the columns [x0, x0 + tile_w) of every row of every image.  Output pixel (n, y, x)
+ * reads source pixel (n, y * src_h / out_h, (x - x0) * src_w / tile_w) (integer divisions: nearest neighbour with
+ * infer_continuous.pyramid_montage's integers; a source of the output's height and tile_w = src_w is read one to one).
+ *   PWC_VIS_FLOW       src: N x src_h x src_w records of src_cs >= 2 floats.  flow_io.flow_to_color with max_rad[n] as the
+ *                      radius: (u, v) = the scaled flow, (0, 0) where it is unknown or valid (N x src_h x src_w bytes, or NULL)
+ *                      is zero; scale = max_rad + DBL_EPSILON; u / scale, v / scale, rad / scale;
+ *                      fk = (atan2(-v, -u) / pi + 1) / 2 * 54, k0 = floor(fk), k1 = (k0 + 1) % 55, f = fk - k0,
+ *                      col = (1 - f) * wheel[k0] / 255 + f * wheel[k1] / 255; col = 1 - rad * (1 - col) where rad <= 1,
+ *                      col * 0.75 elsewhere; the byte is floor(255 * col).  max_rad: N doubles on the device, each finite
+ *                      and >= 0 (anything else gives unspecified colours, nothing is read out of bounds).
+ *   PWC_VIS_FRAME_U8   src: N x src_h x src_w x 3 bytes, copied.
+ *   PWC_VIS_FRAME_F32  src: N x src_h x src_w x 3 floats; the byte is rint(255 * x) in double, clamped to 0 .. 255, 0 for a NaN.
+ *   PWC_VIS_ERROR      src: the predicted flow, gt: the ground truth (records of gt_cs >= 2 floats), neither scaled.
+ *                      d = src - gt, d_err = |d|, d_mag = |gt|, n_err = min(d_err / 3.0, (d_err / d_mag) / 0.05), d_err / 3.0
+ *                      where d_mag == 0; the colour of the bin lo <= n_err < hi with the edges 0, 1/16, 1/8, 1/4, 1/2, 1, 2, 4,
+ *                      8, 16, inf: (49,54,149) (69,117,180) (116,173,209) (171,217,233) (224,243,248) (254,224,144) (253,174,97)
+ *                      (244,109,67) (215,48,39) (165,0,38).  A pixel whose gt is unknown or zero in valid is (0,0,0); one with a
+ *                      known gt and an unknown prediction gets the last bin.  No transcendental: exact. */
+enum { PWC_VIS_FLOW = 0, PWC_VIS_FRAME_U8 = 1, PWC_VIS_FRAME_F32 = 2, PWC_VIS_ERROR = 3 };
+#define PWC_VIS_MAX_TILES 8
+typedef struct pwc_vis_tile {
+    const void* src;
+    const float* gt;          /* PWC_VIS_ERROR */
+    const uint8_t* valid;     /* PWC_VIS_FLOW, PWC_VIS_ERROR: or NULL */
+    const double* max_rad;    /* PWC_VIS_FLOW */
+    int kind, src_cs, gt_cs, src_h, src_w, x0, tile_w;
+    float flow_scale;         /* PWC_VIS_FLOW */
+} pwc_vis_tile;
+/* out: N x out_h x out_w x 3 bytes (RGB), every pixel written: from the first of the 1 .. 8 tiles whose columns hold it, (0,0,0)
+ * where none does.  One launch on `stream` writes the whole batch; the table is copied into the kernel's arguments.  A lane
+ * writes four consecutive pixels of the flat (N, out_h, out_w) index as three dwords wherever out is on a 4-byte boundary, the
+ * tail (and every pixel of an output off that boundary) byte by byte; the bytes are the same.  Two calls give the same bytes, an
+ * image gives the same bytes alone and in a batch.  out must not overlap a source.  Checks, before the launch, in this order: a
+ * null tiles or out, ntiles outside 1 .. 8, N, out_h, out_w < 1, per tile a null src, src_h, src_w, tile_w < 1, columns outside
+ * [0, out_w], an unknown kind, a missing max_rad / gt, a channel stride below 2 (PWC_EINVAL); out_h * out_w or a tile's
+ * src_h * src_w >= 2^31, N > 65535 (PWC_ERANGE); a float source off a 4-byte, max_rad off an 8-byte boundary (PWC_EALIGN). */
+int pwc_flow_vis_tiles_u8(const pwc_vis_tile* tiles, int ntiles, int N, int out_h, int out_w, uint8_t* out, pwc_stream_t stream);
+/* wheel: 55 x 3 bytes, the colour wheel PWC_VIS_FLOW reads (flow_io.color_wheel(); a host copy, no launch). */
+int pwc_flow_vis_wheel_u8(uint8_t* wheel);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ batch of one pair, default PWCDCNet(), optional checkpoint restore (TF V2 bundle
 without TensorFlow), optional timing loop over repeated forwards of the same pair, then
 the 5-level flow pyramid rescaled to pixels at each level (x 20 / 2^(6-l), test.py:57-60).
 Writes <out>/flow_final.flo plus a colour-coded PNG per pyramid level instead of the
-reference's matplotlib PDF.  No interactive GPU prompt: the device is cuda:<--gpu>.
+reference's matplotlib PDF.  --vis gpu colours the PNGs on the GPU (pwcnet_amd.vis) instead of with numpy on copied-back flows;
+the .flo does not depend on it.  No interactive GPU prompt: the device is cuda:<--gpu>.
 """
 import argparse
 import os
@@ -34,6 +35,9 @@ def build_parser():
     ap.add_argument("--normalize_features", action="store_true",
                     help="correlate layer-normalised feature maps (PWCDCNet(normalize_features=True)).  A checkpoint carries no marker for this: pass it exactly when the weights were trained with it")
     ap.add_argument("--norm_eps", type=float, default=1e-16, help="--normalize_features: epsilon under the square root [1e-16]")
+    ap.add_argument("--vis", choices=("host", "gpu"), default="host",
+                    help="colour the PNGs with numpy on the copied-back flows, or on the GPU (pwcnet_amd.vis: only uint8 pictures "
+                         "and the final flow cross to the host) [host]")
     return ap
 
 
@@ -75,9 +79,16 @@ def main():
     flow_io.write_flo(os.path.join(args.out, "flow_final.flo"), flow_final[0].cpu().numpy())
     for l, flow in enumerate(flows):
         upscale = 20.0 / 2 ** (model.num_levels - l)
-        Image.fromarray(flow_io.flow_to_color(flow[0].cpu().numpy() * upscale)).save(
-            os.path.join(args.out, f"flow_level{l}.png"))
-    Image.fromarray(flow_io.flow_to_color(flow_final[0].cpu().numpy())).save(os.path.join(args.out, "flow_final.png"))
+        if args.vis == "gpu":
+            picture = pwcnet_amd.flow_to_color(flow[0:1], flow_scale=upscale)[0].cpu().numpy()
+        else:
+            picture = flow_io.flow_to_color(flow[0].cpu().numpy() * upscale)
+        Image.fromarray(picture).save(os.path.join(args.out, f"flow_level{l}.png"))
+    if args.vis == "gpu":
+        picture = pwcnet_amd.flow_to_color(flow_final[0:1])[0].cpu().numpy()
+    else:
+        picture = flow_io.flow_to_color(flow_final[0].cpu().numpy())
+    Image.fromarray(picture).save(os.path.join(args.out, "flow_final.png"))
     print("Figure saved")
 
 

@@ -16,6 +16,8 @@ frames are uploaded as uint8, resized or padded to the next multiples of 64 on t
 to frame i + K, chained on the GPU from the K consecutive full-resolution flows (pwcnet_amd.chain_flows, across batch
 boundaries; after the refit where --fit is not crop).  A pixel whose chain leaves the frame or meets an unknown flow holds the
 .flo sentinel (flow_io.flow_valid).
+--vis gpu builds every batch's montages in one launch on the GPU (pwcnet_amd.pyramid_montage): the pyramid levels are not copied
+to the host, only the uint8 pictures and the full-resolution flow are; the .flo files do not depend on it.
 """
 import argparse
 import os
@@ -57,6 +59,9 @@ def build_parser():
     ap.add_argument("--chain", type=int, default=0, metavar="K",
                     help="also write <fname>_plus<K>.flo, the flow from frame i to frame i + K chained from the consecutive flows "
                          "on the GPU; unknown pixels hold the .flo sentinel [0: off]")
+    ap.add_argument("--vis", choices=("host", "gpu"), default="host",
+                    help="build the montages with numpy on the copied-back pyramid, or on the GPU (pwcnet_amd.pyramid_montage: only "
+                         "uint8 pictures and the final flow cross to the host) [host]")
     return ap
 
 
@@ -151,24 +156,33 @@ def main():
         for i, j in jobs[w0:w0 + window]:
             if args.fit == "crop":
                 seq = torch.from_numpy(np.stack(frames[i:j + 1]).astype(np.float32) / 255.0).cuda()
-                info = None
+                info, shown = None, seq              # (a float32 frame made as u8 / 255 gives back u8)
             else:                                    # uint8 upload; / 255 and the fit in one launch on the caller's stream
-                seq, info = pwcnet_amd.fit_frames(torch.from_numpy(np.stack(frames[i:j + 1])).cuda(), args.fit)
-            tickets.append((i, j, info, model.submit(seq[:-1].contiguous(), seq[1:].contiguous())))
+                shown = torch.from_numpy(np.stack(frames[i:j + 1])).cuda()
+                seq, info = pwcnet_amd.fit_frames(shown, args.fit)
+            tickets.append((i, j, info, shown if args.vis == "gpu" else None,
+                            model.submit(seq[:-1].contiguous(), seq[1:].contiguous())))
         model.synchronize()
-        for i, j, info, ticket in tickets:
+        for i, j, info, shown, ticket in tickets:
             flow_final, flows = ticket.result()
             if info is not None:
                 flow_final = pwcnet_amd.refit_flow(flow_final, info)
             if chainer is not None:
                 chainer.add(i, flow_final.clone())   # (the replica writes its result buffer again at its next forward)
             flow_final = flow_final.cpu().numpy()
-            flows = [f.cpu().numpy() for f in flows]
+            scales = [20.0 / 2 ** (num_levels - l) for l in range(len(flows))]
+            if args.vis == "gpu":                    # one launch per batch; the pyramid stays on the GPU
+                montages = pwcnet_amd.pyramid_montage(shown[:-1], list(flows), scales).cpu().numpy()
+            else:
+                flows = [f.cpu().numpy() for f in flows]
             for k in range(j - i):
                 dname, fname = out_stem(paths[i + k])
                 os.makedirs(os.path.join(args.out, dname), exist_ok=True)
-                pyr = [f[k] * (20.0 / 2 ** (num_levels - l)) for l, f in enumerate(flows)]
-                Image.fromarray(pyramid_montage(frames[i + k], pyr)).save(os.path.join(args.out, dname, fname + ".png"))
+                if args.vis == "gpu":
+                    montage = montages[k]
+                else:
+                    montage = pyramid_montage(frames[i + k], [f[k] * s for f, s in zip(flows, scales)])
+                Image.fromarray(montage).save(os.path.join(args.out, dname, fname + ".png"))
                 flow_io.write_flo(os.path.join(args.out, dname, fname + ".flo"), flow_final[k])
     print("Figure saved")
 
