@@ -582,7 +582,7 @@ int pwc_conv3x3_dgrad_s2_narrow_f32(const float* dy, int dy_cs, const float* w_h
  * fp32 product, clipped: tf.image.resize_nearest_neighbor applied to the mask.  Invalid pixels are SELECTED out: neither pred
  * nor gt is read there, an invalid pixel adds exactly 0.0f to every sum and exactly 0 to every gradient whatever the two hold
  * (NaN, Inf, the .flo sentinel 1e10).  Every check precedes the launches: null pointers, sizes <= 0, channel strides < 2,
- * gt_div == 0, a workspace that is too small: PWC_EINVAL; ord outside {1, 2}: PWC_EUNSUPPORTED; H * W >= 2^31 or N > 65535
+ * gt_div == 0, a workspace that is too small: PWC_EINVAL; ord outside {1, 2}: PWC_EUNSUPPORTED; H * W > 2^31 - 65537 or N > 65535
  * (sums and metrics): PWC_ERANGE. */
 
 /* pwc_flow_norm_sums_f32 over the valid pixels: out_sums[n] as there, out_counts[n] = the number of valid pixels of image n
@@ -617,7 +617,7 @@ int pwc_flow_metrics_f32(const float* pred, int pred_cs, const float* gt, int gt
  *   rho(d) = (d^2 + eps^2)^q  (generalised Charbonnier),  rho'(d) = 2 q d (d^2 + eps^2)^(q - 1).
  * Every check precedes the launches: null pointers other than the optional ones, sizes <= 0, a channel stride below the
  * channel count, eps <= 0, q outside (0, 1], alpha < 0, a workspace that is too small: PWC_EINVAL; C outside 1..4:
- * PWC_EUNSUPPORTED; H * W >= 2^31 or N > 65535: PWC_ERANGE. */
+ * PWC_EUNSUPPORTED; H * W > 2^31 - 65537 or N > 65535: PWC_ERANGE. */
 
 /* Photometric term.  Pixel p = (n, y, x) samples images_1[n] at (py, px) = (y + flow_scale * flow[p,1], x + flow_scale *
  * flow[p,0]) and CONTRIBUTES iff (valid == NULL or valid[p] != 0, uint8_t[N][H][W]) and 0 <= px <= W - 1 and 0 <= py <= H - 1
@@ -682,7 +682,7 @@ int pwc_flow_smoothness2_grad_f32(const float* flow, int flow_cs, const float* i
  * order: two calls give the same bits.  workspace: at least pwc_census_workspace_floats(N, H, W, with_grad) floats, with_grad
  * 0 for the sums and 1 for the gradient.  Checks, in this order: null pointers and sizes <= 0 (PWC_EINVAL); C outside 1..4
  * or radius outside 1..3 (PWC_EUNSUPPORTED); a channel stride below the channel count, eps, scale, c1 or c2 <= 0, q outside
- * (0, 1] (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); a null or short workspace, null outputs (PWC_EINVAL). */
+ * (0, 1] (PWC_EINVAL); H * W > 2^31 - 65537 or N > 65535 (PWC_ERANGE); a null or short workspace, null outputs (PWC_EINVAL). */
 size_t pwc_census_workspace_floats(int N, int H, int W, int with_grad);
 int pwc_census_sums_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
                         float flow_scale, const uint8_t* valid, int N, int H, int W, int C, int radius, float scale,
@@ -722,7 +722,7 @@ int pwc_census_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_
  * parts = min(256, ceil(W / 32) * ceil(H / 8)) -- the part sums and counts, the planes of y (gradient: and of its two
  * derivatives), the in-frame bytes, and (gradient) three planes of doubles per channel behind one float of slack for their
  * alignment.  Checks, in this order: null pointers and sizes <= 0 (PWC_EINVAL); C outside 1..4 or radius outside 1..3
- * (PWC_EUNSUPPORTED); a channel stride below the channel count, c1 or c2 <= 0 or NaN (PWC_EINVAL); H * W >= 2^31 or N > 65535
+ * (PWC_EUNSUPPORTED); a channel stride below the channel count, c1 or c2 <= 0 or NaN (PWC_EINVAL); H * W > 2^31 - 65537 or N > 65535
  * (PWC_ERANGE); a null or short workspace, null outputs (PWC_EINVAL). */
 size_t pwc_ssim_workspace_floats(int N, int H, int W, int C, int with_grad);
 int pwc_ssim_sums_f32(const float* im0, int im0_cs, const float* im1, int im1_cs, const float* flow, int flow_cs,
@@ -761,7 +761,7 @@ int pwc_ssim_grad_f32(const float* im0, int im0_cs, const float* im1, int im1_cs
  * order: two calls give the same bits; no atomics); both may be NULL, and then no workspace is needed.  Otherwise workspace: at
  * least pwc_fb_workspace_floats(N, H, W) floats.  One launch for both directions, plus one small launch (a thread per image) per count
  * vector.  Checks, all before any launch: null flows or valid_a, N, H, W <= 0, a channel stride below 2, alpha1 or alpha2
- * negative or NaN, counts_b without valid_b (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); counts asked with a null or
+ * negative or NaN, counts_b without valid_b (PWC_EINVAL); H * W > 2^31 - 65537 or N > 65535 (PWC_ERANGE); counts asked with a null or
  * short workspace (PWC_EINVAL). */
 size_t pwc_fb_workspace_floats(int N, int H, int W);
 int pwc_fb_valid_u8(const float* flow_a, int a_cs, const float* flow_b, int b_cs, float flow_scale,
@@ -777,7 +777,7 @@ int pwc_fb_valid_u8(const float* flow_a, int a_cs, const float* flow_b, int b_cs
  * One launch for both directions (workgroup partials in `workspace`, at least pwc_fb_consistency_workspace_floats(N, H, W)
  * floats, added in a fixed tree), then one small launch per direction that adds the parts in index order: two calls give the
  * same bits.  Checks, all before any launch: null flows, N, H, W <= 0, a channel stride below 2, eps <= 0, q outside (0, 1],
- * a null output (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); a null or short workspace (PWC_EINVAL). */
+ * a null output (PWC_EINVAL); H * W > 2^31 - 65537 or N > 65535 (PWC_ERANGE); a null or short workspace (PWC_EINVAL). */
 size_t pwc_fb_consistency_workspace_floats(int N, int H, int W);
 int pwc_fb_consistency_sums_f32(const float* flow_a, int a_cs, const float* flow_b, int b_cs, float flow_scale,
                                 const uint8_t* valid_a, const uint8_t* valid_b, int N, int H, int W, float eps, float q,
@@ -832,7 +832,7 @@ int pwc_fb_consistency_grad_f32(const float* flow_a, int a_cs, const float* flow
  * workspace: 8-byte aligned, at least pwc_splat_workspace_bytes(N, H, W, C) = 8 * (N * H * W * (C + 1) + 1) bytes (0 for sizes
  * that are refused).  It holds the accumulators after the call: pwc_splat_grad_f32 reads them when normalize != 0.
  * Checks, all before any launch, in this order: a null flow, N, H, W <= 0, C < 0, a null x with C > 0 (PWC_EINVAL); C > 64
- * (PWC_EUNSUPPORTED); flow_cs < 2, x_cs < C (PWC_EINVAL); H * W >= 2^31 or N > 65535 (PWC_ERANGE); a null coverage, with C > 0
+ * (PWC_EUNSUPPORTED); flow_cs < 2, x_cs < C (PWC_EINVAL); H * W > 2^31 - 65537 or N > 65535 (PWC_ERANGE); a null coverage, with C > 0
  * a null out or out_cs < C (PWC_EINVAL); a null workspace (PWC_EINVAL), one off an 8-byte boundary (PWC_EALIGN), a short one
  * (PWC_EINVAL). */
 size_t pwc_splat_workspace_bytes(int N, int H, int W, int C);
@@ -1000,7 +1000,7 @@ int pwc_feature_norm_grad_f32(const float* f0, int f0_cs, const float* f1, int f
  * exactly 0; a mask that rules it out keeps its flows from being read.  No atomics, no host synchronisation.  Two launches.
  * workspace: pwc_flow_distill_workspace_bytes(N, h, w) = 12 * N * parts bytes (0 for sizes that are refused), 8-byte aligned.
  * Checks, before any launch, in this order: a null student or teacher, N, h, w, H, W < 1, a channel stride below 2, a window
- * that is not inside the teacher, eps not positive, q outside (0, 1] (PWC_EINVAL); h * w or H * W >= 2^31, N > 65535
+ * that is not inside the teacher, eps not positive, q outside (0, 1] (PWC_EINVAL); h * w or H * W > 2^31 - 65537, N > 65535
  * (PWC_ERANGE); a flow off a 4-byte boundary (PWC_EALIGN); a null sums, counts or workspace (PWC_EINVAL), a workspace off an
  * 8-byte boundary (PWC_EALIGN), a short one (PWC_EINVAL). */
 size_t pwc_flow_distill_workspace_bytes(int N, int h, int w);
@@ -1031,7 +1031,7 @@ int pwc_flow_distill_grad_f32(const float* student, int s_cs, const float* teach
  * flow, one whose f fails reads no corner, a NaN in a place the rule excludes reaches no output.  A gather, no workspace; with
  * 8-byte accesses (even channel strides, pointers on 8-byte boundaries) and without, the bits are the same.  flow_ac must not
  * overlap the inputs.  Checks, before the launch, in this order: a null flow_ab, flow_bc, flow_ac or valid_ac, N, H, W < 1, a
- * channel stride below 2 (PWC_EINVAL); H * W >= 2^31, N > 65535 (PWC_ERANGE); a flow off a 4-byte boundary (PWC_EALIGN).
+ * channel stride below 2 (PWC_EINVAL); H * W > 2^31 - 65537, N > 65535 (PWC_ERANGE); a flow off a 4-byte boundary (PWC_EALIGN).
  * One launch. */
 int pwc_flow_compose_f32(const float* flow_ab, int ab_cs, const float* flow_bc, int bc_cs, const uint8_t* valid_ab,
                          const uint8_t* valid_bc, int N, int H, int W, float* flow_ac, int ac_cs, uint8_t* valid_ac,
@@ -1054,7 +1054,7 @@ int pwc_flow_compose_f32(const float* flow_ab, int ab_cs, const float* flow_bc, 
  * records of dab_cs, dbc_cs >= 2 floats; they must not overlap the inputs or each other.
  * workspace: pwc_flow_compose_grad_workspace_bytes(N, H, W) = 8 * (2 N H W + N) bytes (0 for sizes that are refused), 8-byte
  * aligned.  Checks, before any launch, in this order: a null flow_ab, flow_bc, g, dflow_ab or dflow_bc, N, H, W < 1, a channel
- * stride below 2 (PWC_EINVAL); H * W >= 2^31, N > 65535 (PWC_ERANGE); a flow or gradient off a 4-byte boundary (PWC_EALIGN); a
+ * stride below 2 (PWC_EINVAL); H * W > 2^31 - 65537, N > 65535 (PWC_ERANGE); a flow or gradient off a 4-byte boundary (PWC_EALIGN); a
  * null workspace (PWC_EINVAL), one off an 8-byte boundary (PWC_EALIGN), a short one (PWC_EINVAL).  A memset and three
  * launches: per-image maximum, scatter (with the gather into dflow_ab), finish. */
 size_t pwc_flow_compose_grad_workspace_bytes(int N, int H, int W);
@@ -1074,7 +1074,7 @@ int pwc_flow_compose_grad_f32(const float* flow_ab, int ab_cs, const float* flow
  * max_rad: N doubles, zeroed by the call itself.  A workgroup's maximum is added with one 64-bit integer atomic max on the bits
  * (non-negative doubles order as their bits do): two calls give the same bits, an image gives the same bits alone and in a
  * batch, and the value equals numpy's bit for bit.  Checks, before the memset, in this order: a null flow or max_rad, N, H,
- * W < 1, flow_cs < 2 (PWC_EINVAL); H * W >= 2^31, N > 65535 (PWC_ERANGE); flow off a 4-byte or max_rad off an 8-byte boundary
+ * W < 1, flow_cs < 2 (PWC_EINVAL); H * W > 2^31 - 65537, N > 65535 (PWC_ERANGE); flow off a 4-byte or max_rad off an 8-byte boundary
  * (PWC_EALIGN).  A memset and one launch. */
 int pwc_flow_max_radius_f64(const float* flow, int flow_cs, const uint8_t* valid, int N, int H, int W, float flow_scale,
                             double* max_rad, pwc_stream_t stream);
@@ -1113,7 +1113,7 @@ typedef struct pwc_vis_tile {
  * image gives the same bytes alone and in a batch.  out must not overlap a source.  Checks, before the launch, in this order: a
  * null tiles or out, ntiles outside 1 .. 8, N, out_h, out_w < 1, per tile a null src, src_h, src_w, tile_w < 1, columns outside
  * [0, out_w], an unknown kind, a missing max_rad / gt, a channel stride below 2 (PWC_EINVAL); out_h * out_w or a tile's
- * src_h * src_w >= 2^31, N > 65535 (PWC_ERANGE); a float source off a 4-byte, max_rad off an 8-byte boundary (PWC_EALIGN). */
+ * src_h * src_w > 2^31 - 65537, N > 65535 (PWC_ERANGE); a float source off a 4-byte, max_rad off an 8-byte boundary (PWC_EALIGN). */
 int pwc_flow_vis_tiles_u8(const pwc_vis_tile* tiles, int ntiles, int N, int out_h, int out_w, uint8_t* out, pwc_stream_t stream);
 /* wheel: 55 x 3 bytes, the colour wheel PWC_VIS_FLOW reads (flow_io.color_wheel(); a host copy, no launch). */
 int pwc_flow_vis_wheel_u8(uint8_t* wheel);

@@ -22,8 +22,10 @@ static inline size_t pwc_loss_workspace_floats(int N, int H, int W, int words) {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
     return (size_t)words * N * pwc_loss_parts(H, W);
 }
-// The pixels of an image are indexed with an int, the images with a grid dimension.
-static inline bool pwc_loss_in_range(int N, int H, int W) { return (long)H * W < (1L << 31) && N <= 65535; }
+// The pixels of an image are indexed with an int that the sums loops advance by up to 256 parts * 256 lanes = 65536 past the last
+// pixel before they compare it: H * W + 65536 has to fit.  The images are indexed with a grid dimension.
+#define PWC_LOSS_MAX_PIXELS (2147483647L - 65536L)
+static inline bool pwc_loss_in_range(int N, int H, int W) { return (long)H * W <= PWC_LOSS_MAX_PIXELS && N <= 65535; }
 // The checks the *_sums entry points share, behind their own, in the order they report: the range (PWC_ERANGE), then the
 // workspace (PWC_EINVAL).
 static inline int pwc_loss_sums_check(int N, int H, int W, int words, size_t workspace_floats) {

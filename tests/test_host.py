@@ -387,6 +387,18 @@ def test_correlation_entry_points_report_the_same_codes():
     assert not got, got
 
 
+def test_lrelu_grad_refuses_before_any_launch():
+    """pwc_lrelu_grad_f32: misaligned pointers, strides or channel counts are PWC_EALIGN, a channel stride below C, a null
+    pointer or an empty size PWC_EINVAL -- before any launch."""
+    L = _lib.lib()
+    p, odd = ctypes.c_void_p(4096), ctypes.c_void_p(4100)
+    call = lambda y=p, y_cs=8, dy=p, dy_cs=8, npix=6, C=8: L.pwc_lrelu_grad_f32(y, y_cs, dy, dy_cs, npix, C, 0.1, None)
+    assert call(y=odd) == _EALIGN and call(dy=odd) == _EALIGN and call(C=6, y_cs=6, dy_cs=6) == _EALIGN
+    assert call(y_cs=10) == _EALIGN and call(dy_cs=9) == _EALIGN
+    assert call(y_cs=4) == _EINVAL and call(dy_cs=7) == _EINVAL and call(y=None) == _EINVAL and call(npix=0) == _EINVAL
+    assert call(C=0) == _EINVAL
+
+
 def test_round5_routing_rules_are_host_logic():
     """Which kernel takes which launch is decided by pure host functions of the library (no GPU needed): the small-launch conv
     (up to 1e8 multiply-adds and 4096 output pixels; stride-2 / thin layers beyond), the weights-stationary thin-input conv

@@ -188,6 +188,12 @@ def test_workspace_sizes_and_every_return_code():
                 dict(nws=L.pwc_census_workspace_floats(2, 8, 8, 1) - 1), dict(nws=L.pwc_census_workspace_floats(2, 8, 8, 0))):
         assert grad(**bad) == EINVAL, bad
     assert grad(C=7, cs=7) == EUNSUPPORTED and grad(r=5) == EUNSUPPORTED and grad(N=70000) == ERANGE
+    # an image whose last pixels an int pixel index stepped by up to 65536 cannot pass: the shared range check refuses it
+    for wide in ((1 << 31) - 1, (1 << 31) - 65536):
+        assert sums(H=1, W=wide) == ERANGE and sums(H=1, W=wide, nws=0) == ERANGE
+    assert sums(H=1, W=(1 << 31) - 1 - 65536, nws=0) == EINVAL                       # the largest it takes: on to the workspace
+    assert L.pwc_census_grad_f32(p, 3, p, 3, p, 2, 1.0, None, 1, 1, (1 << 31) - 1, 3, 3, 255.0, 0.81, 0.1, 1e-2, 0.4, p, p, OK_WS, p, 2, 0,
+                                 None) == ERANGE
 
 
 # ------------------------------------------------------------------ refusals before the library call

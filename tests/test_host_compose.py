@@ -190,6 +190,8 @@ def test_library_refuses_before_any_launch():
     assert size(65535, 1, 1) == 8 * 3 * 65535
     assert size(0, 5, 7) == 0 and size(1, 0, 7) == 0 and size(1, 5, -1) == 0
     assert size(65536, 1, 1) == 0 and size(1, 1 << 16, 1 << 15) == 0          # the sizes the entry point refuses
+    assert size(1, 1, (1 << 31) - 1) == 0 and size(1, 1, (1 << 31) - 65536) == 0
+    assert size(1, 1, (1 << 31) - 1 - 65536) == 8 * (2 * ((1 << 31) - 1 - 65536) + 1)      # the largest row it takes
 
     def fwd(ab=p, ab_cs=2, bc=p, bc_cs=2, N=2, H=5, W=7, out=p, out_cs=2, valid=p):
         return L.pwc_flow_compose_f32(ab, ab_cs, bc, bc_cs, None, None, N, H, W, out, out_cs, valid, None)
@@ -204,6 +206,8 @@ def test_library_refuses_before_any_launch():
             assert fn(**bad) == EINVAL, (fn.__name__, bad)
         assert fn(N=65536) == ERANGE
         assert fn(N=1, H=1 << 16, W=1 << 15) == ERANGE
+        # a row whose last pixels the int pixel index of the validity count cannot step over (it advances by up to 65536 past them)
+        assert fn(N=1, H=1, W=(1 << 31) - 1) == ERANGE and fn(N=1, H=1, W=(1 << 31) - 65536) == ERANGE
         assert fn(ab=odd) == EALIGN and fn(bc=odd) == EALIGN
     for bad in (dict(out=None), dict(valid=None), dict(out_cs=1)):
         assert fwd(**bad) == EINVAL, bad

@@ -164,7 +164,14 @@ def test_library_refuses_before_any_launch():
         assert fn(N=65536) == ERANGE
         assert fn(N=1, h=1 << 16, w=1 << 15, H=1 << 16, W=1 << 15, y0=0, x0=0) == ERANGE
         assert fn(N=1, H=1 << 16, W=1 << 15) == ERANGE                             # the teacher alone is too large
+        # a row whose last pixels the sums loop's int pixel index cannot step over (it advances by up to 65536 past them)
+        for wide in ((1 << 31) - 1, (1 << 31) - 65536):
+            assert fn(N=1, h=1, w=wide, H=1, W=wide, y0=0, x0=0) == ERANGE
+            assert fn(N=1, h=1, w=7, H=1, W=wide, y0=0, x0=0) == ERANGE
         assert fn(student=odd) == EALIGN and fn(teacher=odd) == EALIGN
+    most = (1 << 31) - 1 - 65536                                                   # the largest it can: on to the workspace check
+    assert sums(N=1, h=1, w=most, H=1, W=most, y0=0, x0=0, ws_bytes=0) == EINVAL
+    assert L.pwc_flow_distill_workspace_bytes(1, 1, (1 << 31) - 1) == 0 and L.pwc_flow_distill_workspace_bytes(1, 1, most) == 256 * 12
     for bad in (dict(out=None), dict(counts=None), dict(ws=None), dict(ws_bytes=2 * 12 - 1)):
         assert sums(**bad) == EINVAL, bad
     assert sums(ws=half) == EALIGN                                                 # off an 8-byte boundary

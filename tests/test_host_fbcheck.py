@@ -145,6 +145,9 @@ def test_workspace_sizes_and_argument_checks_need_no_gpu():
     assert call(N=65536) == erange and call(H=1 << 16, W=1 << 15) == erange
     assert call(N=65536, nws=0) == erange               # the range is reported before the workspace
     assert call(N=0, H=1 << 16, W=1 << 15) == einval    # ... and the sizes before the range
+    # an image whose last pixels the int pixel index cannot step over (it advances by up to 65536 past them)
+    assert call(H=1, W=(1 << 31) - 1) == erange and call(H=1, W=(1 << 31) - 65536, nws=0) == erange
+    assert call(H=1, W=(1 << 31) - 1 - 65536, nws=0) == einval      # the largest it can: on to the workspace check
 
 
 # ------------------------------------------------------------------ refusals before the library call

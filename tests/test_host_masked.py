@@ -110,6 +110,15 @@ def test_masked_entry_points_refuse_bad_arguments_before_launching():
     assert met(wsf=L.pwc_flow_metrics_workspace_floats(2, 4, 8) - 1) == _EINVAL
     assert sums(H=65536, W=65536) == _ERANGE and sums(N=65536) == _ERANGE
     assert met(H=65536, W=65536) == _ERANGE and met(N=65536) == _ERANGE
+    # an image whose last pixels the int pixel index of the sums loops cannot step over (it advances by up to 65536 past them):
+    # refused; the largest it can is let through to the workspace check
+    def plain(N=2, H=4, W=8, wsf=1 << 16):
+        return L.pwc_flow_norm_sums_f32(_AL, 2, _AL, 2, N, H, W, 16, 32, 20.0, 2, _AL, wsf, _AL, None)
+
+    for f in (sums, met, plain):
+        assert f(H=1, W=(1 << 31) - 1) == _ERANGE and f(H=1, W=(1 << 31) - 65536) == _ERANGE
+        assert f(H=1, W=(1 << 31) - 1, wsf=0) == _ERANGE
+        assert f(H=1, W=(1 << 31) - 1 - 65536, wsf=0) == _EINVAL
 
 
 def test_masked_workspace_sizes():

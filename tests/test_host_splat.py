@@ -191,6 +191,10 @@ def test_workspace_size_and_every_return_code():
         assert grad(**bad) == EINVAL, bad
     assert grad(C=70, x_cs=70) == EUNSUPPORTED and grad(N=70000) == ERANGE and grad(normalize=1, ws=odd, nws=BIG) == EALIGN
     assert grad(N=70000, dx=None, dw=None, df=None) == ERANGE and grad(g_cs=2, normalize=1) == EINVAL
+    # an image whose last pixels an int pixel index stepped by up to 65536 cannot pass: the shared range check refuses it
+    for wide in ((1 << 31) - 1, (1 << 31) - 65536):
+        assert fwd(N=1, H=1, W=wide) == ERANGE and grad(N=1, H=1, W=wide) == ERANGE
+    assert fwd(N=1, H=1, W=(1 << 31) - 1 - 65536, nws=0) == EINVAL                   # the largest it takes: on to the workspace
 
 
 # ------------------------------------------------------------------ refusals before the library call

@@ -176,6 +176,10 @@ def test_workspace_sizes_and_argument_checks_need_no_gpu():
         assert f(N=0, H=1 << 16, W=1 << 15) == einval
     assert s2(nws=1) == einval and s2(ws=None) == einval and s2(out=None) == einval
     assert s2(N=65536, nws=0) == erange                     # the range is reported before the workspace
+    # an image whose last pixels the sums loop's int pixel index cannot step over (it advances by up to 65536 past them)
+    assert s2(H=1, W=(1 << 31) - 1) == erange and s2(H=1, W=(1 << 31) - 65536, nws=0) == erange
+    assert g2(H=1, W=(1 << 31) - 1) == erange
+    assert s2(H=1, W=(1 << 31) - 1 - 65536, nws=0) == einval        # the largest it can: on to the workspace check
     assert g2(ds=None) == einval and g2(df=None) == einval and g2(dcs=1) == einval
 
     # consistency term
@@ -202,6 +206,8 @@ def test_workspace_sizes_and_argument_checks_need_no_gpu():
         assert f(N=65536, nws=0) == erange                  # the range is reported before the workspace
         assert f(N=0, H=1 << 16, W=1 << 15) == einval       # ... and the sizes before the range
         assert f(ws=None) == einval and f(nws=3) == einval
+        assert f(H=1, W=(1 << 31) - 1) == erange and f(H=1, W=(1 << 31) - 65536, nws=0) == erange       # (as s2 above)
+        assert f(H=1, W=(1 << 31) - 1 - 65536, nws=0) == einval
     for key in ("sa", "ca", "sb", "cb"):
         assert cs(**{key: None}) == einval
     for key in ("da", "db", "oa", "ob"):

@@ -135,6 +135,11 @@ def test_header_declares_the_entries_and_they_are_bound():
 
     assert smooth(flow=None) == -1 and smooth(alpha=-1.0) == -1 and smooth(eps=-1.0) == -1 and smooth(q=2.0) == -1
     assert smooth(image_cs=2) == -1 and smooth(nws=1) == -1 and smooth(C=5, image_cs=5) == -4 and smooth(N=70000) == -3
+    # an image whose last pixels the int pixel index of the sums loops cannot step over (it advances by up to 65536 past them):
+    # refused; the largest it can is let through to the workspace check
+    for f in (sums, smooth):
+        assert f(H=1, W=(1 << 31) - 1) == -3 and f(H=1, W=(1 << 31) - 65536) == -3 and f(H=1, W=(1 << 31) - 1, nws=0) == -3
+        assert f(H=1, W=(1 << 31) - 1 - 65536, nws=0) == -1
 
     def sgrad(dsums=p, dflow=p, dflow_cs=2, alpha=10.0):
         return L.pwc_flow_smoothness_grad_f32(p, 2, None, 0, 0, alpha, 1e-3, 0.5, 2, 8, 8, dsums, dflow, dflow_cs, 0, None)

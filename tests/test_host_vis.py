@@ -275,6 +275,10 @@ def test_library_refuses_before_any_launch():
         assert tiles([tile(**bad)]) == EINVAL, bad
     assert tiles([tile()], N=65536) == ERANGE and tiles([tile()], N=1, out_h=1 << 16, out_w=1 << 15) == ERANGE
     assert tiles([tile(src_h=1 << 16, src_w=1 << 15)]) == ERANGE
+    # an image whose last pixels an int pixel index stepped by up to 65536 cannot pass: the shared range check refuses it
+    for wide in ((1 << 31) - 1, (1 << 31) - 65536):
+        assert rad(N=1, H=1, W=wide) == ERANGE and tiles([tile()], N=1, out_h=1, out_w=wide) == ERANGE
+        assert tiles([tile(src_h=1, src_w=wide)]) == ERANGE
     assert tiles([tile(src=4098)]) == EALIGN and tiles([tile(max_rad=4100)]) == EALIGN and tiles([tile(**dict(err, gt=4098))]) == EALIGN
     assert tiles([tile(kind=_lib.VIS_FRAME_F32, src=4098, max_rad=None)]) == EALIGN
     assert tiles([tile(src=None), tile()], N=65536) == EINVAL                      # the order of the header
