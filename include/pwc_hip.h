@@ -1118,6 +1118,52 @@ int pwc_flow_vis_tiles_u8(const pwc_vis_tile* tiles, int ntiles, int N, int out_
 /* wheel: 55 x 3 bytes, the colour wheel PWC_VIS_FLOW reads (flow_io.color_wheel(); a host copy, no launch). */
 int pwc_flow_vis_wheel_u8(uint8_t* wheel);
 
+/* ==== point tracking: query points carried through the consecutive flows of a sequence ====
+ * (pwc_track.hip; semantics and launch plan in DESIGN.md 17.)  flows_fw: T x H x W records of fw_cs >= 2 floats, 2 used, the
+ * flows t -> t + 1 of T + 1 frames of one size, in pixels; flows_bw: the flows t + 1 -> t in the same layout at bw_cs, or NULL;
+ * valids_fw, valids_bw: T x H x W bytes or NULL (every pixel; valids_bw is not read without flows_bw).  points: P x 2 floats
+ * (x, y), the flow's channel order, in frame pixels with the pixel centre at the integer; start: P int32 or NULL (all 0);
+ * status_in: P bytes or NULL.  Outputs, TIME-MAJOR: tracks (T + 1) x P x 2 floats, status (T + 1) x P bytes, every element
+ * written; slice t is contiguous and the last slice of one call is the state that feeds the next.
+ *
+ * ONE STEP carries a point in state (x, y) float32 with status s across the step flow F, checked against G where given; every
+ * operation is an IEEE double + - x, a floor or a comparison in exactly this order, no fused multiply-add:
+ *   s is terminal -- LEFT, UNKNOWN, OCCLUDED where stop_on_occlusion != 0 (and any byte that is no status code): position and
+ *   status repeat.  Otherwise qx = (double)x, qy = (double)y and
+ *   A  not (0 <= qx <= W - 1 and 0 <= qy <= H - 1) (a NaN fails)                            -> LEFT, position kept
+ *      x0 = floor(qx), x1 = min(x0 + 1, W - 1), wx = qx - x0, likewise in y (the sample of the forward-backward check above)
+ *   B  one of the corners (y0,x0) (y0,x1) (y1,x0) (y1,x1) is zero in F's mask, or holds a component that is not finite or
+ *      exceeds 1e9 in magnitude (the .flo sentinel rule) -- all four whatever their weight  -> UNKNOWN, position kept
+ *      S_k = ((1 - wy) ((1 - wx) F00_k + wx F01_k)) + (wy ((1 - wx) F10_k + wx F11_k)), k = 0, 1;  rx = qx + S_0, ry = qy + S_1
+ *   C  not (0 <= rx <= W - 1 and 0 <= ry <= H - 1)                                          -> LEFT, position kept
+ *   D  (G given) b = the sample of G at (rx, ry) by the same rule; a bad corner             -> UNKNOWN, position kept
+ *      d_k = S_k + b_k;  bound = a1 ((S_0 S_0 + S_1 S_1) + (b_0 b_0 + b_1 b_1)) + a2, a1 = (double)alpha1, a2 = (double)alpha2;
+ *      margin = bound - (d_0 d_0 + d_1 d_1);  not (margin >= 0)                             -> OCCLUDED, position (float)rx, (float)ry
+ *      else VISIBLE, position ((float)rx, (float)ry): rounded once.
+ * Selection is by branch: a point that fails A reads no flow, one that fails B no check flow, the flow of a masked corner is
+ * not loaded.  With stop_on_occlusion == 0 an OCCLUDED point keeps stepping from where it is and may become VISIBLE again.
+ *
+ * A TRACK.  Point p with s0 = start[p], 0 <= s0 <= T, is VISIBLE at slice s0 at points[p] (LEFT where the query fails A) and
+ * steps up to slice T with F = flows_fw[t], G = flows_bw[t] and their masks.  direction PWC_TRACK_BOTH (needs flows_bw): it
+ * also steps from s0 down to slice 0, the step t -> t - 1 with F = flows_bw[t - 1], G = flows_fw[t - 1] and the masks swapped
+ * likewise; PWC_TRACK_FORWARD: the slices below s0 are UNSEEN at the query position.  start[p] outside 0 .. T: every slice is
+ * UNSEEN at the query position.  Where status_in is given and status_in[p] != UNSEEN, start[p] is ignored: the point enters
+ * slice 0 in that state at points[p] (the streaming form).  One call over T flows equals, bit for bit, a call over the first
+ * T1 followed by a call over the rest that is fed slice T1 (PWC_TRACK_FORWARD).
+ *
+ * One launch: a lane per point, 256-lane workgroups, at most 4096 of them (grid-stride beyond); no workspace, no atomics.  A
+ * record is one 8-byte access where every float pointer is on an 8-byte boundary and both channel strides are even, else two
+ * 4-byte ones; the bits are the same.  Checks, before the launch, in this order: a null flows_fw, points, tracks or status, T,
+ * H, W, P < 1, a channel stride below 2, an unknown direction, PWC_TRACK_BOTH without flows_bw, with flows_bw an alpha that is
+ * negative or NaN (PWC_EINVAL); H or W > 2^24 (beyond it rounding rx <= W - 1 to float32 could leave the frame), H * W >= 2^31,
+ * T > 65535 (PWC_ERANGE); a float pointer or start off a 4-byte boundary (PWC_EALIGN). */
+enum { PWC_TRACK_UNSEEN = 0, PWC_TRACK_VISIBLE = 1, PWC_TRACK_LEFT = 2, PWC_TRACK_OCCLUDED = 3, PWC_TRACK_UNKNOWN = 4 };
+enum { PWC_TRACK_FORWARD = 0, PWC_TRACK_BOTH = 1 };
+int pwc_track_points_f32(const float* flows_fw, int fw_cs, const float* flows_bw, int bw_cs, const uint8_t* valids_fw,
+                         const uint8_t* valids_bw, int T, int H, int W, const float* points, const int32_t* start,
+                         const uint8_t* status_in, int P, int direction, float alpha1, float alpha2, int stop_on_occlusion,
+                         float* tracks, uint8_t* status, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

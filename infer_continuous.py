@@ -18,6 +18,11 @@ boundaries; after the refit where --fit is not crop).  A pixel whose chain leave
 .flo sentinel (flow_io.flow_valid).
 --vis gpu builds every batch's montages in one launch on the GPU (pwcnet_amd.pyramid_montage): the pyramid levels are not copied
 to the host, only the uint8 pictures and the full-resolution flow are; the .flo files do not depend on it.
+--track SPEC also writes <out>/tracks.npy (frames, P, 2) float32 and <out>/tracks_status.npy (frames, P) uint8: where the query
+points of SPEC are in every frame and what is known about them there (pwcnet_amd.track_points, across batch boundaries; after
+the refit where --fit is not crop; positions (x, y) in the pixels of the frames the flow is computed on).  SPEC is grid:S, the
+centres of S x S cells given in frame 0, or a text file of `frame x y` lines.  --track_fb also runs every batch's pairs reversed
+and marks the points that fail the forward-backward check OCCLUDED.  The frames must all have one size.
 """
 import argparse
 import os
@@ -62,7 +67,49 @@ def build_parser():
     ap.add_argument("--vis", choices=("host", "gpu"), default="host",
                     help="build the montages with numpy on the copied-back pyramid, or on the GPU (pwcnet_amd.pyramid_montage: only "
                          "uint8 pictures and the final flow cross to the host) [host]")
+    ap.add_argument("--track", type=str, default=None, metavar="SPEC",
+                    help="also write tracks.npy / tracks_status.npy: the query points of SPEC -- grid:S or a text file of "
+                         "`frame x y` lines -- followed through the sequence on the GPU [off]")
+    ap.add_argument("--track_fb", action="store_true",
+                    help="--track: also run the reversed pairs and mark points that fail the forward-backward check OCCLUDED")
     return ap
+
+
+def parse_track_spec(spec, nframes, H, W):
+    """(points (P,2) float32 (x, y), start (P,) int32) of --track SPEC for a sequence of nframes H x W frames: `grid:S`, the
+    centres of S x S cells (pwcnet_amd.grid_points) given in frame 0, or the path of a text file with one `frame x y` per line
+    (blank lines and #-comments are skipped)."""
+    if spec.startswith("grid:"):
+        try:
+            stride = int(spec[5:])
+        except ValueError:
+            stride = 0
+        if stride < 1:
+            raise ValueError(f"--track: expected grid:S with a positive integer S, got {spec!r}")
+        from pwcnet_amd.track import grid_points
+        points = grid_points(H, W, stride).numpy()
+        return points, np.zeros(points.shape[0], np.int32)
+    if not os.path.isfile(spec):
+        raise ValueError(f"--track: expected grid:S or the path of a text file of `frame x y` lines, got {spec!r}")
+    points, start = [], []
+    with open(spec) as f:
+        for no, line in enumerate(f, 1):
+            fields = line.split("#", 1)[0].split()
+            if not fields:
+                continue
+            try:
+                frame, x, y = int(fields[0]), float(fields[1]), float(fields[2])
+                if len(fields) != 3:
+                    raise ValueError
+            except (ValueError, IndexError):
+                raise ValueError(f"--track: {spec}:{no}: expected `frame x y`, got {line.strip()!r}") from None
+            if not 0 <= frame < nframes:
+                raise ValueError(f"--track: {spec}:{no}: frame {frame} is outside the sequence of {nframes} frames")
+            points.append((x, y))
+            start.append(frame)
+    if not points:
+        raise ValueError(f"--track: {spec} holds no query point")
+    return np.asarray(points, np.float32).reshape(-1, 2), np.asarray(start, np.int32)
 
 
 def out_stem(path):
@@ -107,6 +154,36 @@ class Chainer:
             del self.held[i]
 
 
+class Tracker:
+    """--track: takes the full-resolution flows i -> i + 1 (and, --track_fb, i + 1 -> i) as they come, batch after batch, steps
+    the query points through them (pwcnet_amd.track_points) and keeps only the (P,2) positions and (P,) states of the last frame
+    seen on the GPU; save() writes the (frames, P, 2) tracks and (frames, P) states."""
+
+    def __init__(self, points, start, nframes, out):
+        self.start = torch.from_numpy(np.asarray(start, np.int32)).cuda()
+        self.points = torch.from_numpy(np.asarray(points, np.float32)).cuda()
+        self.state = torch.zeros(self.points.shape[0], dtype=torch.uint8, device="cuda")       # UNSEEN: not started yet
+        self.tracks = np.zeros((nframes, self.points.shape[0], 2), np.float32)
+        self.status = np.zeros((nframes, self.points.shape[0]), np.uint8)
+        self.out = out
+
+    def add(self, first, flows_fw, flows_bw=None):
+        """flows_fw: (n,H,W,2) on the GPU, the flows of the pairs first, first + 1, ...; flows_bw: the flows of the reversed
+        pairs.  A point not started yet starts at start - first (beyond this batch: not in this call)."""
+        import pwcnet_amd
+        n = flows_fw.shape[0]
+        tracks, status = pwcnet_amd.track_points(flows_fw, self.points, flows_bw=flows_bw, start=(self.start - first).clamp_(min=0),
+                                                 status=self.state)
+        self.points, self.state = tracks[n], status[n]
+        self.tracks[first:first + n + 1] = tracks.cpu().numpy()
+        self.status[first:first + n + 1] = status.cpu().numpy()
+
+    def save(self):
+        os.makedirs(self.out, exist_ok=True)
+        np.save(os.path.join(self.out, "tracks.npy"), self.tracks)
+        np.save(os.path.join(self.out, "tracks_status.npy"), self.status)
+
+
 def main():
     ap = build_parser()
     args = ap.parse_args()
@@ -117,6 +194,9 @@ def main():
         raise ValueError("# of input images must be >= 2")
     if args.chain < 0 or args.chain >= len(paths):
         ap.error(f"--chain must be at least 0 and below the number of frames ({len(paths)}), got {args.chain}")
+
+    if args.track_fb and args.track is None:
+        ap.error("--track_fb needs --track SPEC")
 
     from PIL import Image
     import pwcnet_amd
@@ -150,7 +230,14 @@ def main():
         i = j
     num_levels = model.nets[0].num_levels
     chainer = Chainer(args.chain, frames, paths, args.out) if args.chain > 0 else None
+    tracker = None
+    if args.track is not None:
+        if any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("--track needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
+        tracker = Tracker(*parse_track_spec(args.track, len(frames), *frames[0].shape[:2]), len(frames), args.out)
     window = 2 * max(1, args.pipeline)               # batches submitted before the first one is read back
+    if args.track_fb:
+        window = max(1, args.pipeline)               # (two forwards per batch)
     for w0 in range(0, len(jobs), window):
         tickets = []
         for i, j in jobs[w0:w0 + window]:
@@ -160,15 +247,23 @@ def main():
             else:                                    # uint8 upload; / 255 and the fit in one launch on the caller's stream
                 shown = torch.from_numpy(np.stack(frames[i:j + 1])).cuda()
                 seq, info = pwcnet_amd.fit_frames(shown, args.fit)
-            tickets.append((i, j, info, shown if args.vis == "gpu" else None,
-                            model.submit(seq[:-1].contiguous(), seq[1:].contiguous())))
+            first, second = seq[:-1].contiguous(), seq[1:].contiguous()
+            tickets.append((i, j, info, shown if args.vis == "gpu" else None, model.submit(first, second),
+                            model.submit(second, first) if args.track_fb else None))
         model.synchronize()
-        for i, j, info, shown, ticket in tickets:
+        for i, j, info, shown, ticket, reverse in tickets:
             flow_final, flows = ticket.result()
             if info is not None:
                 flow_final = pwcnet_amd.refit_flow(flow_final, info)
             if chainer is not None:
                 chainer.add(i, flow_final.clone())   # (the replica writes its result buffer again at its next forward)
+            if tracker is not None:
+                flow_back = None
+                if reverse is not None:
+                    flow_back = reverse.result()[0]
+                    if info is not None:
+                        flow_back = pwcnet_amd.refit_flow(flow_back, info)
+                tracker.add(i, flow_final, flow_back)
             flow_final = flow_final.cpu().numpy()
             scales = [20.0 / 2 ** (num_levels - l) for l in range(len(flows))]
             if args.vis == "gpu":                    # one launch per batch; the pyramid stays on the GPU
@@ -184,6 +279,8 @@ def main():
                     montage = pyramid_montage(frames[i + k], [f[k] * s for f, s in zip(flows, scales)])
                 Image.fromarray(montage).save(os.path.join(args.out, dname, fname + ".png"))
                 flow_io.write_flo(os.path.join(args.out, dname, fname + ".flo"), flow_final[k])
+    if tracker is not None:
+        tracker.save()
     print("Figure saved")
 
 

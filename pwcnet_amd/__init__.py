@@ -11,6 +11,8 @@ from .unsup import (census_grad, census_loss, census_sums, fb_consistency_grad, 
                     photometric_sums, smoothness_loss, smoothness_sums, ssim_grad, ssim_loss, ssim_sums)
 from .splat import forward_splat, range_map, range_valid, splat_grad  # noqa: F401
 from .compose import chain_flows, compose_flows, compose_grad  # noqa: F401
+from . import track  # noqa: F401
+from .track import grid_points, track_points  # noqa: F401
 from . import vis  # noqa: F401
 from .vis import flow_error_color, flow_max_radius, flow_to_color, pyramid_montage  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
@@ -26,4 +28,5 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "fb_consistency_sums", "fb_consistency_loss", "fb_consistency_grad", "forward_splat", "splat_grad", "range_map", "range_valid", "FitInfo", "fit_frames", "fit_info",
            "refit_flow", "flow_any_size", "draw_params", "crop_params", "augment_pairs", "frame_pyramid", "mask_pyramid", "level_flow_scale",
            "UnsupObjective", "FeatureNormLayer", "flow_distill_sums", "flow_distill_loss", "flow_distill_grad",
-           "compose_flows", "compose_grad", "chain_flows", "vis", "flow_max_radius", "flow_to_color", "flow_error_color", "pyramid_montage"]
+           "compose_flows", "compose_grad", "chain_flows", "vis", "flow_max_radius", "flow_to_color", "flow_error_color", "pyramid_montage",
+           "track", "track_points", "grid_points"]

@@ -22,7 +22,7 @@ HARNESS_SIGNATURES_NAMES = ("pwc_debug_cost_volume_blk_rows", "pwc_debug_conv3x3
                             "pwc_debug_h2_reserve_cus", "pwc_debug_conv3x3_s2_tile")
 SOURCES = ["conv3x3_mfma.hip", "conv3x3_wino.hip", "conv3x3_direct.hip", "cost_volume.hip", "pwc_ops.hip",
            "pwc_backward.hip", "conv3x3_wgrad.hip", "conv3x3_h2.hip", "conv3x3_c16pair.hip", "conv3x3_sk.hip", "conv3x3_s2.hip", "conv3x3_t32.hip", "conv3x3_w32.hip",
-           "pwc_flow_loss.hip", "pwc_unsup.hip", "pwc_census.hip", "pwc_ssim.hip", "pwc_fbcheck.hip", "pwc_fit.hip", "pwc_augment.hip", "pwc_splat.hip", "pwc_pyramid.hip", "pwc_featnorm.hip", "pwc_distill.hip", "pwc_compose.hip", "pwc_flowvis.hip"]
+           "pwc_flow_loss.hip", "pwc_unsup.hip", "pwc_census.hip", "pwc_ssim.hip", "pwc_fbcheck.hip", "pwc_fit.hip", "pwc_augment.hip", "pwc_splat.hip", "pwc_pyramid.hip", "pwc_featnorm.hip", "pwc_distill.hip", "pwc_compose.hip", "pwc_flowvis.hip", "pwc_track.hip"]
 HEADERS = ["pwc_common.h", "conv_fp32_common.h", "cost_volume_common.h", "loss_common.h", "cost_volume_roll.hip", "cost_volume_mfma.hip", "cost_volume_h2.hip", "cost_volume_blk.hip", "conv3x3_wino4.hip", os.path.join("..", "..", "include", "pwc_hip.h")]
 
 _vp, _i, _f, _l, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long, ctypes.c_size_t, ctypes.c_double
@@ -167,6 +167,7 @@ SIGNATURES = {
     "pwc_flow_max_radius_f64": (_i, [_vp, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
     "pwc_flow_vis_tiles_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "pwc_flow_vis_wheel_u8": (_i, [_vp]),
+    "pwc_track_points_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
 }
 
 if HARNESS:
@@ -179,6 +180,9 @@ STATUS_STREAMK_TIMEOUT = 2
 # tiles of pwc_flow_vis_tiles_u8 (include/pwc_hip.h)
 VIS_FLOW, VIS_FRAME_U8, VIS_FRAME_F32, VIS_ERROR = 0, 1, 2, 3
 VIS_MAX_TILES = 8
+# status codes and directions of pwc_track_points_f32 (include/pwc_hip.h)
+TRACK_UNSEEN, TRACK_VISIBLE, TRACK_LEFT, TRACK_OCCLUDED, TRACK_UNKNOWN = 0, 1, 2, 3, 4
+TRACK_FORWARD, TRACK_BOTH = 0, 1
 
 
 class VisTile(ctypes.Structure):
