@@ -1164,6 +1164,55 @@ int pwc_track_points_f32(const float* flows_fw, int fw_cs, const float* flows_bw
                          const uint8_t* status_in, int P, int direction, float alpha1, float alpha2, int stop_on_occlusion,
                          float* tracks, uint8_t* status, pwc_stream_t stream);
 
+/* ==== frame interpolation: the frames between two frames, splatted along the two flows between them ====
+ * (pwc_interp.hip; semantics, budget and launch plan in DESIGN.md 19.)  frames_0, frames_1: N x H x W x 3, both PWC_INTERP_U8
+ * (records of 3 bytes, cs 3; a byte v is read as (double)v / 255.0) or both PWC_INTERP_F32 (records of cs >= 3 floats, 3 used,
+ * widened; values in [0, 1] are what the budget below assumes).  flows_fw (0 -> 1), flows_bw (1 -> 0): N x H x W records of
+ * fw_cs, bw_cs >= 2 floats, 2 used, in pixels.  valid_fw, valid_bw: N x H x W bytes or NULL (every pixel); weights_fw, weights_bw:
+ * N x H x W floats or NULL, the weight of each SOURCE pixel.  times: M doubles on the HOST, 1 <= M <= 16, each in [0, 1], copied
+ * into the kernels' arguments.  Outputs: frames_t N x M x H x W x 3 in the frames' dtype, dense; source N x M x H x W bytes; every
+ * element written.  Every operation is an IEEE double operation in the order given here, no fused multiply-add; exp is the only
+ * one whose result may differ from a restatement's (tests/interp_ref.py).
+ *
+ * SCATTER, per direction k (0: frame 0 along flows_fw, 1: frame 1 along flows_bw) and source pixel p = (n, y, x) with flow f:
+ *   skipped where its mask is zero, or a component of f is not finite or exceeds 1e9 in magnitude (the .flo sentinel rule; a
+ *   masked pixel's flow is not loaded).  Its weight w, formed ONCE:
+ *     weights_k given: w = weights_k[p]; negative, NaN or Inf: skipped; >= 2^26: the poison word is raised, skipped.
+ *     else q = (x + f_0, y + f_1); in frame iff 0 <= qx <= W - 1 and 0 <= qy <= H - 1; x0 = floor(qx), x1 = min(x0 + 1, W - 1),
+ *       wx1 = qx - x0, wx0 = 1 - wx1, likewise in y; o_c = wy0 (wx0 O00_c + wx1 O01_c) + wy1 (wx0 O10_c + wx1 O11_c) of the OTHER
+ *       frame (the forward-backward check's sample); e = ((|own_0 - o_0| + |own_1 - o_1|) + |own_2 - o_2|) / 3;
+ *       w = exp(-min((double)alpha e, 10)); q out of frame: w = exp(-10).
+ *   For each time t_m: s = t_m (k = 0) or 1 - t_m (k = 1); (px, py) = (x + s f_0, y + s f_1); contributes iff px > -1, px < W,
+ *   py > -1, py < H (a NaN fails); x0 = floor(px), wx = px - x0, likewise y; each corner (y0 + dy, x0 + dx) inside the frame, with
+ *   b = (dx ? wx : 1 - wx) (dy ? wy : 1 - wy), receives by 64-bit integer atomics llrint(v 2^36), v = (b w) colour_c (c = 0, 1, 2),
+ *   b w, b.  A contribution that rounds to no step is not sent; one that is not finite or reaches 2^26 (float frames far out of
+ *   [0, 1]) raises the poison word.
+ * RESOLVE, per output pixel (n, m, y, x): per direction range_k = (the b sum) 2^-36, covered_k iff range_k >= (double)min_range
+ *   and den_k > 0 (the b w sum), c_k = num_k / den_k (the integers as doubles).  source = covered_0 + 2 covered_1.  The value is
+ *   (1 - t) c_0 + t c_1 (source 3), c_0 (1), c_1 (2), (1 - t) frames_0[n, y, x] + t frames_1[n, y, x] (0, a hole).  float frames:
+ *   rounded once; bytes: rint(255 v), ties to even, clamped to [0, 255], 0 for a NaN.  With the poison word set every element is
+ *   NaN (floats) or 0 (bytes) and every source code 0; a cell whose sum reached 2^61 makes its own pixel so.
+ *
+ * workspace: pwc_interp_workspace_bytes(N, M, H, W) = 8 (N M H W 10 + 1) bytes, 8-byte aligned, 0 for sizes the call refuses:
+ * planes [n][m][k][5][H W] and the poison word.  A time's planes meet no other time's, an image's no other image's: a call cut
+ * along N or along M gives the whole call's bits, and two calls give the same bits.  Three steps on `stream`: a memset, one
+ * scatter launch (grid (min(ceil(N H W / 256), 4096), 2) workgroups of 256 lanes, grid-stride beyond the cap), one resolve
+ * launch (a lane per four output pixels, min(ceil(N M H W / 1024), 4096) workgroups, grid-stride beyond); bytes leave as three
+ * dwords per lane where frames_t is on a 4-byte boundary, floats as three 16-byte stores where it is on a 16-byte one, else one by
+ * one -- the values are the same.  No host synchronisation, no process-wide state.  Checks, before the memset, in this order: a
+ * null frames, flows, times, workspace or output pointer, N, H, W < 1, M outside 1 .. 16, dtypes that differ or are unknown, a
+ * time outside [0, 1] or NaN, a negative or NaN alpha or min_range, a flow stride below 2, a float frame stride below 3, a byte
+ * frame stride other than 3 (PWC_EINVAL); H * W >= 2^31 or a workspace size beyond size_t (PWC_ERANGE); a float pointer off a
+ * 4-byte or the workspace off an 8-byte boundary (PWC_EALIGN); a workspace that is too small (PWC_EINVAL). */
+enum { PWC_INTERP_U8 = 0, PWC_INTERP_F32 = 1 };
+#define PWC_INTERP_MAX_TIMES 16
+size_t pwc_interp_workspace_bytes(int N, int M, int H, int W);
+int pwc_interp_frames(const void* frames_0, int dtype_0, int cs_0, const void* frames_1, int dtype_1, int cs_1,
+                      const float* flows_fw, int fw_cs, const float* flows_bw, int bw_cs, const uint8_t* valid_fw,
+                      const uint8_t* valid_bw, const float* weights_fw, const float* weights_bw, int N, int H, int W,
+                      const double* times, int M, float alpha, float min_range, void* workspace, size_t workspace_bytes,
+                      void* frames_t, uint8_t* source, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,10 @@ points of SPEC are in every frame and what is known about them there (pwcnet_amd
 the refit where --fit is not crop; positions (x, y) in the pixels of the frames the flow is computed on).  SPEC is grid:S, the
 centres of S x S cells given in frame 0, or a text file of `frame x y` lines.  --track_fb also runs every batch's pairs reversed
 and marks the points that fail the forward-backward check OCCLUDED.  The frames must all have one size.
+--interp M also writes, for every consecutive pair, the M frames in between at t = k / (M + 1) as
+<out>/<dname>/<fname>_t<k>of<M+1>.png (pwcnet_amd.interpolate_frames: both frames splatted along the two flows between them, one
+call per batch; the reversed pairs are run as --track_fb runs them; after the refit where --fit is not crop).  Only the uint8
+pictures come back to the host.  --interp_alpha A is the weight of the photometric match (exp(-A e)) [20].
 """
 import argparse
 import os
@@ -72,7 +76,19 @@ def build_parser():
                          "`frame x y` lines -- followed through the sequence on the GPU [off]")
     ap.add_argument("--track_fb", action="store_true",
                     help="--track: also run the reversed pairs and mark points that fail the forward-backward check OCCLUDED")
+    ap.add_argument("--interp", type=_positive_int, default=0, metavar="M",
+                    help="also write the M frames between every consecutive pair, <fname>_t<k>of<M+1>.png at t = k / (M + 1), "
+                         "interpolated on the GPU from the two flows between them (the reversed pairs are run too) [off]")
+    ap.add_argument("--interp_alpha", type=float, default=20.0, metavar="A",
+                    help="--interp: the weight of a source pixel is exp(-min(A * e, 10)), e its match's mean colour error [20]")
     return ap
+
+
+def _positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"expected an integer >= 1, got {text!r}")
+    return value
 
 
 def parse_track_spec(spec, nframes, H, W):
@@ -197,6 +213,11 @@ def main():
 
     if args.track_fb and args.track is None:
         ap.error("--track_fb needs --track SPEC")
+    if args.interp > 16:
+        ap.error(f"--interp must be at most 16 (pwcnet_amd.interp.MAX_TIMES), got {args.interp}")
+    if not args.interp_alpha >= 0.0:
+        ap.error(f"--interp_alpha must be non-negative, got {args.interp_alpha}")
+    both_ways = args.track_fb or args.interp > 0      # the reversed pairs are run too: one ticket serves both flags
 
     from PIL import Image
     import pwcnet_amd
@@ -236,34 +257,47 @@ def main():
             raise ValueError("--track needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
         tracker = Tracker(*parse_track_spec(args.track, len(frames), *frames[0].shape[:2]), len(frames), args.out)
     window = 2 * max(1, args.pipeline)               # batches submitted before the first one is read back
-    if args.track_fb:
+    if both_ways:
         window = max(1, args.pipeline)               # (two forwards per batch)
     for w0 in range(0, len(jobs), window):
         tickets = []
         for i, j in jobs[w0:w0 + window]:
+            pictures = None                          # --interp: the uint8 frames at the flows' size
             if args.fit == "crop":
                 seq = torch.from_numpy(np.stack(frames[i:j + 1]).astype(np.float32) / 255.0).cuda()
                 info, shown = None, seq              # (a float32 frame made as u8 / 255 gives back u8)
+                if args.interp > 0:
+                    pictures = torch.from_numpy(np.stack(frames[i:j + 1])).cuda()
             else:                                    # uint8 upload; / 255 and the fit in one launch on the caller's stream
                 shown = torch.from_numpy(np.stack(frames[i:j + 1])).cuda()
                 seq, info = pwcnet_amd.fit_frames(shown, args.fit)
+                pictures = shown
             first, second = seq[:-1].contiguous(), seq[1:].contiguous()
             tickets.append((i, j, info, shown if args.vis == "gpu" else None, model.submit(first, second),
-                            model.submit(second, first) if args.track_fb else None))
+                            model.submit(second, first) if both_ways else None, pictures if args.interp > 0 else None))
         model.synchronize()
-        for i, j, info, shown, ticket, reverse in tickets:
+        for i, j, info, shown, ticket, reverse, pictures in tickets:
             flow_final, flows = ticket.result()
             if info is not None:
                 flow_final = pwcnet_amd.refit_flow(flow_final, info)
             if chainer is not None:
                 chainer.add(i, flow_final.clone())   # (the replica writes its result buffer again at its next forward)
+            flow_back = None
+            if reverse is not None:
+                flow_back = reverse.result()[0]
+                if info is not None:
+                    flow_back = pwcnet_amd.refit_flow(flow_back, info)
             if tracker is not None:
-                flow_back = None
-                if reverse is not None:
-                    flow_back = reverse.result()[0]
-                    if info is not None:
-                        flow_back = pwcnet_amd.refit_flow(flow_back, info)
-                tracker.add(i, flow_final, flow_back)
+                tracker.add(i, flow_final, flow_back if args.track_fb else None)
+            if args.interp > 0:                      # one call per batch; only the uint8 pictures cross to the host
+                between = pwcnet_amd.interpolate_frames(pictures[:-1], pictures[1:], flow_final, flow_back,
+                                                        [k / (args.interp + 1) for k in range(1, args.interp + 1)],
+                                                        alpha=args.interp_alpha)[0].cpu().numpy()
+                for k in range(j - i):
+                    dname, fname = out_stem(paths[i + k])
+                    os.makedirs(os.path.join(args.out, dname), exist_ok=True)
+                    for m in range(args.interp):
+                        Image.fromarray(between[k, m]).save(os.path.join(args.out, dname, f"{fname}_t{m + 1}of{args.interp + 1}.png"))
             flow_final = flow_final.cpu().numpy()
             scales = [20.0 / 2 ** (num_levels - l) for l in range(len(flows))]
             if args.vis == "gpu":                    # one launch per batch; the pyramid stays on the GPU

@@ -13,6 +13,8 @@ from .splat import forward_splat, range_map, range_valid, splat_grad  # noqa: F4
 from .compose import chain_flows, compose_flows, compose_grad  # noqa: F401
 from . import track  # noqa: F401
 from .track import grid_points, track_points  # noqa: F401
+from . import interp  # noqa: F401
+from .interp import interpolate_frames  # noqa: F401
 from . import vis  # noqa: F401
 from .vis import flow_error_color, flow_max_radius, flow_to_color, pyramid_montage  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
@@ -29,4 +31,5 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "refit_flow", "flow_any_size", "draw_params", "crop_params", "augment_pairs", "frame_pyramid", "mask_pyramid", "level_flow_scale",
            "UnsupObjective", "FeatureNormLayer", "flow_distill_sums", "flow_distill_loss", "flow_distill_grad",
            "compose_flows", "compose_grad", "chain_flows", "vis", "flow_max_radius", "flow_to_color", "flow_error_color", "pyramid_montage",
-           "track", "track_points", "grid_points"]
+           "track", "track_points", "grid_points",
+           "interp", "interpolate_frames"]
