@@ -1213,6 +1213,67 @@ int pwc_interp_frames(const void* frames_0, int dtype_0, int cs_0, const void* f
                       const double* times, int M, float alpha, float min_range, void* workspace, size_t workspace_bytes,
                       void* frames_t, uint8_t* source, pwc_stream_t stream);
 
+/* ==== dominant motion: the parametric motion that explains most of a flow field, what it leaves, frames warped by it ====
+ * (pwc_motion.hip; semantics, launch plan and what the tests resolve in DESIGN.md 20.)  flows: N x H x W records of flow_cs >= 2
+ * floats, 2 used, in pixels; valid: N x H x W bytes or NULL (every pixel).  A pixel is KNOWN where its mask is non-zero and both
+ * components are finite and at most 1e9 in magnitude (the .flo sentinel rule); a masked pixel's flow is not loaded.  Every value is
+ * an IEEE double + - x /, a floor, a rint or a comparison in the order given here, no fused multiply-add and no library function:
+ * tests/motion_ref.py restates all three entry points in numpy bit for bit.
+ *
+ * FIT.  Coordinates are normalised, xh = (x - cx) / s, yh = (y - cy) / s with cx = (W - 1) / 2, cy = (H - 1) / 2, s = max(H, W) / 2;
+ * the model flow is (a0 + a1 xh) + a2 yh, (b0 + b1 xh) + b2 yh.  PWC_MOTION_TRANSLATION: a1 = a2 = b1 = b2 = 0;
+ * PWC_MOTION_SIMILARITY: a1 = b2 = alpha, b1 = -a2 = beta; PWC_MOTION_AFFINE: all six.  iters + 1 passes; in each, per known pixel,
+ * w = 1 (pass 0) or 1 / (1 + ((ru ru) + (rv rv)) / (scale scale)) with ru = u - ((a0 + a1 xh) + a2 yh), rv likewise, against the
+ * parameters the pass before wrote (the Cauchy weight), and the twelve sums of w, w xh, w yh, (w xh) xh, (w xh) yh, (w yh) yh, w u,
+ * (w xh) u, (w yh) u, w v, (w xh) v, (w yh) v plus the integer count.  Order of the sums: the image is cut into parts =
+ * min(ceil(H W / 256), 256) parts, lane t of part b adds the pixels b 256 + t, + parts 256, ... in that order starting from 0.0, the
+ * 256 lanes of a part add in the tree k = 128 .. 1 (lane t += lane t + k), one lane per image adds the parts in index order
+ * starting from 0.0 (the rule of the loss sums, in doubles).  That lane solves the normal equations by L D L^T elimination without
+ * pivoting: column j: t_ij = A_ij - l_i0 t_j0 - ... (left to right), d_j = t_jj, l_ij = t_ij / d_j; z_i = r_i - l_i0 z_0 - ...;
+ * x_i = z_i / d_i - l_i+1,i x_i+1 - ... (left to right).  Affine: A = [[Sw Sx Sy] [Sx Sxx Sxy] [Sy Sxy Syy]] with the right-hand
+ * sides (Su Sxu Syu) and (Sv Sxv Syv).  Similarity, unknowns (a0, b0, alpha, beta): A = [[Sw 0 Sx -Sy] [0 Sw Sy Sx] [Sx Sy Q 0]
+ * [-Sy Sx 0 Q]], Q = Sxx + Syy, right-hand side (Su, Sv, Sxu + Syv, Sxv - Syu).  Translation: a0 = Su / Sw, b0 = Sv / Sw.  An image
+ * is DEGENERATE where its count is below 1 / 2 / 3 (translation / similarity / affine) or a pivot fails d > 1e-9 Sw (a NaN
+ * fails; translation: Sw itself): ok = 0, zero parameters, in that pass and every later one.  Outputs, every element written:
+ * matrices N x 3 x 3 doubles, p' = M p for a pixel (x, y, 1): M00 = 1 + a1 / s, M01 = a2 / s, M02 = a0 - ((a1 cx) + (a2 cy)) / s,
+ * M10 = b1 / s, M11 = 1 + b2 / s, M12 = b0 - ((b1 cx) + (b2 cy)) / s, then 0 0 1 (the identity where ok = 0); ok N bytes; count N
+ * int32 known pixels; weight_sum N doubles, Sw of the last pass.  2 (iters + 1) launches on `stream`: sums on the grid (parts, N),
+ * then solve; no atomic, no host synchronisation, no process-wide state; an image's result does not depend on its neighbours in
+ * the batch and two calls give the same bits.  workspace: the size the _workspace_bytes function gives (0 for sizes the call
+ * refuses), 8-byte aligned.  Checks, in this order: a null flows, workspace or output pointer, N, H, W < 1, iters outside
+ * 0 .. 64, scale not > 0 (a NaN fails), flow_cs < 2, an unknown model (PWC_EINVAL); H W > 2^31 - 65537 or N > 65535 (PWC_ERANGE);
+ * flows or count off a 4-byte, workspace, matrices or weight_sum off an 8-byte boundary (PWC_EALIGN); a workspace that is too
+ * small (PWC_EINVAL).
+ *
+ * RESIDUAL, one launch, a lane per pixel (4096 workgroups of 256 lanes at most, grid-stride beyond): mu = (((M00 x) + (M01 y)) +
+ * M02) - x, mv likewise; ru = u - mu, rv = v - mv; residual = ((float)ru, (float)rv), rounded once; inlier = ((ru ru) + (rv rv))
+ * <= threshold threshold.  An unknown pixel, and every pixel of an image whose matrix has a last row other than exactly 0 0 1 or
+ * an entry of the first two rows that is not finite, gets 1e10 in both components and inlier 0.  residual: N x H x W x 2 floats,
+ * dense; inlier: N x H x W bytes.  Checks: null pointers, sizes < 1, flow_cs < 2, a negative or NaN threshold (PWC_EINVAL); the
+ * range as above (PWC_ERANGE); flows or residual off a 4-byte, matrices off an 8-byte boundary (PWC_EALIGN).
+ *
+ * WARP, one launch, a lane per four output pixels of the flat (N, H, W) index: frames N x H x W x C dense, PWC_MOTION_U8 or
+ * PWC_MOTION_F32, 1 <= C <= 4; matrices take an OUTPUT pixel to its source position, sx = ((M00 x) + (M01 y)) + M02, sy likewise.
+ * Covered iff the matrix is affine and finite (as above) and 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails); then x0 =
+ * floor(sx), x1 = min(x0 + 1, W - 1), wx1 = sx - x0, wx0 = 1 - wx1, likewise in y, and per channel
+ * (wy0 ((wx0 c00) + (wx1 c01))) + (wy1 ((wx0 c10) + (wx1 c11))) of the values widened to doubles (a byte v is v); floats are
+ * rounded once, bytes are rint (ties to even) clamped to [0, 255].  Not covered: every channel 0, covered 0.  out: N x H x W x C
+ * in the frames' dtype, covered: N x H x W bytes; bytes leave as C dwords per lane where out is on a 4-byte boundary, floats as C
+ * 16-byte stores where it is on a 16-byte one, else one by one -- the values are the same.  Checks: null pointers, sizes < 1, C
+ * outside 1 .. 4, an unknown dtype (PWC_EINVAL); the range as above (PWC_ERANGE); matrices off an 8-byte, float frames or out off a
+ * 4-byte boundary (PWC_EALIGN). */
+enum { PWC_MOTION_TRANSLATION = 0, PWC_MOTION_SIMILARITY = 1, PWC_MOTION_AFFINE = 2 };
+enum { PWC_MOTION_U8 = 0, PWC_MOTION_F32 = 1 };
+#define PWC_MOTION_MAX_ITERS 64
+size_t pwc_motion_fit_workspace_bytes(int N, int H, int W);
+int pwc_motion_fit_f64(const float* flows, int flow_cs, const uint8_t* valid, int N, int H, int W, int model, int iters,
+                       double scale, void* workspace, size_t workspace_bytes, double* matrices, uint8_t* ok, int32_t* count,
+                       double* weight_sum, pwc_stream_t stream);
+int pwc_motion_residual_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N, int H, int W,
+                            double threshold, float* residual, uint8_t* inlier, pwc_stream_t stream);
+int pwc_warp_affine(const void* frames, int dtype, int C, const double* matrices, int N, int H, int W, void* out, uint8_t* covered,
+                    pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,13 @@ and marks the points that fail the forward-backward check OCCLUDED.  The frames 
 <out>/<dname>/<fname>_t<k>of<M+1>.png (pwcnet_amd.interpolate_frames: both frames splatted along the two flows between them, one
 call per batch; the reversed pairs are run as --track_fb runs them; after the refit where --fit is not crop).  Only the uint8
 pictures come back to the host.  --interp_alpha A is the weight of the photometric match (exp(-A e)) [20].
+--motion MODEL also writes <out>/motion.npy (pairs, 3, 3) float64 and <out>/motion_ok.npy (pairs,) bool: the dominant motion of
+every pair, a translation, similarity or affine matrix taking a pixel (x, y, 1) of frame i to frame i + 1, fitted robustly on the
+GPU (pwcnet_amd.fit_motion, one call per batch; after the refit where --fit is not crop).  --motion_iters K and --motion_scale C
+are the reweighting passes [4] and the Cauchy scale in pixels [1.0].  --motion_residual also writes <fname>_residual.flo, the flow
+with that motion taken out (unknown pixels hold the .flo sentinel), and <fname>_inlier.png, white where a pixel moves with it.
+--stabilize R (needs --motion and frames of one size) smooths the camera path over 2 R + 1 frames (pwcnet_amd.smooth_path) and, in
+a second pass over the frames, writes <fname>_stab.png for every frame (pwcnet_amd.warp_frames).
 """
 import argparse
 import os
@@ -81,6 +88,14 @@ def build_parser():
                          "interpolated on the GPU from the two flows between them (the reversed pairs are run too) [off]")
     ap.add_argument("--interp_alpha", type=float, default=20.0, metavar="A",
                     help="--interp: the weight of a source pixel is exp(-min(A * e, 10)), e its match's mean colour error [20]")
+    ap.add_argument("--motion", choices=("translation", "similarity", "affine"), default=None,
+                    help="also write motion.npy / motion_ok.npy: the dominant motion of every pair, fitted robustly on the GPU [off]")
+    ap.add_argument("--motion_iters", type=int, default=4, metavar="K", help="--motion: reweighting passes, 0 .. 64 [4]")
+    ap.add_argument("--motion_scale", type=float, default=1.0, metavar="C", help="--motion: the Cauchy scale in pixels [1.0]")
+    ap.add_argument("--motion_residual", action="store_true",
+                    help="--motion: also write <fname>_residual.flo and <fname>_inlier.png for every pair")
+    ap.add_argument("--stabilize", type=int, default=0, metavar="R",
+                    help="--motion: also write <fname>_stab.png for every frame, the camera path smoothed over 2 R + 1 frames [0: off]")
     return ap
 
 
@@ -218,6 +233,14 @@ def main():
     if not args.interp_alpha >= 0.0:
         ap.error(f"--interp_alpha must be non-negative, got {args.interp_alpha}")
     both_ways = args.track_fb or args.interp > 0      # the reversed pairs are run too: one ticket serves both flags
+    if args.motion is None and (args.motion_residual or args.stabilize != 0):
+        ap.error("--motion_residual and --stabilize need --motion MODEL")
+    if not 0 <= args.motion_iters <= 64:
+        ap.error(f"--motion_iters must be in 0 .. 64, got {args.motion_iters}")
+    if not args.motion_scale > 0.0:
+        ap.error(f"--motion_scale must be positive, got {args.motion_scale}")
+    if args.stabilize < 0:
+        ap.error(f"--stabilize must be at least 0, got {args.stabilize}")
 
     from PIL import Image
     import pwcnet_amd
@@ -256,6 +279,9 @@ def main():
         if any(f.shape != frames[0].shape for f in frames):
             raise ValueError("--track needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
         tracker = Tracker(*parse_track_spec(args.track, len(frames), *frames[0].shape[:2]), len(frames), args.out)
+    motions, motions_ok = [None] * (len(frames) - 1), [None] * (len(frames) - 1)
+    if args.stabilize > 0 and any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("--stabilize needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
     window = 2 * max(1, args.pipeline)               # batches submitted before the first one is read back
     if both_ways:
         window = max(1, args.pipeline)               # (two forwards per batch)
@@ -298,6 +324,18 @@ def main():
                     os.makedirs(os.path.join(args.out, dname), exist_ok=True)
                     for m in range(args.interp):
                         Image.fromarray(between[k, m]).save(os.path.join(args.out, dname, f"{fname}_t{m + 1}of{args.interp + 1}.png"))
+            if args.motion is not None:              # one call per batch; matrices, flags and uint8 pictures cross to the host
+                matrices, ok, _ = pwcnet_amd.fit_motion(flow_final, model=args.motion, iters=args.motion_iters,
+                                                        scale=args.motion_scale)
+                motions[i:j], motions_ok[i:j] = list(matrices.cpu().numpy()), list(ok.cpu().numpy())
+                if args.motion_residual:
+                    residual, inlier = pwcnet_amd.motion_residual(flow_final, matrices)
+                    residual, inlier = residual.cpu().numpy(), (inlier.to(torch.uint8) * 255).cpu().numpy()
+                    for k in range(j - i):
+                        dname, fname = out_stem(paths[i + k])
+                        os.makedirs(os.path.join(args.out, dname), exist_ok=True)
+                        flow_io.write_flo(os.path.join(args.out, dname, fname + "_residual.flo"), residual[k])
+                        Image.fromarray(inlier[k]).save(os.path.join(args.out, dname, fname + "_inlier.png"))
             flow_final = flow_final.cpu().numpy()
             scales = [20.0 / 2 ** (num_levels - l) for l in range(len(flows))]
             if args.vis == "gpu":                    # one launch per batch; the pyramid stays on the GPU
@@ -315,6 +353,19 @@ def main():
                 flow_io.write_flo(os.path.join(args.out, dname, fname + ".flo"), flow_final[k])
     if tracker is not None:
         tracker.save()
+    if args.motion is not None:
+        os.makedirs(args.out, exist_ok=True)
+        np.save(os.path.join(args.out, "motion.npy"), np.stack(motions))
+        np.save(os.path.join(args.out, "motion_ok.npy"), np.asarray(motions_ok, bool))
+    if args.stabilize > 0:                           # the second pass: the frames again, batch by batch
+        steady = pwcnet_amd.smooth_path(np.stack(motions), args.stabilize)
+        for i in range(0, len(frames), max(1, args.batch)):
+            j = min(i + max(1, args.batch), len(frames))
+            stab = pwcnet_amd.warp_frames(torch.from_numpy(np.stack(frames[i:j])).cuda(), steady[i:j])[0].cpu().numpy()
+            for k in range(j - i):
+                dname, fname = out_stem(paths[i + k])
+                os.makedirs(os.path.join(args.out, dname), exist_ok=True)
+                Image.fromarray(stab[k]).save(os.path.join(args.out, dname, fname + "_stab.png"))
     print("Figure saved")
 
 

@@ -15,6 +15,8 @@ from . import track  # noqa: F401
 from .track import grid_points, track_points  # noqa: F401
 from . import interp  # noqa: F401
 from .interp import interpolate_frames  # noqa: F401
+from . import motion  # noqa: F401
+from .motion import fit_motion, motion_residual, smooth_path, warp_frames  # noqa: F401
 from . import vis  # noqa: F401
 from .vis import flow_error_color, flow_max_radius, flow_to_color, pyramid_montage  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
@@ -32,4 +34,5 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "UnsupObjective", "FeatureNormLayer", "flow_distill_sums", "flow_distill_loss", "flow_distill_grad",
            "compose_flows", "compose_grad", "chain_flows", "vis", "flow_max_radius", "flow_to_color", "flow_error_color", "pyramid_montage",
            "track", "track_points", "grid_points",
-           "interp", "interpolate_frames"]
+           "interp", "interpolate_frames",
+           "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path"]

@@ -2,7 +2,7 @@
 // bit-level contracts (tests/test_gpu_loss_bits.py), and every rule of them is written here once:
 //   sums       an image is cut into at most 256 parts of 256-pixel strides (pwc_loss_parts), a workgroup adds its part in a fixed
 //              tree (pwc_block_tree_sum), one thread per image adds the parts in index order (pwc_loss_final_kernel) -- two calls
-//              give the same bits;
+//              give the same bits; pwc_block_tree_sum_f64 is the same tree in doubles (pwc_motion.hip);
 //   norm       the ground truth's nearest-neighbour index (pwc_nearest_index), the difference with the ground truth DIVIDED
 //              (pwc_flow_diff), the norm of a pixel and its direction (pwc_norm_term, pwc_norm_direction);
 //   rho        the generalised Charbonnier function of the label-free terms and its derivative (unsup_rho, unsup_rho_grad);
@@ -64,6 +64,34 @@ __device__ __forceinline__ void pwc_block_tree_sum(float* sf, int* ci) {
     if (t == 0) {
 #pragma unroll
         for (int j = 0; j < M; ++j) sf[j] = redf[j][0];
+#pragma unroll
+        for (int j = 0; j < K; ++j) ci[j] = redi[j][0];
+    }
+}
+
+// The same rule in doubles (pwc_motion.hip): M doubles and K ints, the same tree, the same barriers.  24 KB of LDS at M = 12.
+template <int M, int K>
+__device__ __forceinline__ void pwc_block_tree_sum_f64(double* sd, int* ci) {
+    __shared__ double redd[M][256];
+    __shared__ int redi[K > 0 ? K : 1][256];
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < M; ++j) redd[j][t] = sd[j];
+#pragma unroll
+    for (int j = 0; j < K; ++j) redi[j][t] = ci[j];
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (t < k) {
+#pragma unroll
+            for (int j = 0; j < M; ++j) redd[j][t] += redd[j][t + k];
+#pragma unroll
+            for (int j = 0; j < K; ++j) redi[j][t] += redi[j][t + k];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) sd[j] = redd[j][0];
 #pragma unroll
         for (int j = 0; j < K; ++j) ci[j] = redi[j][0];
     }
