@@ -1274,6 +1274,45 @@ int pwc_motion_residual_f32(const float* flows, int flow_cs, const uint8_t* vali
 int pwc_warp_affine(const void* frames, int dtype, int C, const double* matrices, int N, int H, int W, void* out, uint8_t* covered,
                     pwc_stream_t stream);
 
+/* ==== moving regions: the connected components of a mask, numbered, with their areas, boxes and mean flows ====
+ * (pwc_regions.hip; semantics, launch plan and what the tests resolve in DESIGN.md 21.)  mask: N x H x W bytes; flows: N x H x W
+ * records of flow_cs >= 2 floats, 2 used, or NULL.  The result is defined by the input alone, not by the order in which lanes run:
+ *
+ *   FOREGROUND  a pixel whose mask byte is non-zero (invert != 0: whose mask byte is ZERO) and, where flows is given, whose two
+ *               components are finite and at most 1e9 in magnitude (the .flo sentinel rule); the flow of a pixel the mask
+ *               excludes is not loaded
+ *   CONNECTED   connectivity 4: foreground pixels that share an edge; 8: an edge or a corner.  Never across images.
+ *   ROOT        the smallest linear index y W + x of a component;  AREA  its pixel count;  KEPT  area >= min_area
+ *   ID          the kept components of an image numbered 1 .. K by ascending ROOT (raster order of their first pixel)
+ *   labels      N x H x W int32: the ID, 0 for background and for components that are not kept
+ *   count       N int32: K, the true number, also where K > max_regions
+ *   TABLE       for ids 1 .. min(K, max_regions), row id - 1; every other row zero; every element written:
+ *               area N x R int32;  box N x R x 4 int32: x0 y0 x1 y1, inclusive  (R = max_regions)
+ *               sums N x R x 2 int64 (only with flows): the sums of q = (int64) rint(clamp(u, -65536, 65536) * 65536.0), likewise v
+ *               mean N x R x 2 doubles (only with flows): ((double)sum_u / 65536.0) / (double)area, likewise v -- these two
+ *               divisions, in this order
+ *
+ * The sums are integers, the same in any order (the 64-bit fixed point of the splat and the composition).  Overflow bound: a
+ * pixel adds at most 2^32 in magnitude (65536 * 65536) and an image has at most 2^26 pixels, so a sum stays below 2^58 -- which
+ * is why H W > 2^26 is refused.  flows, sums and mean are NULL together or given together.
+ * Ten launches on `stream` (nine without flows; the seam launch is left out where the image is one tile): clear the table; label
+ * every pwc_regions_tile_h() x pwc_regions_tile_w() tile in the LDS by union-find; join the tiles along their seams with
+ * agent-scope atomicMin (every read of the array in that launch is an agent-scope atomic load); flatten every pixel to its root;
+ * areas by integer atomics; count, prefix and number the kept roots over min(ceil(H W / 256), 256) CONTIGUOUS chunks of the
+ * linear index; labels, boxes and sums by integer atomics; the means.  No loop waits for another lane or workgroup, no host
+ * synchronisation, no process-wide state, no floating-point atomic: an image's result does not depend on its neighbours in the
+ * batch and two calls give the same bits.  workspace: pwc_regions_workspace_bytes (0 for sizes the call refuses), 8-byte aligned,
+ * contents undefined before and after.  Checks, in this order: a null mask, workspace, labels, count, area or box, flows / sums /
+ * mean not NULL together, N, H, W < 1, connectivity other than 4 or 8, min_area < 1, max_regions outside 1 .. 65535, flows given
+ * with flow_cs < 2 (PWC_EINVAL); H W > 2^26 or N > 65535 (PWC_ERANGE); flows, labels, count, area or box off a 4-byte, workspace,
+ * sums or mean off an 8-byte boundary (PWC_EALIGN); a workspace that is too small (PWC_EINVAL). */
+int pwc_regions_tile_h(void);
+int pwc_regions_tile_w(void);
+size_t pwc_regions_workspace_bytes(int N, int H, int W);
+int pwc_label_regions(const uint8_t* mask, int invert, const float* flows, int flow_cs, int N, int H, int W, int connectivity,
+                      int min_area, int max_regions, void* workspace, size_t workspace_bytes, int32_t* labels, int32_t* count,
+                      int32_t* area, int32_t* box, int64_t* sums, double* mean, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,12 @@ are the reweighting passes [4] and the Cauchy scale in pixels [1.0].  --motion_r
 with that motion taken out (unknown pixels hold the .flo sentinel), and <fname>_inlier.png, white where a pixel moves with it.
 --stabilize R (needs --motion and frames of one size) smooths the camera path over 2 R + 1 frames (pwcnet_amd.smooth_path) and, in
 a second pass over the frames, writes <fname>_stab.png for every frame (pwcnet_amd.warp_frames).
+--regions (needs --motion) also writes, per pair, <fname>_regions.png, a 16-bit greyscale PNG of the ids of the regions that move
+on their own (pwcnet_amd.moving_regions: the connected components of the pixels whose flow is known and no inlier of the dominant
+motion; ids in raster order of the regions' first pixels, saturating at 65535, 0 for the rest), and <fname>_regions.npy, a
+(min(K, 256), 7) float64 table with the columns area x0 y0 x1 y1 mean_u mean_v (the box inclusive, the mean the region's motion
+relative to the camera in pixels).  --regions_min_area A drops smaller regions [16], --regions_connectivity 4 or 8 [8],
+--regions_threshold T is the inlier threshold in pixels [3.0].
 """
 import argparse
 import os
@@ -42,6 +48,9 @@ from glob import glob
 
 import numpy as np
 import torch
+
+
+REGIONS_ROWS = 256                                   # --regions: the rows of a pair's table at most
 
 
 def pyramid_montage(image, flows):
@@ -96,6 +105,13 @@ def build_parser():
                     help="--motion: also write <fname>_residual.flo and <fname>_inlier.png for every pair")
     ap.add_argument("--stabilize", type=int, default=0, metavar="R",
                     help="--motion: also write <fname>_stab.png for every frame, the camera path smoothed over 2 R + 1 frames [0: off]")
+    ap.add_argument("--regions", action="store_true",
+                    help="--motion: also write <fname>_regions.png (16-bit ids) and <fname>_regions.npy (area x0 y0 x1 y1 mean_u "
+                         "mean_v) for every pair: the regions that move on their own, labelled on the GPU")
+    ap.add_argument("--regions_min_area", type=_positive_int, default=16, metavar="A", help="--regions: drop regions below A pixels [16]")
+    ap.add_argument("--regions_connectivity", type=int, choices=(4, 8), default=8, help="--regions: shared edges, or edges and corners [8]")
+    ap.add_argument("--regions_threshold", type=float, default=3.0, metavar="T",
+                    help="--regions: a pixel moves with the camera where its residual is at most T pixels [3.0]")
     return ap
 
 
@@ -235,6 +251,10 @@ def main():
     both_ways = args.track_fb or args.interp > 0      # the reversed pairs are run too: one ticket serves both flags
     if args.motion is None and (args.motion_residual or args.stabilize != 0):
         ap.error("--motion_residual and --stabilize need --motion MODEL")
+    if args.regions and args.motion is None:
+        ap.error("--regions needs --motion MODEL")
+    if not args.regions_threshold >= 0.0:
+        ap.error(f"--regions_threshold must be non-negative, got {args.regions_threshold}")
     if not 0 <= args.motion_iters <= 64:
         ap.error(f"--motion_iters must be in 0 .. 64, got {args.motion_iters}")
     if not args.motion_scale > 0.0:
@@ -336,6 +356,18 @@ def main():
                         os.makedirs(os.path.join(args.out, dname), exist_ok=True)
                         flow_io.write_flo(os.path.join(args.out, dname, fname + "_residual.flo"), residual[k])
                         Image.fromarray(inlier[k]).save(os.path.join(args.out, dname, fname + "_inlier.png"))
+                if args.regions:                     # the ids and the tables cross to the host, nothing else
+                    labels, count, regions = pwcnet_amd.moving_regions(
+                        flow_final, matrices, threshold=args.regions_threshold, connectivity=args.regions_connectivity,
+                        min_area=args.regions_min_area, max_regions=REGIONS_ROWS)[:3]
+                    labels, count = labels.clamp(max=65535).cpu().numpy().astype(np.uint16), count.cpu().numpy()
+                    table = np.concatenate([regions["area"].cpu().numpy()[..., None].astype(np.float64),
+                                            regions["box"].cpu().numpy().astype(np.float64), regions["mean"].cpu().numpy()], axis=2)
+                    for k in range(j - i):
+                        dname, fname = out_stem(paths[i + k])
+                        os.makedirs(os.path.join(args.out, dname), exist_ok=True)
+                        Image.fromarray(labels[k]).save(os.path.join(args.out, dname, fname + "_regions.png"))
+                        np.save(os.path.join(args.out, dname, fname + "_regions.npy"), table[k, :min(int(count[k]), REGIONS_ROWS)])
             flow_final = flow_final.cpu().numpy()
             scales = [20.0 / 2 ** (num_levels - l) for l in range(len(flows))]
             if args.vis == "gpu":                    # one launch per batch; the pyramid stays on the GPU

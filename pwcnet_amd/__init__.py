@@ -17,6 +17,8 @@ from . import interp  # noqa: F401
 from .interp import interpolate_frames  # noqa: F401
 from . import motion  # noqa: F401
 from .motion import fit_motion, motion_residual, smooth_path, warp_frames  # noqa: F401
+from . import regions  # noqa: F401
+from .regions import label_regions, moving_regions  # noqa: F401
 from . import vis  # noqa: F401
 from .vis import flow_error_color, flow_max_radius, flow_to_color, pyramid_montage  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
@@ -35,4 +37,5 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "compose_flows", "compose_grad", "chain_flows", "vis", "flow_max_radius", "flow_to_color", "flow_error_color", "pyramid_montage",
            "track", "track_points", "grid_points",
            "interp", "interpolate_frames",
-           "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path"]
+           "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path",
+           "regions", "label_regions", "moving_regions"]
