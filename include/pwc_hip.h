@@ -1313,6 +1313,75 @@ int pwc_label_regions(const uint8_t* mask, int invert, const float* flows, int f
                       int min_area, int max_regions, void* workspace, size_t workspace_bytes, int32_t* labels, int32_t* count,
                       int32_t* area, int32_t* box, int64_t* sums, double* mean, pwc_stream_t stream);
 
+/* ==== region tracking: which region of image b a region of image a becomes, identities over a sequence ====
+ * (pwc_region_links.hip; semantics, launch plan and what the tests resolve in DESIGN.md 22.)  pwc_label_regions' ids are per
+ * image; these entry points join the label images of consecutive pairs along the flow between them.  The result is defined by the
+ * input alone, not by the order in which lanes run.
+ *
+ * pwc_link_regions, per image of a batch of N independent (a, b) pairs:
+ *   inputs      labels_a, labels_b  N x H x W int32 (pwc_label_regions' ids; any int32 is legal input)
+ *               area_a, area_b      N x R int32 (pwc_label_regions' tables), R = max_regions, 1 .. 1024
+ *               flows_ab            N x H x W records of flow_cs >= 2 floats, 2 used: frame a -> frame b, pixels
+ *               valid_ab            N x H x W bytes or NULL
+ *   VOTER       a pixel p = (x, y) with la = labels_a[p] in 1 .. R, valid byte non-zero (where given), and both flow
+ *               components finite and <= 1e9 in magnitude (the .flo sentinel rule).
+ *               The flow of a pixel that is no voter for the first two reasons is not loaded.
+ *   TARGET      qx = rint((double)x + (double)u), qy = rint((double)y + (double)v): one IEEE double addition each, then
+ *               rint (ties to even); compared AS DOUBLES with 0 and W-1 / H-1 before any conversion to an integer
+ *   VOTE        target out of frame:  left[la-1] += 1
+ *               else lb = labels_b[qy, qx];  c = lb if 1 <= lb <= R else 0;  overlap[la-1][c] += 1
+ *               (column 0: landed on background, or on a region beyond the table)
+ *   best_succ   row a:    the c in 1 .. R with the largest overlap[a][c], ties to the SMALLEST c; 0 if all are zero
+ *   best_pred   column b: the a in 1 .. R with the largest overlap[a][b], ties to the SMALLEST a; 0 if all are zero
+ *   LINK a->b   best_succ[a] == b  and  best_pred[b] == a  and  overlap >= min_overlap (int, >= 1)
+ *               and  (double)overlap >= min_fraction * (double)min(area_a[a-1], area_b[b-1])   (one multiply, one compare)
+ *   outputs     succ N x R int32 (b or 0), pred N x R int32 (a or 0), best_succ, best_pred N x R int32,
+ *               votes N x R x 4 int32: overlap[a][best_succ[a]] (0 if none), overlap[a][0], left[a], the row's voters
+ * All counts are integers added by atomics, the same in any order and at most H W <= 2^26.  A split shows as several b with one
+ * best_pred, a merge as several a with one best_succ; in either case only the mutual pair is a link.
+ * Five launches on `stream`: clear the N x R x (R + 2) vote table (overlap[a][0 .. R] and left[a] in one row); a lane per pixel
+ * votes, the lanes of a wave that hold one key issuing one atomic; a wave per row for best_succ and votes; a workgroup per 64
+ * columns for best_pred; a lane per row for succ and pred.  workspace: pwc_region_links_workspace_bytes(N, R) = 4 N R (R + 2)
+ * rounded up to 8 (0 for what the call refuses: N outside 1 .. 65535, R outside 1 .. 1024), 8-byte aligned, contents undefined
+ * before and after.  Checks, in this order: a null pointer other than valid_ab; N, H, W or max_regions < 1; min_overlap < 1;
+ * min_fraction outside [0, 1] or not finite; flow_cs < 2 (PWC_EINVAL); H W > 2^26, N > 65535 or max_regions > 1024 (PWC_ERANGE);
+ * a pointer other than valid_ab off a 4-byte, the workspace off an 8-byte boundary (PWC_EALIGN); a workspace that is too small
+ * (PWC_EINVAL).
+ *
+ * pwc_region_identities, over a sequence of S label images:
+ *   inputs      pred (S-1) x R (the link s-1 -> s: pwc_link_regions on labels[:-1], labels[1:], flows[:-1]; NULL allowed where
+ *               S == 1), count S int32, optionally ids_prev, age_prev, pred_prev R int32 each (the last image of an earlier call
+ *               and the link from it to image 0; NULL together or given together), next_id int32 >= 1
+ *   image 0     without ids_prev: row r < min(count[0], R) gets next_id + r, age 1.  With it: image 0 is treated like s >= 1.
+ *   image s     row b-1 for b = 1 .. min(count[s], R):  p = pred[s-1][b-1];
+ *               p in 1 .. R and ids[s-1][p-1] != 0  ->  ids[s][b-1] = ids[s-1][p-1],  age = age of that + 1
+ *               else fresh: next_id + (its rank among the fresh rows of image s in ascending b),  age = 1;
+ *               then next_id += the number of fresh rows
+ *   rows beyond min(count[s], R): 0
+ *   outputs     ids S x R int32, age S x R int32, next_id_out 1 int32 (the next_id after image S-1)
+ * next_id_in, 1 int32 on the device or NULL: where given, the first fresh id is read from there (an earlier call's next_id_out,
+ * so that a sequence fed in pieces needs no copy to the host) and `next_id` is the caller's upper bound of it, used for the range
+ * check alone.  One launch of one workgroup; the loop over s is inside the kernel, the previous image's ids and ages are in the
+ * LDS, the fresh ranks come from a ballot and a popcount per wave plus the wave totals.  Checks, in this order: a null count,
+ * ids, age or next_id_out, a null pred with S > 1, ids_prev / age_prev / pred_prev not NULL together; S or max_regions < 1,
+ * next_id < 1 (PWC_EINVAL); max_regions > 1024 or next_id + S R >= 2^31 (PWC_ERANGE); a pointer off a 4-byte boundary
+ * (PWC_EALIGN).
+ *
+ * pwc_relabel_regions: out[s][p] = ids[s][la-1] for la = labels[s][p] in 1 .. R, else 0; S x H x W int32, one launch, a lane per
+ * pixel.  Checks: a null pointer; S, H, W or max_regions < 1 (PWC_EINVAL); H W > 2^26, S > 65535 or max_regions > 1024
+ * (PWC_ERANGE); a pointer off a 4-byte boundary (PWC_EALIGN).
+ * No host synchronisation, no process-wide state, no floating-point atomic, no loop that waits for another lane or workgroup. */
+size_t pwc_region_links_workspace_bytes(int N, int max_regions);
+int pwc_link_regions(const int32_t* labels_a, const int32_t* labels_b, const int32_t* area_a, const int32_t* area_b,
+                     const float* flows_ab, int flow_cs, const uint8_t* valid_ab, int N, int H, int W, int max_regions,
+                     int min_overlap, double min_fraction, void* workspace, size_t workspace_bytes, int32_t* succ, int32_t* pred,
+                     int32_t* best_succ, int32_t* best_pred, int32_t* votes, pwc_stream_t stream);
+int pwc_region_identities(const int32_t* pred, const int32_t* count, const int32_t* ids_prev, const int32_t* age_prev,
+                          const int32_t* pred_prev, int next_id, const int32_t* next_id_in, int S, int max_regions, int32_t* ids,
+                          int32_t* age, int32_t* next_id_out, pwc_stream_t stream);
+int pwc_relabel_regions(const int32_t* labels, const int32_t* ids, int S, int H, int W, int max_regions, int32_t* out,
+                        pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,14 @@ motion; ids in raster order of the regions' first pixels, saturating at 65535, 0
 (min(K, 256), 7) float64 table with the columns area x0 y0 x1 y1 mean_u mean_v (the box inclusive, the mean the region's motion
 relative to the camera in pixels).  --regions_min_area A drops smaller regions [16], --regions_connectivity 4 or 8 [8],
 --regions_threshold T is the inlier threshold in pixels [3.0].
+--regions_track (needs --regions) also follows the regions from pair to pair (pwcnet_amd.track_regions, across batch boundaries): a
+region of pair i is the region of pair i + 1 that most of its pixels land on under the flow i -> i + 1, where that one is also
+fed mostly by it.  Per pair it writes <fname>_regions_ids.png, a 16-bit greyscale PNG of the regions' IDENTITIES (the same number for
+the same object in every pair, saturating at 65535), and <fname>_regions_ids.npy, a (min(K, 256), 2) int32 table with the columns
+identity age (row r: the region with id r + 1 in <fname>_regions.png; age: the consecutive pairs it has been seen in); at the end
+<out>/regions_tracks.npy, int32 rows identity first_pair last_pair.  --regions_track_overlap K and --regions_track_fraction F: a link
+needs at least K shared pixels [1] and at least F of the smaller region's area [0].  A change of the frame size starts new
+identities.
 """
 import argparse
 import os
@@ -112,6 +120,13 @@ def build_parser():
     ap.add_argument("--regions_connectivity", type=int, choices=(4, 8), default=8, help="--regions: shared edges, or edges and corners [8]")
     ap.add_argument("--regions_threshold", type=float, default=3.0, metavar="T",
                     help="--regions: a pixel moves with the camera where its residual is at most T pixels [3.0]")
+    ap.add_argument("--regions_track", action="store_true",
+                    help="--regions: also write <fname>_regions_ids.png / .npy for every pair and regions_tracks.npy: the regions "
+                         "followed from pair to pair on the GPU, one identity per object")
+    ap.add_argument("--regions_track_overlap", type=_positive_int, default=1, metavar="K",
+                    help="--regions_track: a link needs at least K shared pixels [1]")
+    ap.add_argument("--regions_track_fraction", type=float, default=0.0, metavar="F",
+                    help="--regions_track: a link needs at least F of the smaller region's area, 0 .. 1 [0]")
     return ap
 
 
@@ -231,6 +246,44 @@ class Tracker:
         np.save(os.path.join(self.out, "tracks_status.npy"), self.status)
 
 
+class RegionTracker:
+    """--regions_track: takes the labels, counts, tables and full-resolution flows of the pairs as they come, batch after batch,
+    gives every region its identity (pwcnet_amd.track_regions; the last pair's labels, table, ids and flow stay on the GPU as
+    the state) and writes the two files of every pair; save() writes the identities' first and last pairs."""
+
+    def __init__(self, paths, out, min_overlap, min_fraction):
+        self.paths, self.out, self.min_overlap, self.min_fraction = paths, out, min_overlap, min_fraction
+        self.state = None
+        self.spans = {}                              # identity -> [first pair, last pair]
+
+    def add(self, first, labels, count, regions, flows):
+        """labels, count, regions: moving_regions' of the pairs first, first + 1, ...; flows: (n,H,W,2) on the GPU, theirs."""
+        import pwcnet_amd
+        from PIL import Image
+        if self.state is not None and tuple(self.state["labels"].shape) != tuple(labels.shape[1:]):
+            self.state = {"ids": torch.zeros_like(self.state["ids"]), "age": torch.zeros_like(self.state["age"]),
+                          "next_id": self.state["next_id"], "next_id_bound": self.state["next_id_bound"],
+                          "labels": torch.zeros_like(labels[0]), "area": self.state["area"], "count": self.state["count"],
+                          "flow": torch.zeros_like(flows[0]), "valid": None}       # another frame size: nothing links, ids go on
+        ids, age, _, self.state = pwcnet_amd.track_regions(labels, count, regions, flows, state=self.state,
+                                                           min_overlap=self.min_overlap, min_fraction=self.min_fraction)
+        painted = pwcnet_amd.relabel_regions(labels, ids).clamp(max=65535).cpu().numpy().astype(np.uint16)
+        table, count = torch.stack([ids, age], dim=2).cpu().numpy(), count.cpu().numpy()
+        for k in range(labels.shape[0]):
+            dname, fname = out_stem(self.paths[first + k])
+            os.makedirs(os.path.join(self.out, dname), exist_ok=True)
+            rows = table[k, :min(int(count[k]), REGIONS_ROWS)]
+            Image.fromarray(painted[k]).save(os.path.join(self.out, dname, fname + "_regions_ids.png"))
+            np.save(os.path.join(self.out, dname, fname + "_regions_ids.npy"), rows)
+            for identity in rows[:, 0].tolist():
+                self.spans.setdefault(identity, [first + k, first + k])[1] = first + k
+
+    def save(self):
+        os.makedirs(self.out, exist_ok=True)
+        rows = [[identity, span[0], span[1]] for identity, span in sorted(self.spans.items())]
+        np.save(os.path.join(self.out, "regions_tracks.npy"), np.asarray(rows, np.int32).reshape(-1, 3))
+
+
 def main():
     ap = build_parser()
     args = ap.parse_args()
@@ -253,6 +306,10 @@ def main():
         ap.error("--motion_residual and --stabilize need --motion MODEL")
     if args.regions and args.motion is None:
         ap.error("--regions needs --motion MODEL")
+    if args.regions_track and not args.regions:
+        ap.error("--regions_track needs --regions")
+    if not 0.0 <= args.regions_track_fraction <= 1.0:
+        ap.error(f"--regions_track_fraction must be in 0 .. 1, got {args.regions_track_fraction}")
     if not args.regions_threshold >= 0.0:
         ap.error(f"--regions_threshold must be non-negative, got {args.regions_threshold}")
     if not 0 <= args.motion_iters <= 64:
@@ -299,6 +356,9 @@ def main():
         if any(f.shape != frames[0].shape for f in frames):
             raise ValueError("--track needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
         tracker = Tracker(*parse_track_spec(args.track, len(frames), *frames[0].shape[:2]), len(frames), args.out)
+    region_tracker = None
+    if args.regions_track:
+        region_tracker = RegionTracker(paths, args.out, args.regions_track_overlap, args.regions_track_fraction)
     motions, motions_ok = [None] * (len(frames) - 1), [None] * (len(frames) - 1)
     if args.stabilize > 0 and any(f.shape != frames[0].shape for f in frames):
         raise ValueError("--stabilize needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
@@ -360,6 +420,8 @@ def main():
                     labels, count, regions = pwcnet_amd.moving_regions(
                         flow_final, matrices, threshold=args.regions_threshold, connectivity=args.regions_connectivity,
                         min_area=args.regions_min_area, max_regions=REGIONS_ROWS)[:3]
+                    if region_tracker is not None:   # (before the host copies below take the names)
+                        region_tracker.add(i, labels, count, regions, flow_final)
                     labels, count = labels.clamp(max=65535).cpu().numpy().astype(np.uint16), count.cpu().numpy()
                     table = np.concatenate([regions["area"].cpu().numpy()[..., None].astype(np.float64),
                                             regions["box"].cpu().numpy().astype(np.float64), regions["mean"].cpu().numpy()], axis=2)
@@ -385,6 +447,8 @@ def main():
                 flow_io.write_flo(os.path.join(args.out, dname, fname + ".flo"), flow_final[k])
     if tracker is not None:
         tracker.save()
+    if region_tracker is not None:
+        region_tracker.save()
     if args.motion is not None:
         os.makedirs(args.out, exist_ok=True)
         np.save(os.path.join(args.out, "motion.npy"), np.stack(motions))
