@@ -20,6 +20,10 @@ all-gather of the statistics / flows); rank 0 prints one JSON line.
 with ONE radius, the ground truth's largest magnitude over its valid pixels, so the two compare side by side -- and
 D/<index>_err.png, the error on the log colour scale of KITTI's development kit (blue: below the Fl-all threshold, red: an
 outlier, black: no ground truth), all made on the GPU (pwcnet_amd.vis).
+--flow_filter R filters every predicted flow before it is scored and saved: the weighted median over a (2 R + 1)^2 window,
+R = 1 .. 7, guided by the first frame on the flow's grid (pwcnet_amd.filter_flow; after the refit where --fit is not crop), with
+--flow_filter_sigma_space (pixels), --flow_filter_sigma_color (grey levels per channel) [a box, no colour term] and
+--flow_filter_iters [1].  Running with and without it is how its effect on EPE and Fl-all is measured; nobody has yet.
 """
 import argparse
 import json
@@ -47,6 +51,8 @@ def build_parser():
     ap.add_argument("--normalize_features", action="store_true",
                     help="correlate layer-normalised feature maps (PWCDCNet(normalize_features=True)).  A checkpoint carries no marker for this: pass it exactly when the weights were trained with it")
     ap.add_argument("--norm_eps", type=float, default=1e-16, help="--normalize_features: epsilon under the square root [1e-16]")
+    from pwcnet_amd.flow_filter import add_cli_arguments
+    add_cli_arguments(ap)
     return ap
 
 
@@ -55,6 +61,8 @@ def main():
     args = ap.parse_args()
     if args.save_vis and not args.save_dir:
         ap.error("--save_vis requires --save_dir")
+    from pwcnet_amd.flow_filter import check_cli_arguments
+    filt = check_cli_arguments(ap, args)                          # filter_flow's keyword arguments, None without the flag
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -101,8 +109,12 @@ def main():
 
     def forward(im0, im1):
         if args.fit != "crop":
-            return pwcnet_amd.flow_any_size(model, im0, im1, args.fit)[0]
-        return model(im0, im1)[0]
+            flow = pwcnet_amd.flow_any_size(model, im0, im1, args.fit)[0]
+        else:
+            flow = model(im0, im1)[0]
+        if filt is not None:                                      # guided by the first frame on the flow's grid
+            flow = pwcnet_amd.filter_flow(flow, guide=im0, **filt)[0]
+        return flow
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()

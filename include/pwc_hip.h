@@ -1382,6 +1382,58 @@ int pwc_region_identities(const int32_t* pred, const int32_t* count, const int32
 int pwc_relabel_regions(const int32_t* labels, const int32_t* ids, int S, int H, int W, int max_regions, int32_t* out,
                         pwc_stream_t stream);
 
+/* ==== flow filter: the image-guided weighted median of a flow field, smoothing and hole filling ====
+ * (pwc_flow_filter.hip; launch plan, operation counts, resource figures and what the tests resolve in DESIGN.md 23.)  The
+ * weighted median over a window, with weights from spatial distance and colour similarity to the centre pixel and with unknown
+ * pixels left out (Sun, Roth, Black, "Secrets of optical flow estimation").  The weights are integers and a median is a
+ * selection: the result is a function of the input alone, bit for bit (tests/flow_filter_ref.py restates it in numpy).
+ *
+ * pwc_flow_filter_f32, per image of a batch of N:
+ *   inputs      flows        H x W records of flow_cs >= 2 floats, 2 used
+ *               valid        H x W bytes or NULL
+ *               guide        H x W x C, C = guide_c in {1, 3}, bytes (PWC_FLOW_FILTER_U8) or floats (PWC_FLOW_FILTER_F32), dense,
+ *                            or NULL (color_table is then ignored; guide_dtype and guide_c are still checked)
+ *               radius r     1 .. 7
+ *               space_table  (2r+1)^2 uint32 in 0 .. 65535, window raster order, ON THE DEVICE
+ *               color_table  255 C + 1 uint32 in 0 .. 65535, ON THE DEVICE.  Entries above 65535 are the caller's error (a weight
+ *                            is a 32-bit product); pwcnet_amd.filter_flow refuses them on the host.
+ *               smooth, fill flags, at least one set;  min_count >= 1;  iters >= 1
+ *   KNOWN(q)    the valid byte is non-zero (where a mask is given) and both flow components are finite and <= 1e9 in magnitude
+ *               (the .flo sentinel rule, flow_io.flow_valid)
+ *   GUIDE BYTE  a float guide value v becomes rint(clamp((double)v * 255.0, 0, 255)), ties to even, a NaN becomes 0; from then
+ *               on both guide dtypes are bytes
+ *   CANDIDATES  of a centre p: the pixels q INSIDE THE FRAME with |dx|, |dy| <= r and KNOWN(q); nothing is replicated or
+ *               mirrored beyond the border.  w_q = space_table[(dy+r)(2r+1) + (dx+r)] * color_table[d],
+ *               d = sum_c |guide[q,c] - guide[p,c]|; without a guide d = 0 and the colour table is not read (its factor is 1).
+ *               Only candidates with w_q > 0 count: n is their number, T their sum.  Weights and sums are unsigned 64-bit
+ *               integers, exact in any order.
+ *   MEDIAN      floats are ordered by the key k(x) = bits(x) ^ (bits(x) >> 31 ? 0xFFFFFFFF : 0x80000000), a total order in which
+ *               -0 < +0.  Per component, independently: the candidate value with the smallest key K such that
+ *               2 * sum_{k(x_q) <= K} w_q >= T (the lower weighted median).  The output carries that candidate's bits.
+ *   PIXEL       p KNOWN and smooth:       the medians if n >= 1, else the input bits;   out_valid 1
+ *               p KNOWN and not smooth:   the input bits;                               out_valid 1
+ *               p not KNOWN, fill and n >= min_count:   the medians;                    out_valid 1
+ *               otherwise:                (1e10, 1e10);                                 out_valid 0
+ *   PASSES      iters passes, each reading the flow and out_valid of the pass before (a hole wider than r closes from its rim
+ *               inwards); guide and tables are the same in every pass.
+ *   outputs     out H x W records of out_cs >= 2 floats, 2 written; out_valid H x W bytes
+ * One launch per pass on `stream`, no host synchronisation, no process-wide state, no atomics; an image's result depends on that
+ * image alone and two calls give the same bits.  workspace: pwc_flow_filter_workspace_bytes(N, H, W, iters) = 8 P + P rounded up
+ * to 8, P = N H W, for iters > 1 (one intermediate field; the passes alternate between it and out), 8-byte aligned, contents
+ * undefined before and after; NULL is fine where that is 0.
+ * Checks, in this order: a null flows, space_table, out or out_valid, a null color_table with a guide; N, H or W < 1; radius
+ * outside 1 .. 7; guide_c not 1 or 3 or an unknown guide_dtype (with or without a guide); neither smooth nor fill; min_count or iters < 1;
+ * flow_cs or out_cs < 2; out overlapping flows, or out_valid overlapping valid; a workspace that is too small (PWC_EINVAL);
+ * H W >= 2^31 or N > 65535 (PWC_ERANGE); flows, out, a table or a float guide off a 4-byte, the workspace off an 8-byte boundary
+ * (PWC_EALIGN). */
+enum { PWC_FLOW_FILTER_U8 = 0, PWC_FLOW_FILTER_F32 = 1 };
+#define PWC_FLOW_FILTER_MAX_RADIUS 7
+size_t pwc_flow_filter_workspace_bytes(int N, int H, int W, int iters);   /* 0 for iters == 1 and for sizes the call refuses */
+int pwc_flow_filter_f32(const float* flows, int flow_cs, const uint8_t* valid, const void* guide, int guide_dtype, int guide_c,
+                        int N, int H, int W, int radius, const uint32_t* space_table, const uint32_t* color_table,
+                        int smooth, int fill, int min_count, int iters, void* workspace, size_t workspace_bytes,
+                        float* out, int out_cs, uint8_t* out_valid, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

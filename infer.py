@@ -12,6 +12,10 @@ the 5-level flow pyramid rescaled to pixels at each level (x 20 / 2^(6-l), test.
 Writes <out>/flow_final.flo plus a colour-coded PNG per pyramid level instead of the
 reference's matplotlib PDF.  --vis gpu colours the PNGs on the GPU (pwcnet_amd.vis) instead of with numpy on copied-back flows;
 the .flo does not depend on it.  No interactive GPU prompt: the device is cuda:<--gpu>.
+--flow_filter R filters flow_final before it is written and coloured: the weighted median over a (2 R + 1)^2 window, R = 1 .. 7,
+guided by the first frame at the flow's geometry (pwcnet_amd.filter_flow; after the refit where --fit is not crop), with
+--flow_filter_sigma_space (pixels), --flow_filter_sigma_color (grey levels per channel) [a box, no colour term] and
+--flow_filter_iters [1].  Untuned: nobody has measured what it does to the error.
 """
 import argparse
 import os
@@ -38,11 +42,16 @@ def build_parser():
     ap.add_argument("--vis", choices=("host", "gpu"), default="host",
                     help="colour the PNGs with numpy on the copied-back flows, or on the GPU (pwcnet_amd.vis: only uint8 pictures "
                          "and the final flow cross to the host) [host]")
+    from pwcnet_amd.flow_filter import add_cli_arguments
+    add_cli_arguments(ap)
     return ap
 
 
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    from pwcnet_amd.flow_filter import check_cli_arguments
+    filt = check_cli_arguments(ap, args)                                   # filter_flow's keyword arguments, None without the flag
 
     from PIL import Image
     import pwcnet_amd
@@ -53,8 +62,10 @@ def main():
         imgs = [flow_io.factor_crop(np.asarray(Image.open(p).convert("RGB"))) for p in args.input_images]
         images = np.array(imgs, dtype=np.float32) / 255.0                  # (2, h, w, 3)
         x = torch.from_numpy(images).cuda()
+        guide = x[0:1]                                                     # (u8 / 255 as float32 goes back to the same bytes)
     else:                                                                  # uint8 upload; / 255 and the fit in one launch
         x = torch.from_numpy(np.stack([np.asarray(Image.open(p).convert("RGB")) for p in args.input_images])).cuda()
+        guide = x[0:1]                                                     # the first frame on its own grid, uint8
         x, info = pwcnet_amd.fit_frames(x, args.fit)
 
     model = pwcnet_amd.PWCDCNet(range_check="sync", normalize_features=args.normalize_features, norm_eps=args.norm_eps)      # results are final when a call returns (fp16-range check + fp32 repeat)
@@ -74,6 +85,8 @@ def main():
         print(f"Inference time: {(time.time() - t0) / args.iters} sec (averaged over {args.iters} iterations)")
     if args.fit != "crop":
         flow_final = pwcnet_amd.refit_flow(flow_final, info)               # the frame's own size, frame pixels
+    if filt is not None:
+        flow_final = pwcnet_amd.filter_flow(flow_final, guide=guide, **filt)[0]
 
     os.makedirs(args.out, exist_ok=True)
     flow_io.write_flo(os.path.join(args.out, "flow_final.flo"), flow_final[0].cpu().numpy())

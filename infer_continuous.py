@@ -48,6 +48,11 @@ identity age (row r: the region with id r + 1 in <fname>_regions.png; age: the c
 <out>/regions_tracks.npy, int32 rows identity first_pair last_pair.  --regions_track_overlap K and --regions_track_fraction F: a link
 needs at least K shared pixels [1] and at least F of the smaller region's area [0].  A change of the frame size starts new
 identities.
+--flow_filter R filters every pair's full-resolution flow before it is written or handed to any option above: the weighted median
+over a (2 R + 1)^2 window, R = 1 .. 7, guided by the pair's first frame (pwcnet_amd.filter_flow; after the refit where --fit is not
+crop, the reversed pairs' flows guided by their own first frame).  --flow_filter_sigma_space S (pixels) and
+--flow_filter_sigma_color C (grey levels per channel) shape the weights [a box, no colour term], --flow_filter_iters K repeats it
+[1].  The montage shows the network's pyramid and does not change.  Untuned: nobody has measured what it does to the error.
 """
 import argparse
 import os
@@ -127,6 +132,8 @@ def build_parser():
                     help="--regions_track: a link needs at least K shared pixels [1]")
     ap.add_argument("--regions_track_fraction", type=float, default=0.0, metavar="F",
                     help="--regions_track: a link needs at least F of the smaller region's area, 0 .. 1 [0]")
+    from pwcnet_amd.flow_filter import add_cli_arguments
+    add_cli_arguments(ap)
     return ap
 
 
@@ -318,6 +325,8 @@ def main():
         ap.error(f"--motion_scale must be positive, got {args.motion_scale}")
     if args.stabilize < 0:
         ap.error(f"--stabilize must be at least 0, got {args.stabilize}")
+    from pwcnet_amd.flow_filter import check_cli_arguments
+    filt = check_cli_arguments(ap, args)             # filter_flow's keyword arguments, None without --flow_filter
 
     from PIL import Image
     import pwcnet_amd
@@ -386,13 +395,18 @@ def main():
             flow_final, flows = ticket.result()
             if info is not None:
                 flow_final = pwcnet_amd.refit_flow(flow_final, info)
-            if chainer is not None:
-                chainer.add(i, flow_final.clone())   # (the replica writes its result buffer again at its next forward)
             flow_back = None
             if reverse is not None:
                 flow_back = reverse.result()[0]
                 if info is not None:
                     flow_back = pwcnet_amd.refit_flow(flow_back, info)
+            if filt is not None:                     # the frames at the flow's geometry are the guides; uint8 upload
+                guides = torch.from_numpy(np.stack(frames[i:j + 1])).cuda()
+                flow_final = pwcnet_amd.filter_flow(flow_final, guide=guides[:-1], **filt)[0]
+                if flow_back is not None:
+                    flow_back = pwcnet_amd.filter_flow(flow_back, guide=guides[1:], **filt)[0]
+            if chainer is not None:
+                chainer.add(i, flow_final.clone())   # (the replica writes its result buffer again at its next forward)
             if tracker is not None:
                 tracker.add(i, flow_final, flow_back if args.track_fb else None)
             if args.interp > 0:                      # one call per batch; only the uint8 pictures cross to the host
