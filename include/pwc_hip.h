@@ -1434,6 +1434,69 @@ int pwc_flow_filter_f32(const float* flows, int flow_cs, const uint8_t* valid, c
                         int smooth, int fill, int min_count, int iters, void* workspace, size_t workspace_bytes,
                         float* out, int out_cs, uint8_t* out_valid, pwc_stream_t stream);
 
+/* ==== temporal filter: every frame of a clip averaged with its neighbours along the motion ====
+ * (pwc_temporal.hip; launch shape, bytes per pixel, resource figures and what is unmeasured in DESIGN.md 24.)  Every pixel of an
+ * output frame is the weighted mean of itself and of what its trajectory through the R frames after and the R frames before
+ * shows: a neighbour is read where the consecutive flows say the pixel went, weighs by how well its patch matches, and is
+ * dropped -- with everything beyond it on that side -- where the walk leaves the frame, meets an unknown flow or fails the
+ * forward-backward check.
+ *
+ * pwc_temporal_filter, one clip per call:
+ *   inputs      frames       T x H x W x C, C in {1, 3}, dense, bytes (PWC_TEMPORAL_U8) or floats (PWC_TEMPORAL_F32, values in
+ *                            [0, 1] expected, nothing clamped).  GREY LEVEL of a stored value: a = (double)byte, or
+ *                            a = 255.0 * (double)v, a NaN reads as 0.
+ *               flows_fw     (T - 1) x H x W records of fw_cs >= 2 floats, 2 used: flows_fw[j] is the flow j -> j + 1, in pixels
+ *               flows_bw     the same at bw_cs: flows_bw[j] is the flow j + 1 -> j.  Both may be NULL where T == 1.
+ *               valids_fw, valids_bw   (T - 1) x H x W bytes or NULL (every pixel)
+ *               radius R 1 .. 8; patch P 0 .. 2; sigma > 0 in grey levels; max_distance in grey levels, <= 0: off; fb_check;
+ *               alpha1, alpha2 (the forward-backward check's); [i0, i1), the frames of the clip to produce
+ *   outputs     filtered (i1 - i0) x H x W x C in the frames' dtype, support (i1 - i0) x H x W bytes in 0 .. 2 R; every element
+ *               written; frames i0 .. i1 - 1 in order.
+ * Every operation is an IEEE double + - x /, a floor, a rint or a comparison in exactly this order, no fused multiply-add, no
+ * library function (tests/temporal_ref.py restates it in numpy bit for bit).  For output frame i and pixel p = (px, py):
+ *   acc_c = a_c(p), c = 0 .. C - 1;  wsum = 1;  support = 0.
+ *   n = C times the number of offsets o = (ox, oy), |ox|, |oy| <= P, with p + o inside the frame.
+ *   For s = +1, then s = -1:  (x, y) = ((float)px, (float)py).  For k = 1 .. R:
+ *     f = i + s k outside 0 .. T - 1: this direction ends.
+ *     STEP: pwc_track_points_f32's ONE STEP above (A, B, C, D, word for word) of a VISIBLE point at (x, y), with
+ *       s = +1:  F = flows_fw[i + k - 1], its mask valids_fw[i + k - 1];  G = flows_bw[i + k - 1], valids_bw[i + k - 1]
+ *       s = -1:  F = flows_bw[i - k], valids_bw[i - k];  G = flows_fw[i - k], valids_fw[i - k]
+ *       and G not given where fb_check == 0 (step D is then skipped and G's mask is not read).  Any outcome but VISIBLE -- LEFT,
+ *       UNKNOWN, OCCLUDED -- ends this direction: frame f and everything beyond it on this side contribute nothing.  Else
+ *       (x, y) = ((float)rx, (float)ry), rounded once, inside the frame.
+ *     SAMPLES of frame f around q = (x, y):  qx = (double)x, x0 = floor(qx), wx = qx - x0, ux = 1 - wx, likewise in y -- ONE
+ *       fractional part for the whole patch.  col(j) = min(max(x0 + j, 0), W - 1), row(j) = min(max(y0 + j, 0), H - 1): the
+ *       corner coordinates are clamped to the frame, each on its own (the frame replicated beyond its border).  With g the grey
+ *       levels of frame f,
+ *         h_c(jx, jy) = (ux g_c[row(jy)][col(jx)]) + (wx g_c[row(jy)][col(jx + 1)])
+ *         b_c(o)      = (uy h_c(ox, oy)) + (wy h_c(ox, oy + 1))
+ *       b_c(0, 0) is the forward-backward check's sample of frame f at q.
+ *     DISTANCE: sum = 0; for oy = -P .. P, for ox = -P .. P with p + o inside the frame, for c = 0 .. C - 1:
+ *       df = a_c(p + o) - b_c(o);  sum = sum + (df df).   d2 = sum / (double)n.
+ *     WEIGHT: w = 1 / (1 + (d2 / (sigma sigma)));  w = 0 where max_distance > 0 and d2 > (max_distance max_distance).  The walk
+ *       goes on either way.
+ *     acc_c = acc_c + (w b_c(0, 0));  wsum = wsum + w;  support += 1 where w > 0.
+ *   v_c = acc_c / wsum.  Bytes: rint(v_c), ties to even, clamped to [0, 255], 0 for a NaN.  Floats: (float)(v_c / 255.0).
+ * T == 1: no flow is read, filtered is the input (a float NaN comes out as 0), support 0.  A piece [i0, i1) of a call over a clip
+ * equals, bit for bit, the same frames of a call over any sub-clip that holds frames max(i0 - R, 0) .. min(i1 - 1 + R, T - 1).
+ *
+ * One launch on `stream`: a lane per output pixel in tiles of 32 x 8, 256-lane workgroups, grid (ceil(W / 32), ceil(H / 8),
+ * i1 - i0).  A workgroup stages its tile of frame i with a halo of P pixels in the LDS as grey levels, then every lane walks on its
+ * own; the (2P+2)^2 footprint of a neighbour is loaded once, row by row, and all (2P+1)^2 samples are formed from it.  No
+ * workspace, no atomics, no host synchronisation, no process-wide state; 64-bit frame and flow offsets; two calls give the same
+ * bits.  Checks, before the launch, in this order: a null frames, filtered or support, T, H or W < 1; with T > 1 a null flow or a
+ * channel stride below 2; an unknown dtype, C not 1 or 3; radius outside 1 .. 8, patch outside 0 .. 2; sigma (or its square) not
+ * positive and finite, a NaN max_distance; with fb_check an alpha that is negative or NaN; i0 < 0, i1 > T or i0 >= i1
+ * (PWC_EINVAL); H or W > 2^24, H W >= 2^31, T > 65535, more than 65535 tile rows (PWC_ERANGE); with T > 1 a flow, with float frames
+ * frames or filtered, off a 4-byte boundary (PWC_EALIGN). */
+enum { PWC_TEMPORAL_U8 = 0, PWC_TEMPORAL_F32 = 1 };
+#define PWC_TEMPORAL_MAX_RADIUS 8
+#define PWC_TEMPORAL_MAX_PATCH 2
+int pwc_temporal_filter(const void* frames, int dtype, int C, const float* flows_fw, int fw_cs, const float* flows_bw, int bw_cs,
+                        const uint8_t* valids_fw, const uint8_t* valids_bw, int T, int H, int W, int radius, int patch,
+                        double sigma, double max_distance, int fb_check, float alpha1, float alpha2, int i0, int i1,
+                        void* filtered, uint8_t* support, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

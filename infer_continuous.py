@@ -53,6 +53,12 @@ over a (2 R + 1)^2 window, R = 1 .. 7, guided by the pair's first frame (pwcnet_
 crop, the reversed pairs' flows guided by their own first frame).  --flow_filter_sigma_space S (pixels) and
 --flow_filter_sigma_color C (grey levels per channel) shape the weights [a box, no colour term], --flow_filter_iters K repeats it
 [1].  The montage shows the network's pyramid and does not change.  Untuned: nobody has measured what it does to the error.
+--denoise R also writes <out>/<dname>/<fname>_denoised.png for EVERY frame: the frame averaged with its R = 1 .. 8 neighbours on
+either side along the flow (pwcnet_amd.temporal_filter, across batch boundaries; the reversed pairs are run as --track_fb runs
+them; after the refit where --fit is not crop).  A neighbour weighs 1 / (1 + d^2 / S^2) by its patch's difference d in grey levels
+(--denoise_sigma S [10], --denoise_patch P for (2 P + 1)^2 patches [1]) and is dropped where the forward-backward check fails
+(--denoise_no_fb keeps it).  Only the uint8 pictures come back to the host.  The frames must all have one size.  Untuned: nobody
+has measured the denoising quality on real footage.
 """
 import argparse
 import os
@@ -134,6 +140,8 @@ def build_parser():
                     help="--regions_track: a link needs at least F of the smaller region's area, 0 .. 1 [0]")
     from pwcnet_amd.flow_filter import add_cli_arguments
     add_cli_arguments(ap)
+    from pwcnet_amd.temporal import add_cli_arguments as add_denoise_arguments
+    add_denoise_arguments(ap)
     return ap
 
 
@@ -253,6 +261,44 @@ class Tracker:
         np.save(os.path.join(self.out, "tracks_status.npy"), self.status)
 
 
+class Denoiser:
+    """--denoise R: takes the uint8 frames at the flows' size and the full-resolution flows i -> i + 1 and i + 1 -> i as they come,
+    batch after batch, keeps the frames and flows the pieces still to come need on the GPU (the last 2 R frames once a piece is
+    done) and writes <fname>_denoised.png for the frames of every piece of pwcnet_amd.plan_windows as soon as its clip is there --
+    the last R frames of the sequence with the last batch."""
+
+    def __init__(self, kwargs, nframes, batch, paths, out):
+        import pwcnet_amd
+        self.kwargs, self.paths, self.out = kwargs, paths, out
+        self.pieces = pwcnet_amd.plan_windows(nframes, kwargs["radius"], max(1, batch))
+        self.frames, self.fw, self.bw = {}, {}, {}   # frame / pair index -> its tensor on the GPU
+
+    def add(self, first, pictures, flows_fw, flows_bw):
+        """pictures: (n + 1,H,W,3) uint8 on the GPU, the frames first, first + 1, ...; flows_fw, flows_bw: (n,H,W,2), the flows
+        of the pairs first, first + 1, ... and of the reversed pairs."""
+        import pwcnet_amd
+        from PIL import Image
+        n = flows_fw.shape[0]
+        for k in range(n + 1):
+            self.frames[first + k] = pictures[k]
+        for k in range(n):                           # (the replica writes its result buffers again at its next forward)
+            self.fw[first + k], self.bw[first + k] = flows_fw[k].clone(), flows_bw[k].clone()
+        while self.pieces and self.pieces[0][1] - 1 <= first + n:
+            cs, ce, o0, o1 = self.pieces.pop(0)
+            clip = torch.stack([self.frames[i] for i in range(cs, ce)])
+            fw = torch.stack([self.fw[i] for i in range(cs, ce - 1)]) if ce - cs > 1 else None
+            bw = torch.stack([self.bw[i] for i in range(cs, ce - 1)]) if ce - cs > 1 else None
+            denoised = pwcnet_amd.temporal_filter(clip, fw, bw, out_range=(o0 - cs, o1 - cs), **self.kwargs)[0].cpu().numpy()
+            for i in range(o0, o1):
+                dname, fname = out_stem(self.paths[i])
+                os.makedirs(os.path.join(self.out, dname), exist_ok=True)
+                Image.fromarray(denoised[i - o0]).save(os.path.join(self.out, dname, fname + "_denoised.png"))
+            keep = self.pieces[0][0] if self.pieces else first + n + 1
+            for held in (self.frames, self.fw, self.bw):
+                for i in [i for i in held if i < keep]:
+                    del held[i]
+
+
 class RegionTracker:
     """--regions_track: takes the labels, counts, tables and full-resolution flows of the pairs as they come, batch after batch,
     gives every region its identity (pwcnet_amd.track_regions; the last pair's labels, table, ids and flow stay on the GPU as
@@ -308,7 +354,10 @@ def main():
         ap.error(f"--interp must be at most 16 (pwcnet_amd.interp.MAX_TIMES), got {args.interp}")
     if not args.interp_alpha >= 0.0:
         ap.error(f"--interp_alpha must be non-negative, got {args.interp_alpha}")
-    both_ways = args.track_fb or args.interp > 0      # the reversed pairs are run too: one ticket serves both flags
+    from pwcnet_amd.temporal import check_cli_arguments as check_denoise_arguments
+    denoise = check_denoise_arguments(ap, args)      # temporal_filter's keyword arguments, None without --denoise
+    # the reversed pairs are run too: one ticket serves the three flags
+    both_ways = args.track_fb or args.interp > 0 or denoise is not None
     if args.motion is None and (args.motion_residual or args.stabilize != 0):
         ap.error("--motion_residual and --stabilize need --motion MODEL")
     if args.regions and args.motion is None:
@@ -365,6 +414,11 @@ def main():
         if any(f.shape != frames[0].shape for f in frames):
             raise ValueError("--track needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
         tracker = Tracker(*parse_track_spec(args.track, len(frames), *frames[0].shape[:2]), len(frames), args.out)
+    denoiser = None
+    if denoise is not None:
+        if any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("--denoise needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
+        denoiser = Denoiser(denoise, len(frames), args.batch, paths, args.out)
     region_tracker = None
     if args.regions_track:
         region_tracker = RegionTracker(paths, args.out, args.regions_track_overlap, args.regions_track_fraction)
@@ -377,11 +431,11 @@ def main():
     for w0 in range(0, len(jobs), window):
         tickets = []
         for i, j in jobs[w0:w0 + window]:
-            pictures = None                          # --interp: the uint8 frames at the flows' size
+            pictures = None                          # --interp, --denoise: the uint8 frames at the flows' size
             if args.fit == "crop":
                 seq = torch.from_numpy(np.stack(frames[i:j + 1]).astype(np.float32) / 255.0).cuda()
                 info, shown = None, seq              # (a float32 frame made as u8 / 255 gives back u8)
-                if args.interp > 0:
+                if args.interp > 0 or denoiser is not None:
                     pictures = torch.from_numpy(np.stack(frames[i:j + 1])).cuda()
             else:                                    # uint8 upload; / 255 and the fit in one launch on the caller's stream
                 shown = torch.from_numpy(np.stack(frames[i:j + 1])).cuda()
@@ -389,7 +443,8 @@ def main():
                 pictures = shown
             first, second = seq[:-1].contiguous(), seq[1:].contiguous()
             tickets.append((i, j, info, shown if args.vis == "gpu" else None, model.submit(first, second),
-                            model.submit(second, first) if both_ways else None, pictures if args.interp > 0 else None))
+                            model.submit(second, first) if both_ways else None,
+                            pictures if args.interp > 0 or denoiser is not None else None))
         model.synchronize()
         for i, j, info, shown, ticket, reverse, pictures in tickets:
             flow_final, flows = ticket.result()
@@ -418,6 +473,8 @@ def main():
                     os.makedirs(os.path.join(args.out, dname), exist_ok=True)
                     for m in range(args.interp):
                         Image.fromarray(between[k, m]).save(os.path.join(args.out, dname, f"{fname}_t{m + 1}of{args.interp + 1}.png"))
+            if denoiser is not None:                 # only the uint8 pictures cross to the host
+                denoiser.add(i, pictures, flow_final, flow_back)
             if args.motion is not None:              # one call per batch; matrices, flags and uint8 pictures cross to the host
                 matrices, ok, _ = pwcnet_amd.fit_motion(flow_final, model=args.motion, iters=args.motion_iters,
                                                         scale=args.motion_scale)

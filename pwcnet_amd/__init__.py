@@ -23,6 +23,8 @@ from . import region_tracks  # noqa: F401
 from .region_tracks import link_regions, region_identities, relabel_regions, track_regions  # noqa: F401
 from . import flow_filter  # noqa: F401
 from .flow_filter import fill_flow, filter_flow, filter_tables  # noqa: F401
+from . import temporal  # noqa: F401
+from .temporal import plan_windows, temporal_filter  # noqa: F401
 from . import vis  # noqa: F401
 from .vis import flow_error_color, flow_max_radius, flow_to_color, pyramid_montage  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
@@ -44,4 +46,5 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path",
            "regions", "label_regions", "moving_regions",
            "region_tracks", "link_regions", "region_identities", "relabel_regions", "track_regions",
-           "flow_filter", "filter_tables", "filter_flow", "fill_flow"]
+           "flow_filter", "filter_tables", "filter_flow", "fill_flow",
+           "temporal", "temporal_filter", "plan_windows"]
