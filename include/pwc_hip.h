@@ -1497,6 +1497,69 @@ int pwc_temporal_filter(const void* frames, int dtype, int C, const float* flows
                         double sigma, double max_distance, int fb_check, float alpha1, float alpha2, int i0, int i1,
                         void* filtered, uint8_t* support, pwc_stream_t stream);
 
+/* ==== background plate: the frames of a clip registered on one canvas and voted per pixel; every frame against that plate ====
+ * (pwc_plate.hip; the LDS and selection design, launch geometry, resource figures and what is unmeasured in DESIGN.md 25.)
+ * Every value is an IEEE double + - x /, a floor, a rint or a comparison in the order given here, no fused multiply-add and no
+ * library function: tests/plate_ref.py restates both entry points in numpy bit for bit.  AFFINE AND FINITE, of a 3 x 3 matrix of
+ * doubles: WARP's rule above -- the last row exactly 0 0 1 and the six entries of the first two rows finite.
+ *
+ * pwc_plate_build, one clip per call:
+ *   inputs      frames    T x H x W x C dense, PWC_MOTION_U8 or PWC_MOTION_F32, 1 <= C <= 4, 1 <= T <= PWC_PLATE_MAX_FRAMES
+ *               matrices  T x 3 x 3 doubles, each taking a CANVAS pixel (x, y, 1) to its position in frame t (pwc_warp_affine's
+ *                         convention with the canvas as the output)
+ *               use       T bytes or NULL (every frame);  masks  T x H x W bytes or NULL (every pixel)
+ *               the canvas size Hc x Wc;  mode PWC_PLATE_MEDIAN or PWC_PLATE_MEAN;  min_count >= 1
+ *   SAMPLE      of frame t at canvas pixel (x, y):  sx = ((M00 x) + (M01 y)) + M02, sy = ((M10 x) + (M11 y)) + M12.  PRESENT iff
+ *               use[t] is non-zero, the matrix is affine and finite, 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails), the
+ *               masks of all four corners below are non-zero and, for float frames, all four corners are finite in every
+ *               channel (the frame of a sample that fails an earlier condition is not read).  x0 = floor(sx), x1 = min(x0 + 1,
+ *               W - 1), wx1 = sx - x0, wx0 = 1 - wx1, likewise in y; per channel
+ *               v = (wy0 ((wx0 c00) + (wx1 c01))) + (wy1 ((wx0 c10) + (wx1 c11))) of the values widened to doubles (a byte b is b).
+ *   ROUNDED     r = rint(v), ties to even, clamped to [0, 255] for bytes; r = (float)v, one rounding, for floats.
+ *   n           the number of PRESENT samples, 0 .. T.
+ *   MEDIAN      per channel, independently: the element of rank (n - 1) / 2 (integer division, 0-based) of the n ROUNDED
+ *               samples in ascending order -- the lower median.  Floats are ordered by the flow filter's key
+ *               k(x) = bits(x) ^ (bits(x) >> 31 ? 0xFFFFFFFF : 0x80000000), so -0 < +0, and the output is one of the samples' bit
+ *               patterns.
+ *   MEAN        per channel: s = 0.0; s = s + v for the PRESENT samples in frame order (the doubles, not the rounded values);
+ *               s / (double)n, ROUNDED.
+ *   outputs     plate Hc x Wc x C in the frames' dtype, count Hc x Wc bytes = n; where n < min_count the plate is 0 in every
+ *               channel (count still n).  Every element is written.
+ * One launch on `stream`: a lane per canvas pixel in tiles of 32 x 8, 256-lane workgroups, min(tiles, 65536) workgroups,
+ * tile-stride beyond.  MEAN keeps its sums in registers.  MEDIAN keeps the ROUNDED samples of a lane in the LDS, T x 256 dwords of
+ * dynamic LDS (1 KB per frame, 64 KB at T = 64), slot j of lane l at dword 256 j + l: bytes as one dword per sample (channel c in
+ * bits 8 c ..), floats one channel at a time as keys (the corners of the PRESENT samples are gathered again for each further
+ * channel).  A lane reads and writes its own slots only: no barrier, no loop that waits for another lane.  Nothing is sorted: the
+ * result is built from the top bit down, a round counting the samples below prefix | bit and keeping the bit iff that count is
+ * <= (n - 1) / 2 (8 rounds for bytes, all channels in one; 32 for a float channel).  No atomics, no workspace, no scratch, no
+ * host synchronisation, no process-wide state; 64-bit frame offsets; two calls give the same bits.
+ * Checks, in this order: a null frames, matrices, plate or count; T, H, W, Hc or Wc < 1; T > PWC_PLATE_MAX_FRAMES; C outside
+ * 1 .. 4; an unknown dtype or mode; min_count < 1 (PWC_EINVAL); H W or Hc Wc > 2^31 - 65537 (PWC_ERANGE); matrices off an
+ * 8-byte, float frames or plate off a 4-byte boundary (PWC_EALIGN).
+ *
+ * pwc_plate_difference, one launch, a lane per frame pixel of the flat (T, H, W) index (4096 workgroups of 256 lanes at most,
+ * grid-stride beyond):
+ *   inputs      frames T x H x W x C as above (any T >= 1);  plate Hc x Wc x C in the frames' dtype, count Hc x Wc bytes
+ *               (pwc_plate_build's);  matrices T x 3 x 3 doubles, each taking a FRAME pixel (x, y, 1) of frame t to its position
+ *               on the canvas;  min_count >= 1;  threshold >= 0
+ *   KNOWN       iff the matrix is affine and finite, 0 <= sx <= Wc - 1 and 0 <= sy <= Hc - 1 (sx, sy and the corners as in
+ *               SAMPLE, on the canvas), count >= min_count at all four corners and, for floats, the pixel's own channels and
+ *               the plate's four corners are finite in every channel.
+ *   d           0.0; per channel in order: e = |f - s|, f the frame's value widened to double, s the plate's bilinear double v
+ *               (unrounded); d = e where e > d.
+ *   outputs     difference T x H x W floats: (float)d, 0 where not KNOWN;  foreground T x H x W bytes: KNOWN and d > threshold
+ *               (of the double);  known T x H x W bytes.  Every element is written.
+ * Checks, in this order: a null pointer; T, H, W, Hc or Wc < 1; C outside 1 .. 4; an unknown dtype; min_count < 1; a negative or
+ * NaN threshold (PWC_EINVAL); H W or Hc Wc > 2^31 - 65537 or T > 65535 (PWC_ERANGE); matrices off an 8-byte, difference, float
+ * frames or a float plate off a 4-byte boundary (PWC_EALIGN). */
+enum { PWC_PLATE_MEDIAN = 0, PWC_PLATE_MEAN = 1 };
+#define PWC_PLATE_MAX_FRAMES 64
+int pwc_plate_build(const void* frames, int dtype, int C, const double* matrices, const uint8_t* use, const uint8_t* masks, int T,
+                    int H, int W, int Hc, int Wc, int mode, int min_count, void* plate, uint8_t* count, pwc_stream_t stream);
+int pwc_plate_difference(const void* frames, int dtype, int C, const void* plate, const uint8_t* count, const double* matrices,
+                         int T, int H, int W, int Hc, int Wc, int min_count, double threshold, float* difference,
+                         uint8_t* foreground, uint8_t* known, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

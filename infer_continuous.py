@@ -59,6 +59,18 @@ them; after the refit where --fit is not crop).  A neighbour weighs 1 / (1 + d^2
 (--denoise_sigma S [10], --denoise_patch P for (2 P + 1)^2 patches [1]) and is dropped where the forward-backward check fails
 (--denoise_no_fb keeps it).  Only the uint8 pictures come back to the host.  The frames must all have one size.  Untuned: nobody
 has measured the denoising quality on real footage.
+--plate (needs --motion and frames of one size) writes, after the last pair, <out>/plate.png and <out>/plate_count.png: the
+background plate of the sequence.  The dominant motions are chained from frame --plate_anchor A [0] (pwcnet_amd.plate_path; a pair
+whose fit is degenerate cuts the chain, the frames beyond it are left out), the canvas is the box the reachable frames cover in the
+anchor's coordinates grown by --plate_margin M [0] (pwcnet_amd.plate_canvas; an error where a side is above --plate_max_side S
+[4096]), and at most --plate_frames K <= 64 [32] of the reachable frames, evenly spaced, are sampled at every canvas pixel on the GPU
+(pwcnet_amd.background_plate): --plate_mode median [default] writes per channel the lower median of what the frames show there, so
+that what moves on its own is voted out; mean averages.  plate_count.png holds the number of frames that see each pixel (the plate
+is black where none does).  --plate_inliers lets a frame vote only where its pair's flow moves with the camera
+(pwcnet_amd.motion_residual's inliers; the last frame votes everywhere).  --plate_foreground T also writes <fname>_fg.png for
+every reachable frame, batch by batch (pwcnet_amd.plate_difference): white where the frame differs from the plate by more than T
+grey levels in some channel, black where it does not, grey 128 where the plate is unknown.  Untuned: nobody has measured the
+quality of the plate on real footage.
 """
 import argparse
 import os
@@ -142,6 +154,8 @@ def build_parser():
     add_cli_arguments(ap)
     from pwcnet_amd.temporal import add_cli_arguments as add_denoise_arguments
     add_denoise_arguments(ap)
+    from pwcnet_amd.plate import add_cli_arguments as add_plate_arguments
+    add_plate_arguments(ap)
     return ap
 
 
@@ -374,6 +388,8 @@ def main():
         ap.error(f"--motion_scale must be positive, got {args.motion_scale}")
     if args.stabilize < 0:
         ap.error(f"--stabilize must be at least 0, got {args.stabilize}")
+    from pwcnet_amd.plate import check_cli_arguments as check_plate_arguments
+    plate_on = check_plate_arguments(ap, args, len(paths))
     from pwcnet_amd.flow_filter import check_cli_arguments
     filt = check_cli_arguments(ap, args)             # filter_flow's keyword arguments, None without --flow_filter
 
@@ -425,6 +441,9 @@ def main():
     motions, motions_ok = [None] * (len(frames) - 1), [None] * (len(frames) - 1)
     if args.stabilize > 0 and any(f.shape != frames[0].shape for f in frames):
         raise ValueError("--stabilize needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
+    if plate_on and any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("--plate needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
+    plate_inliers = [None] * len(frames) if plate_on and args.plate_inliers else None
     window = 2 * max(1, args.pipeline)               # batches submitted before the first one is read back
     if both_ways:
         window = max(1, args.pipeline)               # (two forwards per batch)
@@ -479,6 +498,8 @@ def main():
                 matrices, ok, _ = pwcnet_amd.fit_motion(flow_final, model=args.motion, iters=args.motion_iters,
                                                         scale=args.motion_scale)
                 motions[i:j], motions_ok[i:j] = list(matrices.cpu().numpy()), list(ok.cpu().numpy())
+                if plate_inliers is not None:        # --plate_inliers: the masks wait on the host for the second pass
+                    plate_inliers[i:j] = list(pwcnet_amd.motion_residual(flow_final, matrices)[1].to(torch.uint8).cpu().numpy())
                 if args.motion_residual:
                     residual, inlier = pwcnet_amd.motion_residual(flow_final, matrices)
                     residual, inlier = residual.cpu().numpy(), (inlier.to(torch.uint8) * 255).cpu().numpy()
@@ -533,6 +554,33 @@ def main():
                 dname, fname = out_stem(paths[i + k])
                 os.makedirs(os.path.join(args.out, dname), exist_ok=True)
                 Image.fromarray(stab[k]).save(os.path.join(args.out, dname, fname + "_stab.png"))
+    if plate_on:                                     # the second pass: the chosen frames in one call, then every frame against it
+        from pwcnet_amd.plate import select_frames
+        H, W = frames[0].shape[:2]
+        to_frame, reach = pwcnet_amd.plate_path(np.stack(motions), np.asarray(motions_ok, bool), anchor=args.plate_anchor)
+        x0, y0, Hc, Wc = pwcnet_amd.plate_canvas(to_frame, reach, H, W, margin=args.plate_margin, max_side=args.plate_max_side)
+        to_canvas_frame, to_canvas = pwcnet_amd.canvas_matrices(to_frame, x0, y0)
+        chosen = select_frames(reach, args.plate_anchor, args.plate_frames)
+        masks = None
+        if plate_inliers is not None:
+            masks = torch.from_numpy(np.stack([np.ones((H, W), np.uint8) if plate_inliers[i] is None else plate_inliers[i]
+                                               for i in chosen])).cuda()
+        plate, count = pwcnet_amd.background_plate(torch.from_numpy(np.stack([frames[i] for i in chosen])).cuda(),
+                                                   to_canvas_frame[chosen], (Hc, Wc), mode=args.plate_mode, masks=masks)
+        os.makedirs(args.out, exist_ok=True)
+        Image.fromarray(plate.cpu().numpy()).save(os.path.join(args.out, "plate.png"))
+        Image.fromarray(count.cpu().numpy()).save(os.path.join(args.out, "plate_count.png"))
+        if args.plate_foreground is not None:
+            reachable = [int(i) for i in np.nonzero(reach)[0]]
+            for b in range(0, len(reachable), max(1, args.batch)):
+                idx = reachable[b:b + max(1, args.batch)]
+                _, fg, known = pwcnet_amd.plate_difference(torch.from_numpy(np.stack([frames[i] for i in idx])).cuda(), plate, count,
+                                                           to_canvas[idx], args.plate_foreground)
+                shown = torch.where(known, fg.to(torch.uint8) * 255, torch.full_like(fg, 128, dtype=torch.uint8)).cpu().numpy()
+                for k, i in enumerate(idx):
+                    dname, fname = out_stem(paths[i])
+                    os.makedirs(os.path.join(args.out, dname), exist_ok=True)
+                    Image.fromarray(shown[k]).save(os.path.join(args.out, dname, fname + "_fg.png"))
     print("Figure saved")
 
 

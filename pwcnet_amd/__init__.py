@@ -25,6 +25,8 @@ from . import flow_filter  # noqa: F401
 from .flow_filter import fill_flow, filter_flow, filter_tables  # noqa: F401
 from . import temporal  # noqa: F401
 from .temporal import plan_windows, temporal_filter  # noqa: F401
+from . import plate  # noqa: F401
+from .plate import background_plate, canvas_matrices, plate_canvas, plate_difference, plate_path  # noqa: F401
 from . import vis  # noqa: F401
 from .vis import flow_error_color, flow_max_radius, flow_to_color, pyramid_montage  # noqa: F401
 from .fit import FitInfo, fit_frames, fit_info, flow_any_size, refit_flow  # noqa: F401
@@ -47,4 +49,5 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "regions", "label_regions", "moving_regions",
            "region_tracks", "link_regions", "region_identities", "relabel_regions", "track_regions",
            "flow_filter", "filter_tables", "filter_flow", "fill_flow",
-           "temporal", "temporal_filter", "plan_windows"]
+           "temporal", "temporal_filter", "plan_windows",
+           "plate", "plate_path", "plate_canvas", "canvas_matrices", "background_plate", "plate_difference"]
