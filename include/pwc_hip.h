@@ -1560,6 +1560,55 @@ int pwc_plate_difference(const void* frames, int dtype, int C, const void* plate
                          int T, int H, int W, int Hc, int Wc, int min_count, double threshold, float* difference,
                          uint8_t* foreground, uint8_t* known, pwc_stream_t stream);
 
+/* ==== projective motion: the homography that explains most of a flow field, and the consumers above with a division per pixel ====
+ * (pwc_homography.hip, projective.h, the PROJ instantiations of pwc_motion.hip, the projective branch of pwc_plate.hip; launch
+ * plan, bytes and what is unmeasured in DESIGN.md 26.)  Every value is an IEEE double + - x / or a comparison in the order given
+ * here, no fused multiply-add and no library function: tests/homography_ref.py restates the fit and the position in numpy bit for
+ * bit.  Flows, valid, KNOWN, the partition of the sums, the tree, the part order and the elimination are "dominant motion"'s.
+ *
+ * POSITION of a pixel (x, y) under a 3 x 3 matrix m0 .. m8 of doubles (projective.h), the one rule of every projective consumer:
+ * the matrix is FINITE iff all nine entries are; D = ((m6 x) + (m7 y)) + m8; where D > 0 (a NaN fails) sx = (((m0 x) + (m1 y)) + m2)
+ * / D and sy = (((m3 x) + (m4 y)) + m5) / D, elsewhere there is NO POSITION.  For a last row of exactly 0 0 1, D is exactly 1 and
+ * sx, sy have the bits of the affine entry points.  A tiny positive D gives a huge or infinite position, which the in-frame
+ * comparisons of WARP and SAMPLE reject -- what keeps the corner reads inside the image.
+ *
+ * FIT (pwc_homography_fit_f64), the reweighted normalised direct linear transform.  xh, yh, cx, cy, s as in dominant motion's FIT;
+ * the target is x' = xh + (u / s), y' = yh + (v / s); the unknowns are g0 .. g7 of G = [[g0 g1 g2] [g3 g4 g5] [g6 g7 1]], the
+ * identity (g0 = g4 = 1) before pass 0 and wherever an image is DEGENERATE.  iters + 1 passes; in each, per known pixel: w = 1
+ * (pass 0); later, against the g of the pass before, D = ((g6 xh) + (g7 yh)) + 1; a pixel with !(D > 0) adds nothing to the sums of
+ * that pass (it is still counted); else rx = (((((g0 xh) + (g1 yh)) + g2) / D) - x') s, ry likewise with g3 g4 g5 and y', and
+ * w = (1 / (1 + (((rx rx) + (ry ry)) / (scale scale)))) / (D D) -- the Cauchy weight of the geometric residual in pixels times the
+ * 1 / D^2 that turns the algebraic error into the geometric one.  With wx = w xh, wy = w yh, b = {w, wx, wy, wx xh, wx yh, wy yh}
+ * and q = (x' x') + (y' y') the 23 sums are S[j] += b[j], S[6 + j] += b[j] x', S[12 + j] += b[j] y' (j = 0 .. 5) and S[17 + j] +=
+ * b[j] q (j = 1 .. 5), plus the integer count of known pixels.  One lane per image adds the parts and solves, unknowns in the order
+ * (g2 g0 g1 g5 g3 g4 g6 g7), the lower triangle
+ *   [S0] [S1 S3] [S2 S4 S5] [0 0 0 S0] [0 0 0 S1 S3] [0 0 0 S2 S4 S5] [-S7 -S9 -S10 -S13 -S15 -S16 S20] [-S8 -S10 -S11 -S14 -S16 -S17 S21 S22]
+ * with the right-hand side (S6 S7 S8 S12 S13 S14 -S18 -S19), by dominant motion's L D L^T elimination, pivot rule d > 1e-9 S0.
+ * DEGENERATE: a count below 4 or a failed pivot; final, as there.  The last pass writes M = T^-1 G T: a_i = (h_i0 / s, h_i1 / s,
+ * h_i2 - (((h_i0 cx) + (h_i1 cy)) / s)) for the three rows h_i of G; e0j = (s a_0j) + (cx a_2j), e1j = (s a_1j) + (cy a_2j), e2j =
+ * a_2j; m = e / e22, all nine.  ok = 0 and the identity where the image is degenerate, e22 is not > 0, an m is not finite, or
+ * ((m6 x) + (m7 y)) + 1 is not > 0 at one of the corners (0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1) -- the horizon would cross
+ * the frame.  Outputs, workspace, launches and checks as pwc_motion_fit_f64's, without a model; 23 x 256 doubles and 256 ints of LDS.
+ *
+ * pwc_motion_residual_projective_f32, pwc_warp_projective, pwc_plate_build_projective, pwc_plate_difference_projective: the entry
+ * points of the same names without "_projective" (pwc_warp_affine for the warp), argument for argument and check for check, with
+ * "affine and finite" replaced by FINITE and the sums sx, sy replaced by POSITION.  Where there is no position the residual is
+ * the sentinel and no inlier, the warp is not covered, the plate has no sample, the difference is not known. */
+size_t pwc_homography_fit_workspace_bytes(int N, int H, int W);
+int pwc_homography_fit_f64(const float* flows, int flow_cs, const uint8_t* valid, int N, int H, int W, int iters, double scale,
+                           void* workspace, size_t workspace_bytes, double* matrices, uint8_t* ok, int32_t* count,
+                           double* weight_sum, pwc_stream_t stream);
+int pwc_motion_residual_projective_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N, int H,
+                                       int W, double threshold, float* residual, uint8_t* inlier, pwc_stream_t stream);
+int pwc_warp_projective(const void* frames, int dtype, int C, const double* matrices, int N, int H, int W, void* out,
+                        uint8_t* covered, pwc_stream_t stream);
+int pwc_plate_build_projective(const void* frames, int dtype, int C, const double* matrices, const uint8_t* use,
+                               const uint8_t* masks, int T, int H, int W, int Hc, int Wc, int mode, int min_count, void* plate,
+                               uint8_t* count, pwc_stream_t stream);
+int pwc_plate_difference_projective(const void* frames, int dtype, int C, const void* plate, const uint8_t* count,
+                                    const double* matrices, int T, int H, int W, int Hc, int Wc, int min_count, double threshold,
+                                    float* difference, uint8_t* foreground, uint8_t* known, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,9 @@ call per batch; the reversed pairs are run as --track_fb runs them; after the re
 pictures come back to the host.  --interp_alpha A is the weight of the photometric match (exp(-A e)) [20].
 --motion MODEL also writes <out>/motion.npy (pairs, 3, 3) float64 and <out>/motion_ok.npy (pairs,) bool: the dominant motion of
 every pair, a translation, similarity or affine matrix taking a pixel (x, y, 1) of frame i to frame i + 1, fitted robustly on the
-GPU (pwcnet_amd.fit_motion, one call per batch; after the refit where --fit is not crop).  --motion_iters K and --motion_scale C
+GPU (pwcnet_amd.fit_motion, one call per batch; after the refit where --fit is not crop; --motion homography: the eight-parameter
+pwcnet_amd.fit_homography, and --motion_residual, --stabilize, --regions, --regions_track and --plate with --plate_foreground then
+call their ops with projective=True, a division per pixel).  --motion_iters K and --motion_scale C
 are the reweighting passes [4] and the Cauchy scale in pixels [1.0].  --motion_residual also writes <fname>_residual.flo, the flow
 with that motion taken out (unknown pixels hold the .flo sentinel), and <fname>_inlier.png, white where a pixel moves with it.
 --stabilize R (needs --motion and frames of one size) smooths the camera path over 2 R + 1 frames (pwcnet_amd.smooth_path) and, in
@@ -128,8 +130,9 @@ def build_parser():
                          "interpolated on the GPU from the two flows between them (the reversed pairs are run too) [off]")
     ap.add_argument("--interp_alpha", type=float, default=20.0, metavar="A",
                     help="--interp: the weight of a source pixel is exp(-min(A * e, 10)), e its match's mean colour error [20]")
-    ap.add_argument("--motion", choices=("translation", "similarity", "affine"), default=None,
-                    help="also write motion.npy / motion_ok.npy: the dominant motion of every pair, fitted robustly on the GPU [off]")
+    ap.add_argument("--motion", choices=("translation", "similarity", "affine", "homography"), default=None,
+                    help="also write motion.npy / motion_ok.npy: the dominant motion of every pair, fitted robustly on the GPU; "
+                         "homography: pwcnet_amd.fit_homography, and every flag below that uses the motion divides per pixel [off]")
     ap.add_argument("--motion_iters", type=int, default=4, metavar="K", help="--motion: reweighting passes, 0 .. 64 [4]")
     ap.add_argument("--motion_scale", type=float, default=1.0, metavar="C", help="--motion: the Cauchy scale in pixels [1.0]")
     ap.add_argument("--motion_residual", action="store_true",
@@ -439,6 +442,7 @@ def main():
     if args.regions_track:
         region_tracker = RegionTracker(paths, args.out, args.regions_track_overlap, args.regions_track_fraction)
     motions, motions_ok = [None] * (len(frames) - 1), [None] * (len(frames) - 1)
+    proj = {"projective": True} if args.motion == "homography" else {}       # the other models: the calls as they were
     if args.stabilize > 0 and any(f.shape != frames[0].shape for f in frames):
         raise ValueError("--stabilize needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
     if plate_on and any(f.shape != frames[0].shape for f in frames):
@@ -495,13 +499,16 @@ def main():
             if denoiser is not None:                 # only the uint8 pictures cross to the host
                 denoiser.add(i, pictures, flow_final, flow_back)
             if args.motion is not None:              # one call per batch; matrices, flags and uint8 pictures cross to the host
-                matrices, ok, _ = pwcnet_amd.fit_motion(flow_final, model=args.motion, iters=args.motion_iters,
-                                                        scale=args.motion_scale)
+                if args.motion == "homography":
+                    matrices, ok, _ = pwcnet_amd.fit_homography(flow_final, iters=args.motion_iters, scale=args.motion_scale)
+                else:
+                    matrices, ok, _ = pwcnet_amd.fit_motion(flow_final, model=args.motion, iters=args.motion_iters,
+                                                            scale=args.motion_scale)
                 motions[i:j], motions_ok[i:j] = list(matrices.cpu().numpy()), list(ok.cpu().numpy())
                 if plate_inliers is not None:        # --plate_inliers: the masks wait on the host for the second pass
-                    plate_inliers[i:j] = list(pwcnet_amd.motion_residual(flow_final, matrices)[1].to(torch.uint8).cpu().numpy())
+                    plate_inliers[i:j] = list(pwcnet_amd.motion_residual(flow_final, matrices, **proj)[1].to(torch.uint8).cpu().numpy())
                 if args.motion_residual:
-                    residual, inlier = pwcnet_amd.motion_residual(flow_final, matrices)
+                    residual, inlier = pwcnet_amd.motion_residual(flow_final, matrices, **proj)
                     residual, inlier = residual.cpu().numpy(), (inlier.to(torch.uint8) * 255).cpu().numpy()
                     for k in range(j - i):
                         dname, fname = out_stem(paths[i + k])
@@ -511,7 +518,7 @@ def main():
                 if args.regions:                     # the ids and the tables cross to the host, nothing else
                     labels, count, regions = pwcnet_amd.moving_regions(
                         flow_final, matrices, threshold=args.regions_threshold, connectivity=args.regions_connectivity,
-                        min_area=args.regions_min_area, max_regions=REGIONS_ROWS)[:3]
+                        min_area=args.regions_min_area, max_regions=REGIONS_ROWS, **proj)[:3]
                     if region_tracker is not None:   # (before the host copies below take the names)
                         region_tracker.add(i, labels, count, regions, flow_final)
                     labels, count = labels.clamp(max=65535).cpu().numpy().astype(np.uint16), count.cpu().numpy()
@@ -546,10 +553,10 @@ def main():
         np.save(os.path.join(args.out, "motion.npy"), np.stack(motions))
         np.save(os.path.join(args.out, "motion_ok.npy"), np.asarray(motions_ok, bool))
     if args.stabilize > 0:                           # the second pass: the frames again, batch by batch
-        steady = pwcnet_amd.smooth_path(np.stack(motions), args.stabilize)
+        steady = pwcnet_amd.smooth_path(np.stack(motions), args.stabilize, **proj)
         for i in range(0, len(frames), max(1, args.batch)):
             j = min(i + max(1, args.batch), len(frames))
-            stab = pwcnet_amd.warp_frames(torch.from_numpy(np.stack(frames[i:j])).cuda(), steady[i:j])[0].cpu().numpy()
+            stab = pwcnet_amd.warp_frames(torch.from_numpy(np.stack(frames[i:j])).cuda(), steady[i:j], **proj)[0].cpu().numpy()
             for k in range(j - i):
                 dname, fname = out_stem(paths[i + k])
                 os.makedirs(os.path.join(args.out, dname), exist_ok=True)
@@ -557,16 +564,16 @@ def main():
     if plate_on:                                     # the second pass: the chosen frames in one call, then every frame against it
         from pwcnet_amd.plate import select_frames
         H, W = frames[0].shape[:2]
-        to_frame, reach = pwcnet_amd.plate_path(np.stack(motions), np.asarray(motions_ok, bool), anchor=args.plate_anchor)
-        x0, y0, Hc, Wc = pwcnet_amd.plate_canvas(to_frame, reach, H, W, margin=args.plate_margin, max_side=args.plate_max_side)
-        to_canvas_frame, to_canvas = pwcnet_amd.canvas_matrices(to_frame, x0, y0)
+        to_frame, reach = pwcnet_amd.plate_path(np.stack(motions), np.asarray(motions_ok, bool), anchor=args.plate_anchor, **proj)
+        x0, y0, Hc, Wc = pwcnet_amd.plate_canvas(to_frame, reach, H, W, margin=args.plate_margin, max_side=args.plate_max_side, **proj)
+        to_canvas_frame, to_canvas = pwcnet_amd.canvas_matrices(to_frame, x0, y0, **proj)
         chosen = select_frames(reach, args.plate_anchor, args.plate_frames)
         masks = None
         if plate_inliers is not None:
             masks = torch.from_numpy(np.stack([np.ones((H, W), np.uint8) if plate_inliers[i] is None else plate_inliers[i]
                                                for i in chosen])).cuda()
         plate, count = pwcnet_amd.background_plate(torch.from_numpy(np.stack([frames[i] for i in chosen])).cuda(),
-                                                   to_canvas_frame[chosen], (Hc, Wc), mode=args.plate_mode, masks=masks)
+                                                   to_canvas_frame[chosen], (Hc, Wc), mode=args.plate_mode, masks=masks, **proj)
         os.makedirs(args.out, exist_ok=True)
         Image.fromarray(plate.cpu().numpy()).save(os.path.join(args.out, "plate.png"))
         Image.fromarray(count.cpu().numpy()).save(os.path.join(args.out, "plate_count.png"))
@@ -575,7 +582,7 @@ def main():
             for b in range(0, len(reachable), max(1, args.batch)):
                 idx = reachable[b:b + max(1, args.batch)]
                 _, fg, known = pwcnet_amd.plate_difference(torch.from_numpy(np.stack([frames[i] for i in idx])).cuda(), plate, count,
-                                                           to_canvas[idx], args.plate_foreground)
+                                                           to_canvas[idx], args.plate_foreground, **proj)
                 shown = torch.where(known, fg.to(torch.uint8) * 255, torch.full_like(fg, 128, dtype=torch.uint8)).cpu().numpy()
                 for k, i in enumerate(idx):
                     dname, fname = out_stem(paths[i])

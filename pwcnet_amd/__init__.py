@@ -17,6 +17,8 @@ from . import interp  # noqa: F401
 from .interp import interpolate_frames  # noqa: F401
 from . import motion  # noqa: F401
 from .motion import fit_motion, motion_residual, smooth_path, warp_frames  # noqa: F401
+from . import homography  # noqa: F401
+from .homography import fit_homography  # noqa: F401
 from . import regions  # noqa: F401
 from .regions import label_regions, moving_regions  # noqa: F401
 from . import region_tracks  # noqa: F401
@@ -45,7 +47,7 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "compose_flows", "compose_grad", "chain_flows", "vis", "flow_max_radius", "flow_to_color", "flow_error_color", "pyramid_montage",
            "track", "track_points", "grid_points",
            "interp", "interpolate_frames",
-           "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path",
+           "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path", "homography", "fit_homography",
            "regions", "label_regions", "moving_regions",
            "region_tracks", "link_regions", "region_identities", "relabel_regions", "track_regions",
            "flow_filter", "filter_tables", "filter_flow", "fill_flow",

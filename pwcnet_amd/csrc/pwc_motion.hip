@@ -6,6 +6,8 @@
 //   pwc_motion_fit_f64               matrices (N, 3, 3) doubles, ok (N) bytes, count (N) int32, weight_sum (N) doubles
 //   pwc_motion_residual_f32          residual (N, H, W, 2) floats and inlier (N, H, W) bytes
 //   pwc_warp_affine                  out (N, H, W, C) in the frames' dtype and covered (N, H, W) bytes
+//   pwc_motion_residual_projective_f32, pwc_warp_projective   the same two with projective.h's position: all nine entries finite,
+//                                    a division per pixel, nothing where D is not positive (the PROJ instantiations below)
 //
 // The fit is iters + 1 passes of two launches each, all on the caller's stream, the device reading what the pass before wrote:
 //   sums    grid (parts, N), loss_common.h's partition: part b takes the pixels b 256 + t, + parts 256, ... of its image.  A known
@@ -26,6 +28,8 @@
 // Flows at any channel stride >= 2: where the pointers of a call are on an 8-byte boundary and the stride is even a record's two
 // floats are one 8-byte access, else two 4-byte ones -- the values, and so every bit, are the same (pwc_track.hip's arrangement).
 #include "loss_common.h"
+#include "motion_ldlt.h"
+#include "projective.h"
 
 #pragma clang fp contract(off)
 
@@ -106,48 +110,7 @@ __global__ __launch_bounds__(256) void motion_sums_kernel(const MotionFitArgs a)
     }
 }
 
-// L D L^T elimination of the symmetric K x K system A (lower triangle read) with R right-hand sides, no pivoting:
-//   column j:  t_ij = A_ij - l_i0 t_j0 - ... - l_i,j-1 t_j,j-1 (left to right), i = j .. K - 1;  d_j = t_jj;  l_ij = t_ij / d_j
-//   per side:  z_i = r_i - l_i0 z_0 - ... - l_i,i-1 z_i-1;  y_i = z_i / d_i;  x_i = y_i - l_i+1,i x_i+1 - ... - l_K-1,i x_K-1
-// false where a pivot fails d_j > tol (a NaN fails); the solutions overwrite r.
-template <int K, int R>
-__device__ __forceinline__ bool motion_ldlt(const double (&A)[K][K], double (&r)[R][K], double tol) {
-    double t[K][K], l[K][K], d[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-#pragma unroll
-        for (int i = j; i < K; ++i) {
-            double v = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v = v - (l[i][k] * t[j][k]);
-            t[i][j] = v;
-        }
-        d[j] = t[j][j];
-        if (!(d[j] > tol)) return false;
-#pragma unroll
-        for (int i = j + 1; i < K; ++i) l[i][j] = t[i][j] / d[j];
-    }
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-        double z[K];
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            double v = r[q][i];
-#pragma unroll
-            for (int k = 0; k < i; ++k) v = v - (l[i][k] * z[k]);
-            z[i] = v;
-        }
-#pragma unroll
-        for (int i = K - 1; i >= 0; --i) {
-            double v = z[i] / d[i];
-#pragma unroll
-            for (int k = i + 1; k < K; ++k) v = v - (l[k][i] * r[q][k]);
-            r[q][i] = v;
-        }
-    }
-    return true;
-}
-
+// (motion_ldlt: motion_ldlt.h, shared with pwc_homography.hip.)
 // One lane per image.
 __global__ __launch_bounds__(64) void motion_solve_kernel(const MotionFitArgs a) {
     const int n = blockIdx.x * 64 + threadIdx.x;
@@ -219,24 +182,35 @@ __device__ __forceinline__ bool motion_affine(const double* m, double* e) {
     return good;
 }
 
-// One lane per pixel of the batch.
-template <bool VEC>
+// One lane per pixel of the batch.  PROJ: the matrices are projective (projective.h's rule) -- all nine entries finite, the
+// position with the division, no residual where there is no position.
+template <bool VEC, bool PROJ>
 __global__ __launch_bounds__(256) void motion_residual_kernel(const MotionResidualArgs a) {
     const long npix = (long)a.N * a.H * a.W;
     for (long g = blockIdx.x * 256L + threadIdx.x; g < npix; g += (long)gridDim.x * 256) {
         const PwcLossPixel q = pwc_loss_pixel(g, a.H, a.W);
         float r0 = MOTION_SENTINEL, r1 = MOTION_SENTINEL;
         uint8_t in = 0;
-        double m[6];
-        if (motion_affine(a.matrices + (size_t)q.n * 9, m) && !(a.valid && !a.valid[g])) {
+        double m[PROJ ? 9 : 6];
+        const bool good = PROJ ? pwc_projective_finite(a.matrices + (size_t)q.n * 9, m) : motion_affine(a.matrices + (size_t)q.n * 9, m);
+        if (good && !(a.valid && !a.valid[g])) {
             float fu, fv;
             motion_load2<VEC>(a.flow + (size_t)g * a.cs, fu, fv);
             if (motion_known(fu, fv)) {
                 const double x = (double)q.x, y = (double)q.y;
-                const double mu = (((m[0] * x) + (m[1] * y)) + m[2]) - x, mv = (((m[3] * x) + (m[4] * y)) + m[5]) - y;
-                const double ru = (double)fu - mu, rv = (double)fv - mv;
-                r0 = (float)ru; r1 = (float)rv;
-                in = ((ru * ru) + (rv * rv)) <= a.thr2 ? 1 : 0;
+                double sx, sy;
+                bool there = true;
+                if (PROJ) {
+                    there = pwc_projective_position(m, x, y, sx, sy);
+                } else {
+                    sx = ((m[0] * x) + (m[1] * y)) + m[2]; sy = ((m[3] * x) + (m[4] * y)) + m[5];
+                }
+                if (there) {
+                    const double mu = sx - x, mv = sy - y;
+                    const double ru = (double)fu - mu, rv = (double)fv - mv;
+                    r0 = (float)ru; r1 = (float)rv;
+                    in = ((ru * ru) + (rv * rv)) <= a.thr2 ? 1 : 0;
+                }
             }
         }
         if (VEC) {
@@ -265,13 +239,19 @@ __device__ __forceinline__ unsigned motion_byte(double v) {
 }
 
 // Output pixel g: its C channels as doubles (pwc_fb_valid_u8's sample of the source position); false where it is not covered.
-template <bool U8, int C>
+// PROJ: projective.h's rule in place of the affine one.
+template <bool U8, int C, bool PROJ>
 __device__ __forceinline__ bool motion_warp_pixel(const MotionWarpArgs& a, long g, double* v) {
     const PwcLossPixel q = pwc_loss_pixel(g, a.H, a.W);
-    double m[6];
-    if (!motion_affine(a.matrices + (size_t)q.n * 9, m)) return false;
+    double m[PROJ ? 9 : 6];
+    if (!(PROJ ? pwc_projective_finite(a.matrices + (size_t)q.n * 9, m) : motion_affine(a.matrices + (size_t)q.n * 9, m))) return false;
     const double x = (double)q.x, y = (double)q.y;
-    const double sx = ((m[0] * x) + (m[1] * y)) + m[2], sy = ((m[3] * x) + (m[4] * y)) + m[5];
+    double sx, sy;
+    if (PROJ) {
+        if (!pwc_projective_position(m, x, y, sx, sy)) return false;
+    } else {
+        sx = ((m[0] * x) + (m[1] * y)) + m[2]; sy = ((m[3] * x) + (m[4] * y)) + m[5];
+    }
     // (every comparison is false for a NaN; an Inf fails one of them) -- what keeps the four corner reads inside image n
     if (!(sx >= 0.0 && sx <= (double)(a.W - 1) && sy >= 0.0 && sy <= (double)(a.H - 1))) return false;
     const double fx0 = floor(sx), fy0 = floor(sy);
@@ -298,7 +278,7 @@ __device__ __forceinline__ bool motion_warp_pixel(const MotionWarpArgs& a, long 
 }
 
 // One lane per run of four output pixels of the flat (N, H, W) index: 4 C bytes (C dwords) or 4 C floats (C 16-byte stores).
-template <bool U8, int C>
+template <bool U8, int C, bool PROJ>
 __global__ __launch_bounds__(256) void motion_warp_kernel(const MotionWarpArgs a) {
     const long total = (long)a.N * a.H * a.W;
     const long runs = (total + 3) / 4;
@@ -310,7 +290,7 @@ __global__ __launch_bounds__(256) void motion_warp_kernel(const MotionWarpArgs a
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             double v[C];
-            const bool ok = g0 + i < total && motion_warp_pixel<U8, C>(a, g0 + i, v);
+            const bool ok = g0 + i < total && motion_warp_pixel<U8, C, PROJ>(a, g0 + i, v);
             cov |= (ok ? 1u : 0u) << (8 * i);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -390,8 +370,8 @@ extern "C" int pwc_motion_fit_f64(const float* flows, int flow_cs, const uint8_t
     return pwc_launch_status();
 }
 
-extern "C" int pwc_motion_residual_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N, int H,
-                                       int W, double threshold, float* residual, uint8_t* inlier, pwc_stream_t stream) {
+static int motion_residual_call(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N, int H, int W,
+                                double threshold, float* residual, uint8_t* inlier, bool projective, pwc_stream_t stream) {
     if (!flows || !matrices || !residual || !inlier) return PWC_EINVAL;
     if (N < 1 || H < 1 || W < 1 || flow_cs < 2 || !(threshold >= 0.0)) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
@@ -402,21 +382,38 @@ extern "C" int pwc_motion_residual_f32(const float* flows, int flow_cs, const ui
     const bool vec = !(flow_cs & 1) && !motion_off(flows, 7u) && !motion_off(residual, 7u);
     const long blocks = ((long)N * H * W + 255) / 256;
     const dim3 grid((unsigned)(blocks > MOTION_MAX_BLOCKS ? MOTION_MAX_BLOCKS : blocks));
-    if (vec) hipLaunchKernelGGL(motion_residual_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(motion_residual_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    const hipStream_t s = (hipStream_t)stream;
+    if (projective) {
+        if (vec) hipLaunchKernelGGL((motion_residual_kernel<true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((motion_residual_kernel<false, true>), grid, dim3(256), 0, s, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((motion_residual_kernel<true, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((motion_residual_kernel<false, false>), grid, dim3(256), 0, s, a);
+    }
     return pwc_launch_status();
 }
 
-template <bool U8>
-static void motion_warp_launch(int C, dim3 grid, hipStream_t s, const MotionWarpArgs& a) {
-    if (C == 1) hipLaunchKernelGGL((motion_warp_kernel<U8, 1>), grid, dim3(256), 0, s, a);
-    else if (C == 2) hipLaunchKernelGGL((motion_warp_kernel<U8, 2>), grid, dim3(256), 0, s, a);
-    else if (C == 3) hipLaunchKernelGGL((motion_warp_kernel<U8, 3>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((motion_warp_kernel<U8, 4>), grid, dim3(256), 0, s, a);
+extern "C" int pwc_motion_residual_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N, int H,
+                                       int W, double threshold, float* residual, uint8_t* inlier, pwc_stream_t stream) {
+    return motion_residual_call(flows, flow_cs, valid, matrices, N, H, W, threshold, residual, inlier, false, stream);
 }
 
-extern "C" int pwc_warp_affine(const void* frames, int dtype, int C, const double* matrices, int N, int H, int W, void* out,
-                               uint8_t* covered, pwc_stream_t stream) {
+extern "C" int pwc_motion_residual_projective_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N,
+                                                  int H, int W, double threshold, float* residual, uint8_t* inlier,
+                                                  pwc_stream_t stream) {
+    return motion_residual_call(flows, flow_cs, valid, matrices, N, H, W, threshold, residual, inlier, true, stream);
+}
+
+template <bool U8, bool PROJ>
+static void motion_warp_launch(int C, dim3 grid, hipStream_t s, const MotionWarpArgs& a) {
+    if (C == 1) hipLaunchKernelGGL((motion_warp_kernel<U8, 1, PROJ>), grid, dim3(256), 0, s, a);
+    else if (C == 2) hipLaunchKernelGGL((motion_warp_kernel<U8, 2, PROJ>), grid, dim3(256), 0, s, a);
+    else if (C == 3) hipLaunchKernelGGL((motion_warp_kernel<U8, 3, PROJ>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((motion_warp_kernel<U8, 4, PROJ>), grid, dim3(256), 0, s, a);
+}
+
+static int motion_warp_call(const void* frames, int dtype, int C, const double* matrices, int N, int H, int W, void* out,
+                            uint8_t* covered, bool projective, pwc_stream_t stream) {
     if (!frames || !matrices || !out || !covered) return PWC_EINVAL;
     if (N < 1 || H < 1 || W < 1 || C < 1 || C > 4 || (dtype != PWC_MOTION_U8 && dtype != PWC_MOTION_F32)) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
@@ -428,7 +425,22 @@ extern "C" int pwc_warp_affine(const void* frames, int dtype, int C, const doubl
     a.covered_vec = motion_off(covered, 3u) ? 0 : 1;
     const long blocks = (((long)N * H * W + 3) / 4 + 255) / 256;
     const dim3 grid((unsigned)(blocks > MOTION_MAX_BLOCKS ? MOTION_MAX_BLOCKS : blocks));
-    if (u8) motion_warp_launch<true>(C, grid, (hipStream_t)stream, a);
-    else motion_warp_launch<false>(C, grid, (hipStream_t)stream, a);
+    if (projective) {
+        if (u8) motion_warp_launch<true, true>(C, grid, (hipStream_t)stream, a);
+        else motion_warp_launch<false, true>(C, grid, (hipStream_t)stream, a);
+    } else {
+        if (u8) motion_warp_launch<true, false>(C, grid, (hipStream_t)stream, a);
+        else motion_warp_launch<false, false>(C, grid, (hipStream_t)stream, a);
+    }
     return pwc_launch_status();
+}
+
+extern "C" int pwc_warp_affine(const void* frames, int dtype, int C, const double* matrices, int N, int H, int W, void* out,
+                               uint8_t* covered, pwc_stream_t stream) {
+    return motion_warp_call(frames, dtype, C, matrices, N, H, W, out, covered, false, stream);
+}
+
+extern "C" int pwc_warp_projective(const void* frames, int dtype, int C, const double* matrices, int N, int H, int W, void* out,
+                                   uint8_t* covered, pwc_stream_t stream) {
+    return motion_warp_call(frames, dtype, C, matrices, N, H, W, out, covered, true, stream);
 }

@@ -20,6 +20,7 @@
 // formed anywhere in this file (the pragma below) -- so tests/plate_ref.py restates it in numpy bit for bit.  No atomics, no
 // workspace, no scratch, no host synchronisation, no process-wide state; frame offsets are 64-bit.
 #include "pwc_common.h"
+#include "projective.h"
 
 #pragma clang fp contract(off)
 
@@ -32,11 +33,14 @@
 __device__ __forceinline__ bool plate_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // (false for a NaN)
 __device__ __forceinline__ bool plate_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
 
-// WARP's rule (pwc_motion.hip's motion_affine): last row exactly 0 0 1, first two rows finite; e: the first two rows.
-__device__ __forceinline__ bool plate_affine(const double* m, double* e) {
+// WARP's rule (pwc_motion.hip's motion_affine): last row exactly 0 0 1, first two rows finite; e: the matrix (the last row is
+// read by the projective branch only).  projective (uniform in the workgroup): projective.h's rule, all nine entries finite.
+__device__ __forceinline__ bool plate_affine(const double* m, double* e, int projective) {
+    if (projective) return pwc_projective_finite(m, e);
     bool good = m[6] == 0.0 && m[7] == 0.0 && m[8] == 1.0;
 #pragma unroll
     for (int j = 0; j < 6; ++j) { e[j] = m[j]; good = good && plate_finite(e[j]); }
+    e[6] = 0.0; e[7] = 0.0; e[8] = 1.0;
     return good;
 }
 
@@ -57,9 +61,14 @@ struct PlateCorners {
     size_t o00, o01, o10, o11;
     double wx0, wx1, wy0, wy1;
 };
-__device__ __forceinline__ bool plate_corners(const double* m, int px, int py, int H, int W, PlateCorners& k) {
+__device__ __forceinline__ bool plate_corners(const double* m, int px, int py, int H, int W, PlateCorners& k, int projective) {
     const double x = (double)px, y = (double)py;
-    const double sx = ((m[0] * x) + (m[1] * y)) + m[2], sy = ((m[3] * x) + (m[4] * y)) + m[5];
+    double sx, sy;
+    if (projective) {                                                      // (uniform in the workgroup)
+        if (!pwc_projective_position(m, x, y, sx, sy)) return false;
+    } else {
+        sx = ((m[0] * x) + (m[1] * y)) + m[2]; sy = ((m[3] * x) + (m[4] * y)) + m[5];
+    }
     if (!(sx >= 0.0 && sx <= (double)(W - 1) && sy >= 0.0 && sy <= (double)(H - 1))) return false;
     const double fx0 = floor(sx), fy0 = floor(sy);
     const int x0 = (int)fx0, y0 = (int)fy0;
@@ -97,6 +106,7 @@ struct PlateBuildArgs {
     void* plate;              // [Hc][Wc][C]
     uint8_t* count;           // [Hc][Wc]
     int T, H, W, Hc, Wc, min_count;
+    int projective;           // the matrices are projective (projective.h); 0: affine, the last row exactly 0 0 1
 };
 
 template <bool U8, int C>
@@ -124,11 +134,11 @@ __global__ __launch_bounds__(256) void plate_build_kernel(const PlateBuildArgs a
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = 0.0;
         for (int t = 0; t < a.T; ++t) {
-            double m[6];
-            if ((a.use && !a.use[t]) || !plate_affine(a.matrices + 9 * t, m)) continue;     // (uniform in the workgroup)
+            double m[9];
+            if ((a.use && !a.use[t]) || !plate_affine(a.matrices + 9 * t, m, a.projective)) continue;     // (uniform in the workgroup)
             ++used;
             PlateCorners k;
-            if (!plate_corners(m, px, py, a.H, a.W, k)) continue;
+            if (!plate_corners(m, px, py, a.H, a.W, k, a.projective)) continue;
             const size_t img = (size_t)t * plane;
             if (a.masks) {
                 const uint8_t* mk = a.masks + img;
@@ -189,11 +199,11 @@ __global__ __launch_bounds__(256) void plate_build_kernel(const PlateBuildArgs a
                     int j = 0;
                     for (int t = 0; t < a.T; ++t) {
                         if (!((present >> t) & 1ull)) continue;
-                        double m[6];
+                        double m[9];
                         PlateCorners k;
                         bool fin = true;
-                        plate_affine(a.matrices + 9 * t, m);
-                        plate_corners(m, px, py, a.H, a.W, k);             // (true: the sample is PRESENT)
+                        plate_affine(a.matrices + 9 * t, m, a.projective);
+                        plate_corners(m, px, py, a.H, a.W, k, a.projective);   // (true: the sample is PRESENT)
                         const double v = plate_blend<false>(a.frames, (size_t)t * plane, C, c, k, &fin);
                         mine[256 * j] = plate_key(__float_as_uint((float)v));
                         ++j;
@@ -225,6 +235,7 @@ struct PlateDiffArgs {
     uint8_t* known;           // [T][H][W]
     double threshold;
     int T, H, W, Hc, Wc, min_count;
+    int projective;           // the matrices are projective (projective.h); 0: affine, the last row exactly 0 0 1
 };
 
 template <bool U8, int C>
@@ -234,9 +245,9 @@ __global__ __launch_bounds__(256) void plate_difference_kernel(const PlateDiffAr
         const int t = (int)(g / plane);
         const long r = g - (long)t * plane;
         const int y = (int)(r / a.W), x = (int)(r - (long)y * a.W);
-        double m[6], d = 0.0;
+        double m[9], d = 0.0;
         PlateCorners k;
-        bool ok = plate_affine(a.matrices + 9 * t, m) && plate_corners(m, x, y, a.Hc, a.Wc, k);
+        bool ok = plate_affine(a.matrices + 9 * t, m, a.projective) && plate_corners(m, x, y, a.Hc, a.Wc, k, a.projective);
         ok = ok && (int)a.count[k.o00] >= a.min_count && (int)a.count[k.o01] >= a.min_count && (int)a.count[k.o10] >= a.min_count &&
              (int)a.count[k.o11] >= a.min_count;
         if (ok) {
@@ -280,9 +291,9 @@ static void plate_build_channels(int C, int mean, dim3 grid, size_t lds, hipStre
     else plate_build_launch<U8, 4>(mean, grid, lds, s, a);
 }
 
-extern "C" int pwc_plate_build(const void* frames, int dtype, int C, const double* matrices, const uint8_t* use, const uint8_t* masks,
-                               int T, int H, int W, int Hc, int Wc, int mode, int min_count, void* plate, uint8_t* count,
-                               pwc_stream_t stream) {
+static int plate_build_call(const void* frames, int dtype, int C, const double* matrices, const uint8_t* use, const uint8_t* masks,
+                            int T, int H, int W, int Hc, int Wc, int mode, int min_count, void* plate, uint8_t* count, int projective,
+                            pwc_stream_t stream) {
     if (!frames || !matrices || !plate || !count) return PWC_EINVAL;
     if (T < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1 || T > PWC_PLATE_MAX_FRAMES || C < 1 || C > 4) return PWC_EINVAL;
     if ((dtype != PWC_MOTION_U8 && dtype != PWC_MOTION_F32) || (mode != PWC_PLATE_MEDIAN && mode != PWC_PLATE_MEAN) || min_count < 1)
@@ -292,13 +303,25 @@ extern "C" int pwc_plate_build(const void* frames, int dtype, int C, const doubl
     if (plate_off(matrices, 7u) || (!u8 && (plate_off(frames, 3u) || plate_off(plate, 3u)))) return PWC_EALIGN;
     PlateBuildArgs a = {};
     a.frames = frames; a.matrices = matrices; a.use = use; a.masks = masks; a.plate = plate; a.count = count;
-    a.T = T; a.H = H; a.W = W; a.Hc = Hc; a.Wc = Wc; a.min_count = min_count;
+    a.T = T; a.H = H; a.W = W; a.Hc = Hc; a.Wc = Wc; a.min_count = min_count; a.projective = projective;
     const long tiles = (((long)Wc + PLATE_TILE_W - 1) / PLATE_TILE_W) * (((long)Hc + PLATE_TILE_H - 1) / PLATE_TILE_H);
     const dim3 grid((unsigned)(tiles > PLATE_MAX_TILES ? PLATE_MAX_TILES : tiles));
     const size_t lds = (size_t)T * 256 * sizeof(unsigned);                 // <= 64 KB
     if (u8) plate_build_channels<true>(C, mode == PWC_PLATE_MEAN, grid, lds, (hipStream_t)stream, a);
     else plate_build_channels<false>(C, mode == PWC_PLATE_MEAN, grid, lds, (hipStream_t)stream, a);
     return pwc_launch_status();
+}
+
+extern "C" int pwc_plate_build(const void* frames, int dtype, int C, const double* matrices, const uint8_t* use, const uint8_t* masks,
+                               int T, int H, int W, int Hc, int Wc, int mode, int min_count, void* plate, uint8_t* count,
+                               pwc_stream_t stream) {
+    return plate_build_call(frames, dtype, C, matrices, use, masks, T, H, W, Hc, Wc, mode, min_count, plate, count, 0, stream);
+}
+
+extern "C" int pwc_plate_build_projective(const void* frames, int dtype, int C, const double* matrices, const uint8_t* use,
+                                          const uint8_t* masks, int T, int H, int W, int Hc, int Wc, int mode, int min_count, void* plate,
+                                          uint8_t* count, pwc_stream_t stream) {
+    return plate_build_call(frames, dtype, C, matrices, use, masks, T, H, W, Hc, Wc, mode, min_count, plate, count, 1, stream);
 }
 
 template <bool U8>
@@ -309,9 +332,9 @@ static void plate_difference_launch(int C, dim3 grid, hipStream_t s, const Plate
     else hipLaunchKernelGGL((plate_difference_kernel<U8, 4>), grid, dim3(256), 0, s, a);
 }
 
-extern "C" int pwc_plate_difference(const void* frames, int dtype, int C, const void* plate, const uint8_t* count,
-                                    const double* matrices, int T, int H, int W, int Hc, int Wc, int min_count, double threshold,
-                                    float* difference, uint8_t* foreground, uint8_t* known, pwc_stream_t stream) {
+static int plate_difference_call(const void* frames, int dtype, int C, const void* plate, const uint8_t* count,
+                                 const double* matrices, int T, int H, int W, int Hc, int Wc, int min_count, double threshold,
+                                 float* difference, uint8_t* foreground, uint8_t* known, int projective, pwc_stream_t stream) {
     if (!frames || !plate || !count || !matrices || !difference || !foreground || !known) return PWC_EINVAL;
     if (T < 1 || H < 1 || W < 1 || Hc < 1 || Wc < 1 || C < 1 || C > 4) return PWC_EINVAL;
     if ((dtype != PWC_MOTION_U8 && dtype != PWC_MOTION_F32) || min_count < 1 || !(threshold >= 0.0)) return PWC_EINVAL;
@@ -322,10 +345,25 @@ extern "C" int pwc_plate_difference(const void* frames, int dtype, int C, const 
     PlateDiffArgs a = {};
     a.frames = frames; a.plate = plate; a.count = count; a.matrices = matrices; a.difference = difference;
     a.foreground = foreground; a.known = known; a.threshold = threshold;
-    a.T = T; a.H = H; a.W = W; a.Hc = Hc; a.Wc = Wc; a.min_count = min_count;
+    a.T = T; a.H = H; a.W = W; a.Hc = Hc; a.Wc = Wc; a.min_count = min_count; a.projective = projective;
     const long blocks = ((long)T * H * W + 255) / 256;
     const dim3 grid((unsigned)(blocks > PLATE_MAX_BLOCKS ? PLATE_MAX_BLOCKS : blocks));
     if (u8) plate_difference_launch<true>(C, grid, (hipStream_t)stream, a);
     else plate_difference_launch<false>(C, grid, (hipStream_t)stream, a);
     return pwc_launch_status();
+}
+
+extern "C" int pwc_plate_difference(const void* frames, int dtype, int C, const void* plate, const uint8_t* count,
+                                    const double* matrices, int T, int H, int W, int Hc, int Wc, int min_count, double threshold,
+                                    float* difference, uint8_t* foreground, uint8_t* known, pwc_stream_t stream) {
+    return plate_difference_call(frames, dtype, C, plate, count, matrices, T, H, W, Hc, Wc, min_count, threshold, difference, foreground,
+                                 known, 0, stream);
+}
+
+extern "C" int pwc_plate_difference_projective(const void* frames, int dtype, int C, const void* plate, const uint8_t* count,
+                                               const double* matrices, int T, int H, int W, int Hc, int Wc, int min_count,
+                                               double threshold, float* difference, uint8_t* foreground, uint8_t* known,
+                                               pwc_stream_t stream) {
+    return plate_difference_call(frames, dtype, C, plate, count, matrices, T, H, W, Hc, Wc, min_count, threshold, difference, foreground,
+                                 known, 1, stream);
 }

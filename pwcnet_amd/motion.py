@@ -6,6 +6,9 @@ warped by it (csrc/pwc_motion.hip).
     warp_frames(frames, matrices)                                        -> (out (N,H,W,C), covered (N,H,W) bool)
     smooth_path(matrices, radius)                                        -> (T+1,3,3) float64 numpy, the matrices warp_frames wants
 
+The last three take projective=True for the matrices of homography.fit_homography: the position of a pixel is then
+(M p) / (m6 x + m7 y + m8), and there is none where that divisor is not positive (include/pwc_hip.h, "projective motion").
+
 fit_motion is a robust fit (iteratively reweighted least squares with the Cauchy weight) of a translation, a similarity or an
 affine motion to every flow of a batch, wholly on the device: 2 (iters + 1) launches on the current stream and no host
 synchronisation between the passes.  The exact sequence of operations is in include/pwc_hip.h, "dominant motion"; the kernels
@@ -92,16 +95,21 @@ def fit_motion(flows, valid=None, model="affine", iters=4, scale=1.0):
     return matrices, ok.view(torch.bool), {"count": count, "weight_sum": weight_sum}
 
 
-def motion_residual(flows, matrices, valid=None, threshold=3.0):
+def motion_residual(flows, matrices, valid=None, threshold=3.0, projective=False):
     """(residual (N,H,W,2) float32, inlier (N,H,W) torch.bool): the flow with the motion of `matrices` taken out, and the pixels
     that move with it (pwc_motion_residual_f32, one launch, a lane per pixel).
 
     flows, valid: as fit_motion's.  matrices: (N,3,3) torch.float64, fit_motion's.  residual = flow - (M p - p), computed in
     double and rounded once; inlier where |residual|^2 <= threshold^2 (of the double, before the rounding).  An unknown pixel
     holds the .flo sentinel 1e10 in both components and is no inlier (compose_flows' convention), and so does every pixel of an
-    image whose matrix is not affine (last row other than exactly 0 0 1) or not finite.  No autograd."""
+    image whose matrix is not affine (last row other than exactly 0 0 1) or not finite.
+    projective=True (pwc_motion_residual_projective_f32): matrices are fit_homography's; residual = flow - (pos - p) with the
+    projective position pos = (M p) / D, D = m6 x + m7 y + m8; the sentinel and no inlier where D is not positive, and everywhere
+    in an image one of whose nine entries is not finite.  An affine matrix gives the bits of projective=False.  No autograd."""
     N, H, W = _check_flows(flows, valid)
     _check_matrices(matrices, N)
+    if not isinstance(projective, (bool, np.bool_)):
+        raise TypeError(f"projective: expected a bool, got {projective!r}")
     if not float(threshold) >= 0.0:
         raise ValueError(f"threshold: expected a non-negative number, got {threshold!r}")
     _check_device(flows, flows=flows, valid=valid, matrices=matrices)
@@ -109,13 +117,13 @@ def motion_residual(flows, matrices, valid=None, threshold=3.0):
     matrices = matrices.detach().contiguous()
     residual = torch.empty((N, H, W, 2), dtype=torch.float32, device=flows.device)
     inlier = torch.empty((N, H, W), dtype=torch.uint8, device=flows.device)
-    _lib.check(_lib.lib().pwc_motion_residual_f32(_p(fv.ptr), fv.cs, _ptr(valid), _p(matrices.data_ptr()), N, H, W, float(threshold),
-                                                  _p(residual.data_ptr()), _p(inlier.data_ptr()), _lib.current_stream()),
-               "motion residual")
+    entry = _lib.lib().pwc_motion_residual_projective_f32 if projective else _lib.lib().pwc_motion_residual_f32
+    _lib.check(entry(_p(fv.ptr), fv.cs, _ptr(valid), _p(matrices.data_ptr()), N, H, W, float(threshold), _p(residual.data_ptr()),
+                     _p(inlier.data_ptr()), _lib.current_stream()), "motion residual")
     return residual, inlier.view(torch.bool)
 
 
-def warp_frames(frames, matrices):
+def warp_frames(frames, matrices, projective=False):
     """(out (N,H,W,C) in the frames' dtype, covered (N,H,W) torch.bool): every frame resampled through its matrix
     (pwc_warp_affine, one launch, a lane per four output pixels).
 
@@ -123,7 +131,12 @@ def warp_frames(frames, matrices):
     a numpy array (smooth_path's), each taking an OUTPUT pixel (x, y, 1) to its position in the source frame.  A position inside
     [0, W - 1] x [0, H - 1] is sampled bilinearly with clamped corners (fb_valid's sample, in double) and rounded once -- to
     float32, or rint clamped to [0, 255] for bytes.  Elsewhere, and everywhere in an image whose matrix is not affine (last row
-    other than exactly 0 0 1) or not finite, the output is 0 and covered is False.  No autograd."""
+    other than exactly 0 0 1) or not finite, the output is 0 and covered is False.
+    projective=True (pwc_warp_projective): the source position is (M p) / D, D = m6 x + m7 y + m8; not covered where D is not
+    positive, and everywhere in an image one of whose nine entries is not finite.  An affine matrix gives the bits of
+    projective=False.  No autograd."""
+    if not isinstance(projective, (bool, np.bool_)):
+        raise TypeError(f"projective: expected a bool, got {projective!r}")
     if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.float32):
         raise TypeError(f"frames: expected a torch.uint8 or torch.float32 tensor, got "
                         f"{frames.dtype if isinstance(frames, torch.Tensor) else type(frames)}")
@@ -141,12 +154,13 @@ def warp_frames(frames, matrices):
     out = torch.empty_like(frames)
     covered = torch.empty((N, H, W), dtype=torch.uint8, device=frames.device)
     dtype = _lib.MOTION_U8 if frames.dtype == torch.uint8 else _lib.MOTION_F32
-    _lib.check(_lib.lib().pwc_warp_affine(_p(frames.data_ptr()), dtype, C, _p(matrices.data_ptr()), N, H, W, _p(out.data_ptr()),
-                                          _p(covered.data_ptr()), _lib.current_stream()), "warp frames")
+    entry = _lib.lib().pwc_warp_projective if projective else _lib.lib().pwc_warp_affine
+    _lib.check(entry(_p(frames.data_ptr()), dtype, C, _p(matrices.data_ptr()), N, H, W, _p(out.data_ptr()), _p(covered.data_ptr()),
+                     _lib.current_stream()), "warp frames")
     return out, covered.view(torch.bool)
 
 
-def smooth_path(matrices, radius):
+def smooth_path(matrices, radius, projective=False):
     """(T + 1, 3, 3) float64 numpy: the stabilising matrices A_t of a sequence of T + 1 frames from the T motions between them,
     one per frame, the matrices warp_frames wants.  Host numpy float64.
 
@@ -155,7 +169,13 @@ def smooth_path(matrices, radius):
     [t - radius, t + radius], clipped to the sequence, and A_t = P_t inv(Pbar_t) takes a pixel of the stabilised frame t to
     where frame t holds it.  radius = 0 gives identities.
     The entry-wise mean of affine matrices is a choice: it is not a geodesic mean (it does not average rotations as rotations),
-    it is what is cheap and behaves for the small motions between neighbouring frames."""
+    it is what is cheap and behaves for the small motions between neighbouring frames.
+    projective=True: matrices are fit_homography's; the full 3 x 3 products are chained and inverted, every P_t, mean and A_t
+    divided by its [2][2] entry, and Pbar_t is the mean of the eight normalised entries (the ninth is 1); warp_frames wants the
+    result with projective=True.  A path whose [2][2] entry reaches 0 gives non-finite matrices, which warp_frames covers
+    nothing with."""
+    if not isinstance(projective, (bool, np.bool_)):
+        raise TypeError(f"projective: expected a bool, got {projective!r}")
     if isinstance(matrices, torch.Tensor):
         matrices = matrices.detach().cpu().numpy()
     M = np.asarray(matrices, np.float64)
@@ -168,9 +188,20 @@ def smooth_path(matrices, radius):
     P[0] = np.eye(3)
     for t in range(T):
         P[t + 1] = M[t] @ P[t]
+        if projective:
+            with np.errstate(all="ignore"):
+                P[t + 1] = P[t + 1] / P[t + 1, 2, 2]
     A = np.empty_like(P)
     for t in range(T + 1):
         mean = P[max(0, t - radius):min(T, t + radius) + 1].mean(axis=0)
+        if projective:
+            try:
+                with np.errstate(all="ignore"):
+                    A[t] = P[t] @ np.linalg.inv(mean)
+                    A[t] = A[t] / A[t, 2, 2]
+            except np.linalg.LinAlgError:
+                A[t] = np.nan
+            continue
         mean[2] = (0.0, 0.0, 1.0)
         A[t] = P[t] @ np.linalg.inv(mean)
         A[t, 2] = (0.0, 0.0, 1.0)

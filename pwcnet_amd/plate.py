@@ -17,6 +17,10 @@ in include/pwc_hip.h, "background plate"; the kernels equal their numpy restatem
 autograd.
 
 The lower median and min_count = 1 are choices: nobody has measured the quality of the plate on real footage.
+
+All five take projective=True for the matrices of homography.fit_homography (a camera that pans or tilts): the helpers then chain
+and invert full 3 x 3 matrices normalised to [2][2] = 1, and the two ops divide per pixel, (M p) / (m6 x + m7 y + m8), with no
+sample where that divisor is not positive (include/pwc_hip.h, "projective motion").  The default False is every call as it was.
 """
 import math
 
@@ -85,7 +89,22 @@ def _host_matrices(matrices, what, rows=None):
     return M
 
 
-def plate_path(matrices, ok=None, anchor=0):
+def _check_projective(projective):
+    if not isinstance(projective, (bool, np.bool_)):
+        raise TypeError(f"projective: expected a bool, got {projective!r}")
+    return bool(projective)
+
+
+def _normalised(M):
+    """M divided by its [2][2] entry, or None where that entry is not finite and positive or the result is not finite."""
+    with np.errstate(all="ignore"):
+        if not (np.isfinite(M[2, 2]) and M[2, 2] > 0.0):
+            return None
+        M = M / M[2, 2]
+    return M if np.isfinite(M).all() else None
+
+
+def plate_path(matrices, ok=None, anchor=0, projective=False):
     """(to_frame (T + 1,3,3) float64 numpy, reach (T + 1,) bool): for every frame of a sequence of T + 1 the matrix that takes a
     pixel (x, y, 1) of the ANCHOR frame to where that frame holds it, from the T motions between neighbours.  Host numpy float64.
 
@@ -93,7 +112,10 @@ def plate_path(matrices, ok=None, anchor=0):
     to_frame[t + 1] = M_t to_frame[t] going forwards and to_frame[t] = inv(M_t) to_frame[t + 1] going backwards, the last row set
     to 0 0 1 after every step.  ok: (T,) bool, fit_motion's, None = all True.  Where ok[t] is False -- or M_t is not finite or
     cannot be inverted on the way back -- the chain is broken between frames t and t + 1: every frame beyond the break, seen from
-    the anchor, has reach False and the identity."""
+    the anchor, has reach False and the identity.
+    projective=True: matrices are fit_homography's; the full 3 x 3 products are kept, divided by their [2][2] entry after every
+    step, and a step whose [2][2] entry is not finite and positive breaks the chain as well."""
+    projective = _check_projective(projective)
     M = _host_matrices(matrices, "matrices")
     T = M.shape[0]
     if ok is None:
@@ -111,8 +133,14 @@ def plate_path(matrices, ok=None, anchor=0):
     for t in range(anchor, T):
         if not (ok[t] and np.isfinite(M[t]).all()):
             break
-        to_frame[t + 1] = M[t] @ to_frame[t]
-        to_frame[t + 1, 2] = (0.0, 0.0, 1.0)
+        step = M[t] @ to_frame[t]
+        if projective:
+            step = _normalised(step)
+            if step is None:
+                break
+        else:
+            step[2] = (0.0, 0.0, 1.0)
+        to_frame[t + 1] = step
         reach[t + 1] = True
     for t in range(anchor - 1, -1, -1):
         if not (ok[t] and np.isfinite(M[t]).all()):
@@ -123,8 +151,14 @@ def plate_path(matrices, ok=None, anchor=0):
             break
         if not np.isfinite(inverse).all():
             break
-        to_frame[t] = inverse @ to_frame[t + 1]
-        to_frame[t, 2] = (0.0, 0.0, 1.0)
+        step = inverse @ to_frame[t + 1]
+        if projective:
+            step = _normalised(step)
+            if step is None:
+                break
+        else:
+            step[2] = (0.0, 0.0, 1.0)
+        to_frame[t] = step
         reach[t] = True
     return to_frame, reach
 
@@ -139,13 +173,16 @@ def _check_path(to_frame, reach):
     return P, reach
 
 
-def plate_canvas(to_frame, reach, H, W, margin=0, max_side=4096):
+def plate_canvas(to_frame, reach, H, W, margin=0, max_side=4096, projective=False):
     """(x0, y0, Hc, Wc): the integer box, in the anchor frame's coordinates, that the reachable frames cover -- canvas pixel
     (x, y) is the anchor's (x + x0, y + y0).  Host only.
 
     The four corners (0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1) of every frame with reach[t] are carried to anchor
     coordinates by inv(to_frame[t]); x0 = floor(min x) - margin, x1 = ceil(max x) + margin, Wc = x1 - x0 + 1, likewise in y.
-    ValueError where no frame is reachable or a side is above max_side (a path that drifts: lower --plate_frames or raise it)."""
+    ValueError where no frame is reachable or a side is above max_side (a path that drifts: lower --plate_frames or raise it).
+    projective=True: the corners are carried with the division, (x, y) = (q0, q1) / q2 for q = inv(to_frame[t]) corner; a frame
+    with a corner at q2 <= 0 (behind the horizon), or whose matrix cannot be inverted, counts as not reached."""
+    projective = _check_projective(projective)
     P, reach = _check_path(to_frame, reach)
     H, W = _check_int(H, "H", 1, 1 << 30), _check_int(W, "W", 1, 1 << 30)
     margin = _check_int(margin, "margin", 0, 1 << 30)
@@ -155,9 +192,20 @@ def plate_canvas(to_frame, reach, H, W, margin=0, max_side=4096):
     corners = np.array([[0.0, 0.0, 1.0], [W - 1.0, 0.0, 1.0], [0.0, H - 1.0, 1.0], [W - 1.0, H - 1.0, 1.0]]).T
     xs, ys = [], []
     for t in np.nonzero(reach)[0]:
-        q = np.linalg.inv(P[t]) @ corners
+        if projective:
+            try:
+                q = np.linalg.inv(P[t]) @ corners
+            except np.linalg.LinAlgError:
+                continue
+            if not (q[2] > 0.0).all():
+                continue
+            q = q / q[2]
+        else:
+            q = np.linalg.inv(P[t]) @ corners
         xs.append(q[0])
         ys.append(q[1])
+    if not xs:
+        raise ValueError("reach: no frame is reachable in front of the horizon")
     xs, ys = np.concatenate(xs), np.concatenate(ys)
     if not (np.isfinite(xs).all() and np.isfinite(ys).all()):
         raise ValueError("to_frame: a reachable frame's corners are not finite on the canvas")
@@ -169,17 +217,34 @@ def plate_canvas(to_frame, reach, H, W, margin=0, max_side=4096):
     return int(x0), int(y0), int(Hc), int(Wc)
 
 
-def canvas_matrices(to_frame, x0, y0):
+def canvas_matrices(to_frame, x0, y0, projective=False):
     """(matrices, frame_matrices), (T + 1,3,3) float64 numpy each: matrices[t] = to_frame[t] @ [[1,0,x0],[0,1,y0],[0,0,1]] takes a
     CANVAS pixel to its position in frame t (what background_plate wants), frame_matrices[t] = inv(matrices[t]) takes a pixel of
     frame t to the canvas (what plate_difference wants); last rows 0 0 1.  A matrix that cannot be inverted gives NaNs, which
-    both kernels read as "this frame sees nothing".  Host only."""
+    both kernels read as "this frame sees nothing".  Host only.
+    projective=True: the full 3 x 3 matrices, each divided by its [2][2] entry; NaNs where that entry is not finite and positive
+    (what background_plate and plate_difference want with projective=True)."""
+    projective = _check_projective(projective)
     P = _host_matrices(to_frame, "to_frame")
     for what, v in (("x0", x0), ("y0", y0)):
         if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
             raise ValueError(f"{what}: expected a finite number, got {v!r}")
     shift = np.array([[1.0, 0.0, float(x0)], [0.0, 1.0, float(y0)], [0.0, 0.0, 1.0]])
     matrices = P @ shift
+    if projective:
+        frame_matrices = np.full_like(matrices, np.nan)
+        for t in range(P.shape[0]):
+            forward = _normalised(matrices[t])
+            matrices[t] = np.nan if forward is None else forward
+            if forward is None:
+                continue
+            try:
+                inverse = _normalised(np.linalg.inv(forward))
+            except np.linalg.LinAlgError:
+                continue
+            if inverse is not None:
+                frame_matrices[t] = inverse
+        return matrices, frame_matrices
     matrices[:, 2] = (0.0, 0.0, 1.0)
     frame_matrices = np.full_like(matrices, np.nan)
     for t in range(P.shape[0]):
@@ -211,7 +276,7 @@ def _device_matrices(matrices, T, device):
     return matrices
 
 
-def background_plate(frames, matrices, canvas, mode="median", use=None, masks=None, min_count=1):
+def background_plate(frames, matrices, canvas, mode="median", use=None, masks=None, min_count=1, projective=False):
     """(plate (Hc,Wc,C) in the frames' dtype, count (Hc,Wc) torch.uint8): the clip's frames on one canvas, voted per pixel
     (pwc_plate_build: one launch on the current stream, no workspace, no host synchronisation).
 
@@ -224,7 +289,11 @@ def background_plate(frames, matrices, canvas, mode="median", use=None, masks=No
     warp_frames rounds (the element of rank (n - 1) // 2 of n; floats ordered with -0 < +0, the output is one of the samples'
     bit patterns); "mean": the mean of the unrounded samples, added in frame order, rounded once.  count: n, the samples a pixel
     has; where n < min_count (>= 1) the plate is 0.  Two calls give the same bits.  The lower median and min_count = 1 are
-    choices nobody has measured on real footage.  No autograd: the outputs never require grad."""
+    choices nobody has measured on real footage.
+    projective=True (pwc_plate_build_projective): matrices are canvas_matrices' with projective=True; the position is (M p) / D,
+    D = m6 x + m7 y + m8; a frame has no sample where D is not positive or one of its nine entries is not finite.  Affine matrices
+    give the bits of projective=False.  No autograd: the outputs never require grad."""
+    projective = _check_projective(projective)
     T, H, W, C = _check_frames(frames)
     if T > MAX_FRAMES:
         raise ValueError(f"frames: expected at most {MAX_FRAMES} frames, got {T}")
@@ -252,13 +321,13 @@ def background_plate(frames, matrices, canvas, mode="median", use=None, masks=No
     plate = torch.empty((Hc, Wc, C), dtype=frames.dtype, device=frames.device)
     count = torch.empty((Hc, Wc), dtype=torch.uint8, device=frames.device)
     dtype = _lib.MOTION_U8 if frames.dtype == torch.uint8 else _lib.MOTION_F32
-    _lib.check(_lib.lib().pwc_plate_build(_p(frames.data_ptr()), dtype, C, _p(matrices.data_ptr()), _ptr(use_t), _ptr(masks), T, H, W,
-                                          Hc, Wc, MODES[mode], min_count, _p(plate.data_ptr()), _p(count.data_ptr()),
-                                          _lib.current_stream()), "background plate")
+    entry = _lib.lib().pwc_plate_build_projective if projective else _lib.lib().pwc_plate_build
+    _lib.check(entry(_p(frames.data_ptr()), dtype, C, _p(matrices.data_ptr()), _ptr(use_t), _ptr(masks), T, H, W, Hc, Wc, MODES[mode],
+                     min_count, _p(plate.data_ptr()), _p(count.data_ptr()), _lib.current_stream()), "background plate")
     return plate, count
 
 
-def plate_difference(frames, plate, count, matrices, threshold, min_count=1):
+def plate_difference(frames, plate, count, matrices, threshold, min_count=1, projective=False):
     """(difference (T,H,W) float32, foreground (T,H,W) torch.bool, known (T,H,W) torch.bool): every frame against the plate
     sampled where the frame looks (pwc_plate_difference: one launch, a lane per frame pixel).
 
@@ -268,7 +337,9 @@ def plate_difference(frames, plate, count, matrices, threshold, min_count=1):
     is on the canvas, all four corners of the bilinear sample have count >= min_count and, for floats, everything read is
     finite.  difference: the largest absolute difference over the channels between the frame's value and the plate's
     (unrounded) sample, in the frames' units; 0 where not known.  foreground: known and difference > threshold (>= 0).
-    No autograd."""
+    projective=True (pwc_plate_difference_projective): matrices are canvas_matrices' frame_matrices with projective=True; a
+    pixel is not known where D = m6 x + m7 y + m8 is not positive or an entry of its matrix is not finite.  No autograd."""
+    projective = _check_projective(projective)
     T, H, W, C = _check_frames(frames)
     if not isinstance(plate, torch.Tensor) or plate.dtype != frames.dtype:
         raise TypeError(f"plate: expected a {frames.dtype} tensor, the frames' dtype, got "
@@ -291,10 +362,10 @@ def plate_difference(frames, plate, count, matrices, threshold, min_count=1):
     foreground = torch.empty((T, H, W), dtype=torch.uint8, device=frames.device)
     known = torch.empty((T, H, W), dtype=torch.uint8, device=frames.device)
     dtype = _lib.MOTION_U8 if frames.dtype == torch.uint8 else _lib.MOTION_F32
-    _lib.check(_lib.lib().pwc_plate_difference(_p(frames.data_ptr()), dtype, C, _p(plate.data_ptr()), _p(count.data_ptr()),
-                                               _p(matrices.data_ptr()), T, H, W, Hc, Wc, min_count, float(threshold),
-                                               _p(difference.data_ptr()), _p(foreground.data_ptr()), _p(known.data_ptr()),
-                                               _lib.current_stream()), "plate difference")
+    entry = _lib.lib().pwc_plate_difference_projective if projective else _lib.lib().pwc_plate_difference
+    _lib.check(entry(_p(frames.data_ptr()), dtype, C, _p(plate.data_ptr()), _p(count.data_ptr()), _p(matrices.data_ptr()), T, H, W, Hc,
+                     Wc, min_count, float(threshold), _p(difference.data_ptr()), _p(foreground.data_ptr()), _p(known.data_ptr()),
+                     _lib.current_stream()), "plate difference")
     return difference, foreground.view(torch.bool), known.view(torch.bool)
 
 

@@ -92,17 +92,18 @@ def label_regions(mask, connectivity=8, min_area=1, max_regions=256, flows=None,
     return labels, count, {"area": area, "box": box, "mean": mean, "sums": sums}
 
 
-def moving_regions(flows, matrices, valid=None, threshold=3.0, **label_kw):
+def moving_regions(flows, matrices, valid=None, threshold=3.0, projective=False, **label_kw):
     """(labels, count, regions, residual, inlier): what moves on its own, as objects -- motion_residual followed by
     label_regions(inlier, invert=True, flows=residual, ...), nothing in between.
 
-    flows, matrices, valid, threshold: motion_residual's (matrices are fit_motion's).  label_kw: connectivity, min_area,
+    flows, matrices, valid, threshold, projective: motion_residual's (matrices are fit_motion's, or fit_homography's with
+    projective=True).  label_kw: connectivity, min_area,
     max_regions of label_regions.  A region is a connected set of pixels whose flow is known and differs from the dominant motion
     by more than `threshold` px; unknown pixels hold 1e10 in the residual and fall out through the flow rule.  regions["mean"] is
     a region's mean motion RELATIVE to the camera, in pixels.  Nothing here judges segmentation quality on real video."""
     unknown = set(label_kw) - {"connectivity", "min_area", "max_regions"}
     if unknown:
         raise TypeError(f"moving_regions: unexpected keyword arguments {sorted(unknown)}")
-    residual, inlier = motion_residual(flows, matrices, valid=valid, threshold=threshold)
+    residual, inlier = motion_residual(flows, matrices, valid=valid, threshold=threshold, projective=projective)
     labels, count, regions = label_regions(inlier, flows=residual, invert=True, **label_kw)
     return labels, count, regions, residual, inlier
