@@ -1609,6 +1609,73 @@ int pwc_plate_difference_projective(const void* frames, int dtype, int C, const 
                                     const double* matrices, int T, int H, int W, int Hc, int Wc, int min_count, double threshold,
                                     float* difference, uint8_t* foreground, uint8_t* known, pwc_stream_t stream);
 
+/* ==== epipolar motion: the fundamental matrix that explains most of a flow field, and every pixel's Sampson distance to it ====
+ * (pwc_fundamental.hip, motion_jacobi.h; launch plan, bytes and what is unmeasured in DESIGN.md 27.)  A point map -- affine or a
+ * homography -- is exact only for a camera that rotates or a scene that is flat; a camera that translates through depth leaves
+ * parallax, and the constraint that still holds for everything rigid is p'^T F p = 0.  Every value is an IEEE double + - x / sqrt
+ * or a comparison in the order given here, no fused multiply-add; sqrt on doubles (correctly rounded) is the only library call:
+ * tests/fundamental_ref.py restates it in numpy bit for bit.  Flows, valid, KNOWN, the partition of the sums, the tree and the
+ * part order are "dominant motion"'s; xh, yh, cx, cy, s and the target x' = xh + (u / s), y' = yh + (v / s) are "projective
+ * motion"'s: one normalisation T serves both frames.
+ *
+ * SAMPSON(f, x, y, x', y') for nine doubles f0 .. f8 (row-major F): l0 = ((f0 x) + (f1 y)) + f2, l1 = ((f3 x) + (f4 y)) + f5,
+ * l2 = ((f6 x) + (f7 y)) + f8 (l = F p); r = ((x' l0) + (y' l1)) + l2 (= a^T f); m0 = ((f0 x') + (f3 y')) + f6, m1 = ((f1 x') +
+ * (f4 y')) + f7 (l' = F^T p'); g = (((l0 l0) + (l1 l1)) + (m0 m0)) + (m1 m1).
+ *
+ * FIT (pwc_fundamental_fit_f64), the reweighted normalised eight-point fit; iters + 1 passes; in each, per known pixel: w = 1
+ * (pass 0); later, against the F^ of the pass before (9 doubles per image in the workspace), r and g = SAMPSON(F^, xh, yh, x', y');
+ * a pixel with !(g > 0) adds nothing to the sums of that pass (it is still counted); else d2 = ((r r) / g) (s s), the squared
+ * Sampson distance in pixels, and w = (1 / (1 + (d2 / (scale scale)))) / g -- the Cauchy weight over the factor that turns the
+ * algebraic error into the geometric one.  The pixel contributes w a a^T with a = (x' xh, x' yh, x', y' xh, y' yh, y', xh, yh, 1);
+ * the 45 entries of the triangle are 36 distinct monomials and 36 sums are kept: with wx = w xh, wy = w yh, b = {w, wx, wy, wx xh,
+ * wx yh, wy yh} and pa = {x', y', x' x', x' y', y' y'}: S[j] += b[j] and S[6 (m + 1) + j] += b[j] pa[m] (j = 0 .. 5, m = 0 .. 4),
+ * plus the integer count of known pixels; ONE tree round over all 36 (36 x 256 doubles and 256 ints of LDS).  One lane per image
+ * adds the parts in index order and solves: with a_k = P[pk] Q[qk], P = (1, x', y'), Q = (1, xh, yh), pk = (1 1 1 2 2 2 0 0 0), qk =
+ * (1 2 0 1 2 0 1 2 0) and mono(i, j) the place of the product of entries i and j in (1, x, y, x x, x y, y y), entry (k, l) of the
+ * symmetric 9 x 9 matrix A is S[6 mono(pk_k, pk_l) + mono(qk_k, qk_l)]; tr = A00 + A11 + ... + A88 left to right.
+ * JACOBI (motion_jacobi.h, sizes 9 and 3): V = I; exactly 10 sweeps over (p, q), p < q, in row order; an entry A_pq that is
+ * exactly 0 is skipped; else theta = (A_qq - A_pp) / (2 A_pq), t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt((theta theta) + 1)),
+ * c = 1 / sqrt((t t) + 1), s = t c; for k other than p, q, from the old values, A_kp <- (c A_kp) - (s A_kq) and A_kq <- (s A_kp) +
+ * (c A_kq) (and their mirror images); A_pp <- A_pp - (t A_pq), A_qq <- A_qq + (t A_pq), A_pq <- 0; for every k, V_kp <- (c V_kp) -
+ * (s V_kq), V_kq <- (s V_kp) + (c V_kq).  Eigenvalue j is A_jj, its eigenvector column j of V.  (Six sweeps bring the off-diagonal
+ * part of the test scene's matrix to 1e-13 of the trace, four do not; 10 is a choice.)
+ * F^ is the eigenvector of the smallest eigenvalue e0, ties to the lowest column; e1 is the smallest of the others, ties likewise;
+ * eigen = (e0 / tr, e1 / tr).  RANK 2: B_ij = ((F^_0i F^_0j) + (F^_1i F^_1j)) + (F^_2i F^_2j) (= F^^T F^), JACOBI at size 3, v the
+ * eigenvector of its smallest eigenvalue (the epipole of the first frame in normalised coordinates); u_i = ((F^_i0 v0) + (F^_i1 v1))
+ * + (F^_i2 v2) and F^_ij <- F^_ij - (u_i v_j): the closest rank-2 matrix.
+ * DEGENERATE: fewer than 8 known pixels (no decomposition: eigen 0 0), !(e1 > 1e-9 tr) -- the flow is then a homography's, a pure
+ * rotation or a flat scene, and F is not determined --, or an entry of F^, v or eigen that is not finite.  Final: a degenerate
+ * image's F^ is all zeros in every later pass (every pixel is then left out) and its eigen stays that of the pass that found it.
+ * The last pass writes F = T^T F^ T: a_i = (h_i0 / s, h_i1 / s, h_i2 - (((h_i0 cx) + (h_i1 cy)) / s)) for the rows h_i of F^; m_0j =
+ * a_0j / s, m_1j = a_1j / s, m_2j = a_2j - (((a_0j cx) + (a_1j cy)) / s); m <- m / sqrt(m0 m0 + m1 m1 + ... + m8 m8) (left to right);
+ * the entry of largest magnitude (ties to the lowest index) is made positive by negating all nine.  epipole = ((s v0) + (cx v2),
+ * (s v1) + (cy v2), v2): homogeneous, not normalised, F epipole = 0 up to rounding.  ok = 0, matrices all zeros and epipole zeros
+ * where the image is degenerate or an entry of m or the epipole is not finite.
+ * matrices N x 9 doubles; ok N bytes; count N int32 known pixels; weight_sum N doubles, S[0] of the last pass; eigen N x 2 doubles;
+ * epipole N x 3 doubles.  2 (iters + 1) launches on `stream`: sums on the grid (parts, N), then solve; no atomic, no host
+ * synchronisation, no process-wide state; an image's result does not depend on its neighbours in the batch and two calls give the
+ * same bits.  workspace: pwc_fundamental_fit_workspace_bytes = 8 (N parts 36 + N 9) + 4 N parts rounded up to 8 (0 for sizes the
+ * call refuses), 8-byte aligned.  Checks, in pwc_homography_fit_f64's order: a null flows, workspace or output pointer, N, H, W < 1,
+ * iters outside 0 .. PWC_MOTION_MAX_ITERS, scale not > 0 (a NaN fails), flow_cs < 2 (PWC_EINVAL); H W > 2^31 - 65537 or N > 65535
+ * (PWC_ERANGE); flows or count off a 4-byte, workspace, matrices, weight_sum, eigen or epipole off an 8-byte boundary (PWC_EALIGN);
+ * a workspace that is too small (PWC_EINVAL).
+ *
+ * RESIDUAL (pwc_epipolar_residual_f32), one launch, a lane per pixel (4096 workgroups of 256 lanes at most, grid-stride beyond),
+ * in PIXEL coordinates: r, g = SAMPSON(F, x, y, x + u, y + v) with u, v widened to doubles; dd = |r| / sqrt(g), the Sampson distance
+ * in pixels; distance = (float)dd, rounded once; inlier = dd <= threshold (of the double).  distance is 1e10 and inlier 0 where the
+ * flow is unknown, valid is 0, !(g > 0), or all nine entries of the image's matrix are zero (what FIT writes with ok = 0).
+ * distance: N x H x W floats; inlier: N x H x W bytes.  Checks: null pointers, sizes < 1, flow_cs < 2, a negative or NaN threshold
+ * (PWC_EINVAL); the range as above (PWC_ERANGE); flows or distance off a 4-byte, matrices off an 8-byte boundary (PWC_EALIGN).
+ *
+ * What the model cannot see: a point that moves ALONG its epipolar line (a car ahead driving the way the camera drives) satisfies
+ * the constraint; and a camera that only rotates leaves F undetermined (ok = 0; eigen shows how close a clip is to that). */
+size_t pwc_fundamental_fit_workspace_bytes(int N, int H, int W);
+int pwc_fundamental_fit_f64(const float* flows, int flow_cs, const uint8_t* valid, int N, int H, int W, int iters, double scale,
+                            void* workspace, size_t workspace_bytes, double* matrices, uint8_t* ok, int32_t* count,
+                            double* weight_sum, double* eigen, double* epipole, pwc_stream_t stream);
+int pwc_epipolar_residual_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N, int H, int W,
+                              double threshold, float* distance, uint8_t* inlier, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,12 @@ pictures come back to the host.  --interp_alpha A is the weight of the photometr
 every pair, a translation, similarity or affine matrix taking a pixel (x, y, 1) of frame i to frame i + 1, fitted robustly on the
 GPU (pwcnet_amd.fit_motion, one call per batch; after the refit where --fit is not crop; --motion homography: the eight-parameter
 pwcnet_amd.fit_homography, and --motion_residual, --stabilize, --regions, --regions_track and --plate with --plate_foreground then
-call their ops with projective=True, a division per pixel).  --motion_iters K and --motion_scale C
+call their ops with projective=True, a division per pixel; --motion fundamental: pwcnet_amd.fit_fundamental, the epipolar
+model for a camera that translates through depth -- motion.npy then holds the fundamental matrices, <out>/epipoles.npy (pairs, 3)
+the homogeneous epipoles, --motion_residual writes <fname>_sampson.npy, every pixel's Sampson distance in pixels (1e10 where
+unknown), in place of the residual .flo, --regions and --regions_track go through pwcnet_amd.epipolar_regions with
+--regions_threshold as its threshold and the regions' mean flow itself in the table, and --stabilize and --plate, which need a
+point map, are refused).  --motion_iters K and --motion_scale C
 are the reweighting passes [4] and the Cauchy scale in pixels [1.0].  --motion_residual also writes <fname>_residual.flo, the flow
 with that motion taken out (unknown pixels hold the .flo sentinel), and <fname>_inlier.png, white where a pixel moves with it.
 --stabilize R (needs --motion and frames of one size) smooths the camera path over 2 R + 1 frames (pwcnet_amd.smooth_path) and, in
@@ -130,9 +135,10 @@ def build_parser():
                          "interpolated on the GPU from the two flows between them (the reversed pairs are run too) [off]")
     ap.add_argument("--interp_alpha", type=float, default=20.0, metavar="A",
                     help="--interp: the weight of a source pixel is exp(-min(A * e, 10)), e its match's mean colour error [20]")
-    ap.add_argument("--motion", choices=("translation", "similarity", "affine", "homography"), default=None,
+    ap.add_argument("--motion", choices=("translation", "similarity", "affine", "homography", "fundamental"), default=None,
                     help="also write motion.npy / motion_ok.npy: the dominant motion of every pair, fitted robustly on the GPU; "
-                         "homography: pwcnet_amd.fit_homography, and every flag below that uses the motion divides per pixel [off]")
+                         "homography: pwcnet_amd.fit_homography, and every flag below that uses the motion divides per pixel; "
+                         "fundamental: pwcnet_amd.fit_fundamental, the epipolar model (also writes epipoles.npy; no --stabilize, no --plate) [off]")
     ap.add_argument("--motion_iters", type=int, default=4, metavar="K", help="--motion: reweighting passes, 0 .. 64 [4]")
     ap.add_argument("--motion_scale", type=float, default=1.0, metavar="C", help="--motion: the Cauchy scale in pixels [1.0]")
     ap.add_argument("--motion_residual", action="store_true",
@@ -377,6 +383,8 @@ def main():
     both_ways = args.track_fb or args.interp > 0 or denoise is not None
     if args.motion is None and (args.motion_residual or args.stabilize != 0):
         ap.error("--motion_residual and --stabilize need --motion MODEL")
+    if args.motion == "fundamental" and (args.stabilize != 0 or args.plate):
+        ap.error("--stabilize and --plate need a point map; --motion fundamental is a constraint, not one: use affine or homography")
     if args.regions and args.motion is None:
         ap.error("--regions needs --motion MODEL")
     if args.regions_track and not args.regions:
@@ -442,6 +450,8 @@ def main():
     if args.regions_track:
         region_tracker = RegionTracker(paths, args.out, args.regions_track_overlap, args.regions_track_fraction)
     motions, motions_ok = [None] * (len(frames) - 1), [None] * (len(frames) - 1)
+    epipolar = args.motion == "fundamental"
+    epipoles = [None] * (len(frames) - 1) if epipolar else None
     proj = {"projective": True} if args.motion == "homography" else {}       # the other models: the calls as they were
     if args.stabilize > 0 and any(f.shape != frames[0].shape for f in frames):
         raise ValueError("--stabilize needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
@@ -499,7 +509,10 @@ def main():
             if denoiser is not None:                 # only the uint8 pictures cross to the host
                 denoiser.add(i, pictures, flow_final, flow_back)
             if args.motion is not None:              # one call per batch; matrices, flags and uint8 pictures cross to the host
-                if args.motion == "homography":
+                if epipolar:
+                    matrices, ok, fit_info = pwcnet_amd.fit_fundamental(flow_final, iters=args.motion_iters, scale=args.motion_scale)
+                    epipoles[i:j] = list(fit_info["epipole"].cpu().numpy())
+                elif args.motion == "homography":
                     matrices, ok, _ = pwcnet_amd.fit_homography(flow_final, iters=args.motion_iters, scale=args.motion_scale)
                 else:
                     matrices, ok, _ = pwcnet_amd.fit_motion(flow_final, model=args.motion, iters=args.motion_iters,
@@ -507,7 +520,15 @@ def main():
                 motions[i:j], motions_ok[i:j] = list(matrices.cpu().numpy()), list(ok.cpu().numpy())
                 if plate_inliers is not None:        # --plate_inliers: the masks wait on the host for the second pass
                     plate_inliers[i:j] = list(pwcnet_amd.motion_residual(flow_final, matrices, **proj)[1].to(torch.uint8).cpu().numpy())
-                if args.motion_residual:
+                if args.motion_residual and epipolar:
+                    distance, inlier = pwcnet_amd.epipolar_residual(flow_final, matrices)
+                    distance, inlier = distance.cpu().numpy(), (inlier.to(torch.uint8) * 255).cpu().numpy()
+                    for k in range(j - i):
+                        dname, fname = out_stem(paths[i + k])
+                        os.makedirs(os.path.join(args.out, dname), exist_ok=True)
+                        np.save(os.path.join(args.out, dname, fname + "_sampson.npy"), distance[k])
+                        Image.fromarray(inlier[k]).save(os.path.join(args.out, dname, fname + "_inlier.png"))
+                elif args.motion_residual:
                     residual, inlier = pwcnet_amd.motion_residual(flow_final, matrices, **proj)
                     residual, inlier = residual.cpu().numpy(), (inlier.to(torch.uint8) * 255).cpu().numpy()
                     for k in range(j - i):
@@ -516,7 +537,8 @@ def main():
                         flow_io.write_flo(os.path.join(args.out, dname, fname + "_residual.flo"), residual[k])
                         Image.fromarray(inlier[k]).save(os.path.join(args.out, dname, fname + "_inlier.png"))
                 if args.regions:                     # the ids and the tables cross to the host, nothing else
-                    labels, count, regions = pwcnet_amd.moving_regions(
+                    find_regions = pwcnet_amd.epipolar_regions if epipolar else pwcnet_amd.moving_regions
+                    labels, count, regions = find_regions(
                         flow_final, matrices, threshold=args.regions_threshold, connectivity=args.regions_connectivity,
                         min_area=args.regions_min_area, max_regions=REGIONS_ROWS, **proj)[:3]
                     if region_tracker is not None:   # (before the host copies below take the names)
@@ -552,6 +574,8 @@ def main():
         os.makedirs(args.out, exist_ok=True)
         np.save(os.path.join(args.out, "motion.npy"), np.stack(motions))
         np.save(os.path.join(args.out, "motion_ok.npy"), np.asarray(motions_ok, bool))
+        if epipolar:
+            np.save(os.path.join(args.out, "epipoles.npy"), np.stack(epipoles))
     if args.stabilize > 0:                           # the second pass: the frames again, batch by batch
         steady = pwcnet_amd.smooth_path(np.stack(motions), args.stabilize, **proj)
         for i in range(0, len(frames), max(1, args.batch)):

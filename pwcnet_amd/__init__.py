@@ -21,6 +21,8 @@ from . import homography  # noqa: F401
 from .homography import fit_homography  # noqa: F401
 from . import regions  # noqa: F401
 from .regions import label_regions, moving_regions  # noqa: F401
+from . import fundamental  # noqa: F401
+from .fundamental import epipolar_regions, epipolar_residual, fit_fundamental  # noqa: F401
 from . import region_tracks  # noqa: F401
 from .region_tracks import link_regions, region_identities, relabel_regions, track_regions  # noqa: F401
 from . import flow_filter  # noqa: F401
@@ -49,6 +51,7 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "interp", "interpolate_frames",
            "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path", "homography", "fit_homography",
            "regions", "label_regions", "moving_regions",
+           "fundamental", "fit_fundamental", "epipolar_residual", "epipolar_regions",
            "region_tracks", "link_regions", "region_identities", "relabel_regions", "track_regions",
            "flow_filter", "filter_tables", "filter_flow", "fill_flow",
            "temporal", "temporal_filter", "plan_windows",
