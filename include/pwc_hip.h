@@ -1676,6 +1676,73 @@ int pwc_fundamental_fit_f64(const float* flows, int flow_cs, const uint8_t* vali
 int pwc_epipolar_residual_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, int N, int H, int W,
                               double threshold, float* distance, uint8_t* inlier, pwc_stream_t stream);
 
+/* ==== relative pose and depth: how the camera moved between two frames, and how far away every rigid pixel is ====
+ * (pwc_pose.hip, two_view.h, motion_jacobi.h; launch plan, bytes and what is unmeasured in DESIGN.md 28.)  With a calibration K =
+ * [fx 0 cx; 0 fy cy; 0 0 1], the same for both frames, in pixels of the flow's grid, the fundamental matrix of "epipolar motion"
+ * becomes the essential matrix E = K^T F K = [t]x R up to scale, and X' = R X + t takes a point of the first camera's frame to the
+ * second's.  |t| is not observable from two views: t has unit length and every depth is in units of that baseline.  Every value is
+ * an IEEE double + - x / sqrt or a comparison in the order given here, no fused multiply-add; sqrt on doubles is the only library
+ * call: tests/pose_ref.py restates it in numpy bit for bit.  Flows, valid, KNOWN and the partition are "dominant motion"'s;
+ * SAMPSON and JACOBI are "epipolar motion"'s.  intrinsics: N x 4 doubles fx fy cx cy; FINE: all four finite, fx > 0 and fy > 0.
+ *
+ * RAYS of a pixel (x, y) with flow (u, v) widened to doubles: x' = x + u, y' = y + v; d0 = ((x - cx) / fx, (y - cy) / fy, 1),
+ * d1 = ((x' - cx) / fx, (y' - cy) / fy, 1).
+ * TRIANGULATE(R, t, d0, d1) for a row-major R: a_r = ((R_r0 d0x) + (R_r1 d0y)) + R_r2 (a = R d0); c = d1 x a as c0 = (d1y a2) - a1,
+ * c1 = a0 - (d1x a2), c2 = (d1x a1) - (d1y a0); e = d1 x t likewise, e0 = (d1y t2) - t1, e1 = t0 - (d1x t2), e2 = (d1x t1) - (d1y t0);
+ * den = ((c0 c0) + (c1 c1)) + (c2 c2); Z0 = (-(((c0 e0) + (c1 e1)) + (c2 e2))) / den; Z1 = (Z0 a2) + t2.  Z0 and Z1 are the depths of
+ * the point in the first and the second camera (Z1 d1 = Z0 a + t crossed with d1).  Under -t both are the exact negations.
+ *
+ * POSE (pwc_camera_pose_f64), three launches.
+ * Decompose, a lane per image.  GOOD starts as: not all nine entries of F are zero, and the intrinsics are FINE; an image that is
+ * not GOOD skips what follows.  G = F K: G_i0 = F_i0 fx, G_i1 = F_i1 fy, G_i2 = ((F_i0 cx) + (F_i1 cy)) + F_i2; E = K^T G: E_0j =
+ * fx G_0j, E_1j = fy G_1j, E_2j = ((cx G_0j) + (cy G_1j)) + G_2j.  B_ij = ((E_0i E_0j) + (E_1i E_1j)) + (E_2i E_2j) (= E^T E), JACOBI
+ * at size 3: v3 is the column of the smallest eigenvalue l3 (ties to the lowest column), v1 and v2 the two others in column order
+ * with eigenvalues l1, l2.  s1 = sqrt(l1), s2 = sqrt(l2), s3 = l3 > 0 ? sqrt(l3) : 0; GOOD needs s1 > 0 and s2 > 0; singular =
+ * (s2 / s1, s3 / s1) -- an essential matrix has (1, 0); s3 is the root of an eigenvalue, so rounding alone leaves about 1e-8 there.
+ * u1_i = (((E_i0 v1_0) + (E_i1 v1_1)) + (E_i2 v1_2)) / s1, u2 likewise with v2 and s2; u3 = u1 x u2 as u3_0 = (u1_1 u2_2) -
+ * (u1_2 u2_1), u3_1 = (u1_2 u2_0) - (u1_0 u2_2), u3_2 = (u1_0 u2_1) - (u1_1 u2_0), then u3 <- u3 / sqrt(((u3_0 u3_0) + (u3_1 u3_1)) +
+ * (u3_2 u3_2)).  c = v1 x v2 in the same form and det = ((c0 v3_0) + (c1 v3_1)) + (c2 v3_2); det < 0 negates v3.  The singular values
+ * are forced to (1, 1, 0): R_a = U W V^T, entry (r, c) = ((u2_r v1_c) - (u1_r v2_c)) + (u3_r v3_c); R_b = U W^T V^T, entry (r, c) =
+ * ((u1_r v2_c) - (u2_r v1_c)) + (u3_r v3_c); t = u3.  GOOD needs every entry of R_a, R_b, t, E and singular finite.  Candidates, in this
+ * order: 0 (R_a, +t), 1 (R_a, -t), 2 (R_b, +t), 3 (R_b, -t).  essential = E and singular as above where GOOD, zeros elsewhere.
+ * Vote, grid (parts, N), only for a GOOD image.  A pixel is a voter when it is KNOWN, r, g = SAMPSON(F, x, y, x', y') has g > 0 and
+ * (|r| / sqrt(g)) <= threshold -- RESIDUAL's inlier rule.  With RAYS and TRIANGULATE(R_a, t) and TRIANGULATE(R_b, t): candidate 0
+ * (2) gets the pixel's vote when den > 0, Z0 > 0 and Z1 > 0; candidate 1 (3) when den > 0, Z0 < 0 and Z1 < 0.  The counts are
+ * integers: a lane's registers, a butterfly over the wave, the four waves through the LDS, one integer atomic per count and
+ * workgroup -- the same in any order.
+ * Select, a lane per image: the winner is the candidate with the most votes, ties to the lowest index.  ok = 1 where the image is
+ * GOOD, voters > 0 and 2 votes[winner] > voters (an ambiguous vote is a failure); rotation and translation are the winner's
+ * (translation negated for candidates 1 and 3); where ok = 0 both are all zeros.  votes and voters are zeros where not GOOD.
+ * rotation N x 9, translation N x 3 doubles; ok N bytes; votes N x 4, voters N int32; singular N x 2, essential N x 9 doubles.
+ * workspace: pwc_camera_pose_workspace_bytes = 8 x 22 N (0 for N < 1 or N > 65535), 8-byte aligned.  No host synchronisation, no
+ * floating-point atomic; an image's result does not depend on its neighbours in the batch and two calls give the same bits.
+ * Checks: a null pointer but valid, N, H, W < 1, flow_cs < 2, a negative or NaN threshold (PWC_EINVAL); H W > 2^31 - 65537 or N >
+ * 65535 (PWC_ERANGE); flows, votes or voters off a 4-byte, any double array or the workspace off an 8-byte boundary (PWC_EALIGN);
+ * a workspace that is too small (PWC_EINVAL).
+ *
+ * DEPTH (pwc_triangulate_depth_f32), one launch, a lane per pixel (4096 workgroups of 256 lanes at most, grid-stride beyond),
+ * RESIDUAL's flow loads.  An image is OFF where all nine entries of its rotation are zero (what POSE writes with ok = 0) or its
+ * intrinsics are not FINE.  Per pixel RAYS and TRIANGULATE(R, t).  Where a2 > 0: ex = x' - ((fx (a0 / a2)) + cx), ey = y' - ((fy
+ * (a1 / a2)) + cy), pp = sqrt((ex ex) + (ey ey)): the distance in pixels between where the point is seen and where a point at
+ * infinity on the same ray would be; the relative error of the depth is about the flow's error over pp.  known = 1 and depth =
+ * (float)Z0, rounded once -- the depth in the FIRST camera in baselines -- where the image is not OFF, the pixel is KNOWN, a2 > 0,
+ * den > 0, Z0 > 0, Z1 > 0 and pp >= min_parallax; elsewhere known = 0 and depth = 1e10.  parallax (may be null) = (float)pp where
+ * the image is not OFF, the pixel is KNOWN and a2 > 0, else 0.  The epipolar constraint is NOT tested: a pixel that moves on its
+ * own gets a meaningless depth, so pass RESIDUAL's inlier as valid.  Checks: null pointers but valid and parallax, sizes < 1,
+ * flow_cs < 2, a negative or NaN min_parallax (PWC_EINVAL); the range as above (PWC_ERANGE); flows, depth or parallax off a
+ * 4-byte, rotation, translation or intrinsics off an 8-byte boundary (PWC_EALIGN).
+ *
+ * What this cannot do: the scale of t; a scene that moves; pixels near the epipole, where pp is small and the depth is noise; a
+ * camera that only rotates (FIT's ok = 0 upstream: F is all zeros and so is everything here). */
+size_t pwc_camera_pose_workspace_bytes(int N);
+int pwc_camera_pose_f64(const float* flows, int flow_cs, const uint8_t* valid, const double* matrices, const double* intrinsics,
+                        int N, int H, int W, double threshold, void* workspace, size_t workspace_bytes, double* rotation,
+                        double* translation, uint8_t* ok, int32_t* votes, int32_t* voters, double* singular, double* essential,
+                        pwc_stream_t stream);
+int pwc_triangulate_depth_f32(const float* flows, int flow_cs, const uint8_t* valid, const double* rotation,
+                              const double* translation, const double* intrinsics, int N, int H, int W, double min_parallax,
+                              float* depth, uint8_t* known, float* parallax, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

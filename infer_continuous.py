@@ -36,7 +36,12 @@ model for a camera that translates through depth -- motion.npy then holds the fu
 the homogeneous epipoles, --motion_residual writes <fname>_sampson.npy, every pixel's Sampson distance in pixels (1e10 where
 unknown), in place of the residual .flo, --regions and --regions_track go through pwcnet_amd.epipolar_regions with
 --regions_threshold as its threshold and the regions' mean flow itself in the table, and --stabilize and --plate, which need a
-point map, are refused).  --motion_iters K and --motion_scale C
+point map, are refused; --intrinsics FX FY CX CY, the camera's calibration in pixels, also writes <out>/pose.npy (pairs, 3, 4)
+float64, [R | t] of pwcnet_amd.camera_pose with X' = R X + t and |t| = 1, all zeros where <out>/pose_ok.npy (pairs,) bool is False,
+and with --depth, per pair, <fname>_depth.npy (float32, the depth in the first frame in baselines of THAT pair, 1e10 where unknown;
+pwcnet_amd.triangulate_depth on the inliers of pwcnet_amd.epipolar_residual) and <fname>_depth.png, 8-bit inverse depth scaled to
+the image's largest known inverse depth, 0 where unknown; --depth_min_parallax P switches pixels with less parallax off [0.25]).
+--motion_iters K and --motion_scale C
 are the reweighting passes [4] and the Cauchy scale in pixels [1.0].  --motion_residual also writes <fname>_residual.flo, the flow
 with that motion taken out (unknown pixels hold the .flo sentinel), and <fname>_inlier.png, white where a pixel moves with it.
 --stabilize R (needs --motion and frames of one size) smooths the camera path over 2 R + 1 frames (pwcnet_amd.smooth_path) and, in
@@ -139,6 +144,15 @@ def build_parser():
                     help="also write motion.npy / motion_ok.npy: the dominant motion of every pair, fitted robustly on the GPU; "
                          "homography: pwcnet_amd.fit_homography, and every flag below that uses the motion divides per pixel; "
                          "fundamental: pwcnet_amd.fit_fundamental, the epipolar model (also writes epipoles.npy; no --stabilize, no --plate) [off]")
+    ap.add_argument("--intrinsics", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
+                    help="--motion fundamental: the camera's focal lengths and principal point in pixels of the FRAMES (with --fit "
+                         "resize the flow is refitted to the frames' own grid, so these need no scaling); also write pose.npy "
+                         "(pairs, 3, 4), [R | t] with |t| = 1, and pose_ok.npy (pwcnet_amd.camera_pose) [off]")
+    ap.add_argument("--depth", action="store_true",
+                    help="--intrinsics: also write <fname>_depth.npy (float32 depth in baselines of that pair, 1e10 where unknown) "
+                         "and <fname>_depth.png (8-bit inverse depth, 0 where unknown) for every pair")
+    ap.add_argument("--depth_min_parallax", type=float, default=0.25, metavar="P",
+                    help="--depth: pixels with less than P pixels of parallax are unknown [0.25]")
     ap.add_argument("--motion_iters", type=int, default=4, metavar="K", help="--motion: reweighting passes, 0 .. 64 [4]")
     ap.add_argument("--motion_scale", type=float, default=1.0, metavar="C", help="--motion: the Cauchy scale in pixels [1.0]")
     ap.add_argument("--motion_residual", action="store_true",
@@ -216,6 +230,15 @@ def out_stem(path):
     """(dname, fname) of a frame's outputs under --out."""
     parts = re.split("[/.]", path)
     return parts[-3:-1] if len(parts) >= 3 else ("", parts[-2])
+
+
+def inverse_depth_picture(depth):
+    """--depth: the (H, W) uint8 picture of a downloaded depth map -- inverse depth over the image's largest known inverse depth,
+    times 255 and rounded; 0 where the depth is unknown (the 1e10 sentinel)."""
+    known = np.abs(depth) <= np.float32(1e9)
+    inverse = np.where(known, 1.0 / np.where(known, depth, np.float32(1.0)).astype(np.float64), 0.0)
+    top = inverse.max() if known.any() else 0.0
+    return np.rint(inverse * (255.0 / top)).astype(np.uint8) if top > 0.0 else np.zeros(depth.shape, np.uint8)
 
 
 class Chainer:
@@ -385,6 +408,12 @@ def main():
         ap.error("--motion_residual and --stabilize need --motion MODEL")
     if args.motion == "fundamental" and (args.stabilize != 0 or args.plate):
         ap.error("--stabilize and --plate need a point map; --motion fundamental is a constraint, not one: use affine or homography")
+    if args.intrinsics is not None and args.motion != "fundamental":
+        ap.error("--intrinsics needs --motion fundamental: the pose comes from the fundamental matrix")
+    if args.depth and args.intrinsics is None:
+        ap.error("--depth needs --intrinsics FX FY CX CY")
+    if not args.depth_min_parallax >= 0.0:
+        ap.error(f"--depth_min_parallax must be non-negative, got {args.depth_min_parallax}")
     if args.regions and args.motion is None:
         ap.error("--regions needs --motion MODEL")
     if args.regions_track and not args.regions:
@@ -452,6 +481,7 @@ def main():
     motions, motions_ok = [None] * (len(frames) - 1), [None] * (len(frames) - 1)
     epipolar = args.motion == "fundamental"
     epipoles = [None] * (len(frames) - 1) if epipolar else None
+    poses, poses_ok = ([None] * (len(frames) - 1), [None] * (len(frames) - 1)) if args.intrinsics is not None else (None, None)
     proj = {"projective": True} if args.motion == "homography" else {}       # the other models: the calls as they were
     if args.stabilize > 0 and any(f.shape != frames[0].shape for f in frames):
         raise ValueError("--stabilize needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
@@ -512,6 +542,19 @@ def main():
                 if epipolar:
                     matrices, ok, fit_info = pwcnet_amd.fit_fundamental(flow_final, iters=args.motion_iters, scale=args.motion_scale)
                     epipoles[i:j] = list(fit_info["epipole"].cpu().numpy())
+                    if poses is not None:            # the pose, flags and (--depth) the depth maps cross to the host
+                        rotation, translation, pose_ok, _ = pwcnet_amd.camera_pose(flow_final, matrices, args.intrinsics)
+                        poses[i:j] = list(torch.cat([rotation, translation[:, :, None]], dim=2).cpu().numpy())
+                        poses_ok[i:j] = list(pose_ok.cpu().numpy())
+                        if args.depth:
+                            inlier = pwcnet_amd.epipolar_residual(flow_final, matrices)[1]
+                            depth = pwcnet_amd.triangulate_depth(flow_final, rotation, translation, args.intrinsics, valid=inlier,
+                                                                 min_parallax=args.depth_min_parallax)[0].cpu().numpy()
+                            for k in range(j - i):
+                                dname, fname = out_stem(paths[i + k])
+                                os.makedirs(os.path.join(args.out, dname), exist_ok=True)
+                                np.save(os.path.join(args.out, dname, fname + "_depth.npy"), depth[k])
+                                Image.fromarray(inverse_depth_picture(depth[k])).save(os.path.join(args.out, dname, fname + "_depth.png"))
                 elif args.motion == "homography":
                     matrices, ok, _ = pwcnet_amd.fit_homography(flow_final, iters=args.motion_iters, scale=args.motion_scale)
                 else:
@@ -576,6 +619,9 @@ def main():
         np.save(os.path.join(args.out, "motion_ok.npy"), np.asarray(motions_ok, bool))
         if epipolar:
             np.save(os.path.join(args.out, "epipoles.npy"), np.stack(epipoles))
+        if poses is not None:
+            np.save(os.path.join(args.out, "pose.npy"), np.stack(poses))
+            np.save(os.path.join(args.out, "pose_ok.npy"), np.asarray(poses_ok, bool))
     if args.stabilize > 0:                           # the second pass: the frames again, batch by batch
         steady = pwcnet_amd.smooth_path(np.stack(motions), args.stabilize, **proj)
         for i in range(0, len(frames), max(1, args.batch)):

@@ -23,6 +23,8 @@ from . import regions  # noqa: F401
 from .regions import label_regions, moving_regions  # noqa: F401
 from . import fundamental  # noqa: F401
 from .fundamental import epipolar_regions, epipolar_residual, fit_fundamental  # noqa: F401
+from . import pose  # noqa: F401
+from .pose import camera_pose, flow_depth, triangulate_depth  # noqa: F401
 from . import region_tracks  # noqa: F401
 from .region_tracks import link_regions, region_identities, relabel_regions, track_regions  # noqa: F401
 from . import flow_filter  # noqa: F401
@@ -52,6 +54,7 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "motion", "fit_motion", "motion_residual", "warp_frames", "smooth_path", "homography", "fit_homography",
            "regions", "label_regions", "moving_regions",
            "fundamental", "fit_fundamental", "epipolar_residual", "epipolar_regions",
+           "pose", "camera_pose", "triangulate_depth", "flow_depth",
            "region_tracks", "link_regions", "region_identities", "relabel_regions", "track_regions",
            "flow_filter", "filter_tables", "filter_flow", "fill_flow",
            "temporal", "temporal_filter", "plan_windows",
