@@ -1743,6 +1743,82 @@ int pwc_triangulate_depth_f32(const float* flows, int flow_cs, const uint8_t* va
                               const double* translation, const double* intrinsics, int N, int H, int W, double min_parallax,
                               float* depth, uint8_t* known, float* parallax, pwc_stream_t stream);
 
+/* ==== scale chain and camera trajectory: one unit of length for the pairs of a sequence, and the camera's path in it ====
+ * (pwc_trajectory.hip, two_view.h; launch plan, digit choice, bytes and what is unmeasured in DESIGN.md 29.)  The T pairs of ONE
+ * sequence: pair j is frames j -> j + 1 with the pose (R_j, t_j), |t_j| = 1, and the depth map of "relative pose and depth" in the
+ * baseline b_j of that pair.  A SEAM j lies between pair j - 1 and pair j: a rigid point that pair j - 1 sees has two depths in
+ * camera j, Z1 in baselines of pair j - 1 and d in baselines of pair j, and Z1 / d = b_j / b_(j-1).  RAYS, TRIANGULATE, KNOWN and
+ * FINE are "relative pose and depth"'s; the same arithmetic rules hold: IEEE double + - x / in the order given, no fused
+ * multiply-add; floor is the only library call; tests/trajectory_ref.py restates both entry points in numpy bit for bit.
+ *
+ * LINKS (pwc_scale_links_f32).  Inputs: flows T x H x W records of flow_cs floats; rotation T x 9, translation T x 3, intrinsics
+ * T x 4 doubles; depth T x H x W floats and known T x H x W bytes as DEPTH wrote them.  Optionally ONE previous pair (prev_flow not
+ * null: prev_flow H x W records of prev_cs floats, prev_rotation, prev_translation, prev_intrinsics, prev_known; its depth map is not
+ * read): seam 0 then lies between it and pair 0.  Seams: 1 .. T - 1, and 0 with a previous pair.
+ * A seam is DEAD where either pair's rotation is all zeros (POSE's ok = 0) or the EARLIER pair's intrinsics are not FINE.
+ * SAMPLE of pixel p = (x, y) of the earlier pair, in this order; a failing step ends it (the pixel is no sample):
+ *   the seam is not DEAD; known[p] of the earlier pair is not 0; its flow (u, v) is KNOWN;
+ *   q = (qx, qy) = (x + u, y + v) in doubles lies in the frame: 0 <= qx <= W - 1 and 0 <= qy <= H - 1;
+ *   x0 = floor(qx), y0 = floor(qy), x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1); the LATER pair's known is not 0 at ALL FOUR
+ *   corners (y0, x0), (y0, x1), (y1, x0), (y1, x1), whatever their weight -- "flow composition"'s rule for a sample, not a second one;
+ *   wx1 = qx - x0, wy1 = qy - y0, wx0 = 1 - wx1, wy0 = 1 - wy1; with the later pair's depths widened to doubles
+ *   top = (wx0 D(y0,x0)) + (wx1 D(y0,x1)), bot = (wx0 D(y1,x0)) + (wx1 D(y1,x1)), d = (wy0 top) + (wy1 bot);
+ *   RAYS with the earlier pair's intrinsics (x' = qx, y' = qy) and TRIANGULATE with its pose: den > 0, Z1 > 0, d > 0;
+ *   r = (float)(Z1 / d), rounded once, is finite and > 0.
+ * WHICH WAY ROUND: r = Z1 / d = b_j / b_(j-1) is what multiplies scale[j - 1] to give scale[j], where scale[j] is pair j's baseline
+ * in the unit of its segment (TRAJECTORY); the quotient d / Z1 of the two depth maps is its reciprocal.
+ * samples[j] = n, the samples of seam j; ratio[j] = the sample of rank (n - 1) / 2 (integer division) in ascending order, the LOWER
+ * median; n = 0: ratio[j] = 0.  Without a previous pair ratio[0] = 0 and samples[0] = 0.
+ * The selection is exact.  The bits of a positive float32 order as unsigned integers do; the key of a pixel is the bits of r, 0 for
+ * no sample.  Digits: 11 bits (key >> 21), 11 bits ((key >> 10) & 2047), 10 bits (key & 1023).  Launches, each reading what the one
+ * before wrote: keys (grid (parts, seams), "dominant motion"'s partition: the keys into the workspace and the first digit's
+ * histogram), then per digit a select (a workgroup per seam: the bin b with before <= rank < before + count[b], bins in ascending
+ * order; rank -= before) and, for the second and third digit, a histogram of that digit over the keys whose higher digits are the
+ * chosen ones.  A workgroup's histogram is in the LDS and is merged into the seam's table with one integer atomic per non-empty bin.
+ * Integers only: the result is the same bits on every run; no floating-point atomic, no sort, no host synchronisation, no lane or
+ * workgroup waits for another.  A seam's result does not depend on the other seams.
+ * workspace: pwc_scale_links_workspace_bytes(T, H, W, has_prev) = 4 (seams (4 + 5120) + seams H W) + 16, 0 for a size < 1, H W >
+ * 2^26 or T > 65535; 8-byte aligned.  Checks: a null pointer but the prev_ ones, a previous pair that is given in part, sizes < 1, a
+ * channel stride < 2, a workspace that is too small (PWC_EINVAL); H W > 2^26 or T > 65535 (PWC_ERANGE); flows, depth, ratio or samples
+ * off a 4-byte, a double array or the workspace off an 8-byte boundary (PWC_EALIGN).
+ *
+ * TRAJECTORY (pwc_camera_trajectory_f64), one launch, one lane, the pairs in order.  OK(j): pair j's rotation is not all zeros.
+ * State before pair 0: [A | c] = [I | 0], scale = 0, seg = -1, opened = 0, before = false; or, with prev_rotation not null, [A | c] =
+ * prev_row (3 x 4 row-major), scale = prev_scale[0], seg = prev_segment[0], opened = prev_segment[1], before = (prev_rotation is not
+ * all zeros).  For j = 0 .. T - 1:
+ *   linked[j] = OK(j) and before and samples[j] >= min_samples and ratio[j] is finite and > 0;
+ *   OK(j) and not linked[j]: [A | c] = [I | 0] -- a new segment starts, the world frame restarts at this pair's first camera;
+ *   trajectory[j] = [A | c];
+ *   not OK(j): scale = 0, seg = -1;  linked[j]: scale = scale x (double)ratio[j];  else: scale = 1, seg = opened, opened += 1;
+ *   scales[j] = scale, segment[j] = seg;
+ *   OK(j): A <- R_j A, entry (r, q) = ((R_r0 A_0q) + (R_r1 A_1q)) + (R_r2 A_2q), and c_r <- (((R_r0 c_0) + (R_r1 c_1)) + (R_r2 c_2)) +
+ *   (scale t_r) (from the old c);  not OK(j): [A | c] = [I | 0];
+ *   before = OK(j).
+ * trajectory[T] = [A | c]; segment_state = (seg, opened).  trajectory is world-to-camera, X_cam_i = A_i X_world + c_i, the world
+ * being the first camera of the frame's segment and every length in the baseline of that segment's first pair: depth[j] x scales[j]
+ * is pair j's depth in that unit.  Frame j is the LAST camera of one segment and the FIRST of the next where a segment starts at
+ * pair j: its row holds [I | 0], the start.  The frame after a pair that is not OK holds [I | 0].
+ * STREAMING: a sequence fed in pieces, each call given the piece before's last pair as the previous pair of LINKS and trajectory[T]
+ * of that call, scales[T - 1] and segment_state as prev_row, prev_scale and prev_segment, gives the bits of one call; row 0 of a call
+ * is the final word on the frame it shares with the call before (it replaces that call's last row).
+ * trajectory (T + 1) x 12, scales T doubles; segment T int32; linked T bytes; segment_state 2 int32.  Checks: a null pointer but the
+ * prev_ ones, prev_rotation given without the other three, T < 1, min_samples < 1 (PWC_EINVAL); T > 65535 (PWC_ERANGE); a double
+ * array off an 8-byte, ratio, samples or an int32 array off a 4-byte boundary (PWC_EALIGN).
+ *
+ * What this cannot do: a point that moves along its epipolar line has a consistent but wrong depth in both pairs and is a sample; a
+ * pair that only rotates is not OK and breaks the chain (nothing bridges it); the scale is a running product, so its error grows with
+ * the length of the clip -- no loop closure, no refinement; segments do not share a unit. */
+size_t pwc_scale_links_workspace_bytes(int T, int H, int W, int has_prev);
+int pwc_scale_links_f32(const float* flows, int flow_cs, const double* rotation, const double* translation, const double* intrinsics,
+                        const float* depth, const uint8_t* known, int T, int H, int W, const float* prev_flow, int prev_cs,
+                        const double* prev_rotation, const double* prev_translation, const double* prev_intrinsics,
+                        const uint8_t* prev_known, void* workspace, size_t workspace_bytes, float* ratio, int32_t* samples,
+                        pwc_stream_t stream);
+int pwc_camera_trajectory_f64(const double* rotation, const double* translation, const float* ratio, const int32_t* samples, int T,
+                              int min_samples, const double* prev_rotation, const double* prev_row, const double* prev_scale,
+                              const int32_t* prev_segment, double* trajectory, double* scales, int32_t* segment, uint8_t* linked,
+                              int32_t* segment_state, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,14 @@ point map, are refused; --intrinsics FX FY CX CY, the camera's calibration in pi
 float64, [R | t] of pwcnet_amd.camera_pose with X' = R X + t and |t| = 1, all zeros where <out>/pose_ok.npy (pairs,) bool is False,
 and with --depth, per pair, <fname>_depth.npy (float32, the depth in the first frame in baselines of THAT pair, 1e10 where unknown;
 pwcnet_amd.triangulate_depth on the inliers of pwcnet_amd.epipolar_residual) and <fname>_depth.png, 8-bit inverse depth scaled to
-the image's largest known inverse depth, 0 where unknown; --depth_min_parallax P switches pixels with less parallax off [0.25]).
+the image's largest known inverse depth, 0 where unknown; --depth_min_parallax P switches pixels with less parallax off [0.25]);
+--trajectory (needs --intrinsics and frames of one size) chains the pairs' baselines on the GPU (pwcnet_amd.camera_trajectory,
+across batch boundaries; the depth maps are computed for it whether or not --depth is given) and writes <out>/trajectory.npy
+(frames, 3, 4) float64, world-to-camera [A | c] with X_cam = A X_world + c, the world being the first camera of the frame's segment,
+<out>/scale.npy (pairs,) float64, <out>/segment.npy (pairs,) int32 and <out>/scale_links.npy (pairs, 2) float64 with the columns
+ratio samples.  The --depth files stay in per-pair baselines: depth * scale[pair] is the depth in the unit of the pair's segment, the
+baseline of that segment's first pair; a pair without a pose has scale 0 and segment -1, and a seam with fewer than
+--trajectory_min_samples K samples [64] starts a new segment with a unit of its own.  Untuned, no loop closure: the scale drifts.
 --motion_iters K and --motion_scale C
 are the reweighting passes [4] and the Cauchy scale in pixels [1.0].  --motion_residual also writes <fname>_residual.flo, the flow
 with that motion taken out (unknown pixels hold the .flo sentinel), and <fname>_inlier.png, white where a pixel moves with it.
@@ -153,6 +160,11 @@ def build_parser():
                          "and <fname>_depth.png (8-bit inverse depth, 0 where unknown) for every pair")
     ap.add_argument("--depth_min_parallax", type=float, default=0.25, metavar="P",
                     help="--depth: pixels with less than P pixels of parallax are unknown [0.25]")
+    ap.add_argument("--trajectory", action="store_true",
+                    help="--intrinsics: also write trajectory.npy (frames, 3, 4), scale.npy, segment.npy and scale_links.npy: the "
+                         "pairs' baselines chained into one unit per segment and the camera's path, on the GPU")
+    ap.add_argument("--trajectory_min_samples", type=_positive_int, default=64, metavar="K",
+                    help="--trajectory: a seam links two pairs' scales only with at least K samples [64]")
     ap.add_argument("--motion_iters", type=int, default=4, metavar="K", help="--motion: reweighting passes, 0 .. 64 [4]")
     ap.add_argument("--motion_scale", type=float, default=1.0, metavar="C", help="--motion: the Cauchy scale in pixels [1.0]")
     ap.add_argument("--motion_residual", action="store_true",
@@ -345,6 +357,38 @@ class Denoiser:
                     del held[i]
 
 
+class PathChainer:
+    """--trajectory: takes the full-resolution flows, poses, depth maps and known masks of the pairs as they come, batch after
+    batch, chains their baselines (pwcnet_amd.camera_trajectory; the last pair stays on the GPU as the state) and keeps the rows on
+    the host; save() writes the four files."""
+
+    def __init__(self, nframes, intrinsics, min_samples, out):
+        self.intrinsics, self.min_samples, self.out = intrinsics, min_samples, out
+        self.state = None
+        self.trajectory = np.zeros((nframes, 3, 4), np.float64)
+        self.scale = np.zeros(nframes - 1, np.float64)
+        self.segment = np.zeros(nframes - 1, np.int32)
+        self.links = np.zeros((nframes - 1, 2), np.float64)
+
+    def add(self, first, flows, rotation, translation, depth, known):
+        import pwcnet_amd
+        n = flows.shape[0]
+        trajectory, scales, segment, info, state = pwcnet_amd.camera_trajectory(
+            flows, rotation, translation, self.intrinsics, depth, known, min_samples=self.min_samples, state=self.state)
+        state["flow"] = state["flow"].clone()        # (the replica writes its result buffer again at its next forward)
+        self.state = state
+        self.trajectory[first:first + n + 1] = trajectory.cpu().numpy()       # row 0 replaces the last row of the batch before
+        self.scale[first:first + n], self.segment[first:first + n] = scales.cpu().numpy(), segment.cpu().numpy()
+        self.links[first:first + n, 0], self.links[first:first + n, 1] = info["ratio"].cpu().numpy(), info["samples"].cpu().numpy()
+
+    def save(self):
+        os.makedirs(self.out, exist_ok=True)
+        np.save(os.path.join(self.out, "trajectory.npy"), self.trajectory)
+        np.save(os.path.join(self.out, "scale.npy"), self.scale)
+        np.save(os.path.join(self.out, "segment.npy"), self.segment)
+        np.save(os.path.join(self.out, "scale_links.npy"), self.links)
+
+
 class RegionTracker:
     """--regions_track: takes the labels, counts, tables and full-resolution flows of the pairs as they come, batch after batch,
     gives every region its identity (pwcnet_amd.track_regions; the last pair's labels, table, ids and flow stay on the GPU as
@@ -412,6 +456,8 @@ def main():
         ap.error("--intrinsics needs --motion fundamental: the pose comes from the fundamental matrix")
     if args.depth and args.intrinsics is None:
         ap.error("--depth needs --intrinsics FX FY CX CY")
+    if args.trajectory and (args.motion != "fundamental" or args.intrinsics is None):
+        ap.error("--trajectory needs --motion fundamental --intrinsics FX FY CX CY")
     if not args.depth_min_parallax >= 0.0:
         ap.error(f"--depth_min_parallax must be non-negative, got {args.depth_min_parallax}")
     if args.regions and args.motion is None:
@@ -478,6 +524,11 @@ def main():
     region_tracker = None
     if args.regions_track:
         region_tracker = RegionTracker(paths, args.out, args.regions_track_overlap, args.regions_track_fraction)
+    path_chainer = None
+    if args.trajectory:
+        if any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("--trajectory needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
+        path_chainer = PathChainer(len(frames), args.intrinsics, args.trajectory_min_samples, args.out)
     motions, motions_ok = [None] * (len(frames) - 1), [None] * (len(frames) - 1)
     epipolar = args.motion == "fundamental"
     epipoles = [None] * (len(frames) - 1) if epipolar else None
@@ -546,11 +597,14 @@ def main():
                         rotation, translation, pose_ok, _ = pwcnet_amd.camera_pose(flow_final, matrices, args.intrinsics)
                         poses[i:j] = list(torch.cat([rotation, translation[:, :, None]], dim=2).cpu().numpy())
                         poses_ok[i:j] = list(pose_ok.cpu().numpy())
-                        if args.depth:
+                        if args.depth or path_chainer is not None:
                             inlier = pwcnet_amd.epipolar_residual(flow_final, matrices)[1]
-                            depth = pwcnet_amd.triangulate_depth(flow_final, rotation, translation, args.intrinsics, valid=inlier,
-                                                                 min_parallax=args.depth_min_parallax)[0].cpu().numpy()
-                            for k in range(j - i):
+                            depth, depth_known = pwcnet_amd.triangulate_depth(flow_final, rotation, translation, args.intrinsics,
+                                                                              valid=inlier, min_parallax=args.depth_min_parallax)
+                            if path_chainer is not None:     # the maps stay on the GPU for it; four small arrays cross to the host
+                                path_chainer.add(i, flow_final, rotation, translation, depth, depth_known)
+                            depth = depth.cpu().numpy() if args.depth else None
+                            for k in range(j - i if args.depth else 0):
                                 dname, fname = out_stem(paths[i + k])
                                 os.makedirs(os.path.join(args.out, dname), exist_ok=True)
                                 np.save(os.path.join(args.out, dname, fname + "_depth.npy"), depth[k])
@@ -613,6 +667,8 @@ def main():
         tracker.save()
     if region_tracker is not None:
         region_tracker.save()
+    if path_chainer is not None:
+        path_chainer.save()
     if args.motion is not None:
         os.makedirs(args.out, exist_ok=True)
         np.save(os.path.join(args.out, "motion.npy"), np.stack(motions))

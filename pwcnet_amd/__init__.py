@@ -25,6 +25,8 @@ from . import fundamental  # noqa: F401
 from .fundamental import epipolar_regions, epipolar_residual, fit_fundamental  # noqa: F401
 from . import pose  # noqa: F401
 from .pose import camera_pose, flow_depth, triangulate_depth  # noqa: F401
+from . import trajectory  # noqa: F401
+from .trajectory import camera_trajectory, flow_trajectory  # noqa: F401
 from . import region_tracks  # noqa: F401
 from .region_tracks import link_regions, region_identities, relabel_regions, track_regions  # noqa: F401
 from . import flow_filter  # noqa: F401
@@ -55,6 +57,7 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "regions", "label_regions", "moving_regions",
            "fundamental", "fit_fundamental", "epipolar_residual", "epipolar_regions",
            "pose", "camera_pose", "triangulate_depth", "flow_depth",
+           "trajectory", "camera_trajectory", "flow_trajectory",
            "region_tracks", "link_regions", "region_identities", "relabel_regions", "track_regions",
            "flow_filter", "filter_tables", "filter_flow", "fill_flow",
            "temporal", "temporal_filter", "plan_windows",

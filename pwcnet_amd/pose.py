@@ -16,7 +16,7 @@ for bit (tests/pose_ref.py).  No autograd.
 
 Units: the length of a two-view translation cannot be observed, so translation has unit length and every depth is in BASELINES,
 multiples of the distance the camera moved between the two frames.  Each pair of a sequence has its own baseline and therefore its
-own scale: depths of different pairs are not comparable and nothing here chains them.
+own scale: depths of different pairs are not comparable until pwcnet_amd.trajectory has chained the scales.
 What this cannot do:
   * A camera that only rotates (or a flat scene) leaves F undetermined: fit_fundamental's ok is False upstream, its matrix is all
     zeros, and camera_pose then gives ok False and triangulate_depth an all-unknown map.
