@@ -1819,6 +1819,68 @@ int pwc_camera_trajectory_f64(const double* rotation, const double* translation,
                               const int32_t* prev_segment, double* trajectory, double* scales, int32_t* segment, uint8_t* linked,
                               int32_t* segment_state, pwc_stream_t stream);
 
+/* ==== pose refinement: the pose of "relative pose and depth" fitted to the Sampson distance of its inliers, five parameters ====
+ * (pwc_pose_refine.hip, two_view.h, motion_ldlt.h; launch plan, bytes and what is unmeasured in DESIGN.md 30.)  POSE stops at the
+ * closed form: an algebraic fit with eight unknowns, projected.  This is the textbook next step, a reweighted Gauss-Newton fit of
+ * the five parameters of (R, t), |t| = 1, to the Sampson distance in pixels over a FIXED set of pixels.  Flows, valid, KNOWN, the
+ * partition of the sums, the tree, the part order and the L D L^T elimination are "dominant motion"'s; RAYS, FINE and the vectors a,
+ * c, e of TRIANGULATE are "relative pose and depth"'s; the same arithmetic rules hold: IEEE double + - x / sqrt and comparisons in
+ * the order given, no fused multiply-add, sqrt the only library call; tests/pose_refine_ref.py restates it in numpy bit for bit.
+ * Inputs: flows, valid, intrinsics as POSE's; rotation0 N x 9 and translation0 N x 3 doubles as POSE wrote them (they are read in
+ * every pass and may not overlap an output).  An image is OFF where all nine entries of its rotation0 are zero or its intrinsics
+ * are not FINE: its outputs are all zeros, ok = 0, and its workgroups return before any pixel is read.
+ *
+ * EPIPOLAR(R, t, d0, d1): a, c, e as in TRIANGULATE; r = ((e0 a0) + (e1 a1)) + (e2 a2) (= d1 . (t x a) = d1^T E d0 with E = [t]x R);
+ * l0 = ((t1 a2) - (t2 a1)) / fx, l1 = ((t2 a0) - (t0 a2)) / fy (the first two entries of E d0 = t x a, taken to pixels); m0 =
+ * (((R_00 e0) + (R_10 e1)) + (R_20 e2)) / fx, m1 = (((R_01 e0) + (R_11 e1)) + (R_21 e2)) / fy (of E^T d1 = R^T e); g = (((l0 l0) +
+ * (l1 l1)) + (m0 m0)) + (m1 m1).  r r / g is the squared Sampson distance in pixels.
+ * BASIS(t): i the index of the entry of t smallest in magnitude, ties to the lowest index; v = e_i x t, that is (0, -t2, t1), (t2, 0,
+ * -t0) or (-t1, t0, 0); nrm = sqrt((p p) + (q q)) with (p, q) = (t2, t1), (t2, t0) or (t1, t0); b1 = v / nrm entry by entry (a negated
+ * entry is negated first; the zero entry is 0); b2 = t x b1 as b2_0 = (t1 b1_2) - (t2 b1_1), b2_1 = (t2 b1_0) - (t0 b1_2), b2_2 =
+ * (t0 b1_1) - (t1 b1_0).
+ * THE SET, the same in every pass: a pixel that is KNOWN, with RAYS and r, g = EPIPOLAR(rotation0, translation0) has g > 0 and
+ * (|r| / sqrt(g)) <= threshold.  threshold = +inf admits every known pixel with g > 0.  samples = the pixels of the set.
+ * PASS k = 0 .. iters against the pose theta_k = (R, t): theta_0 is the input, theta_k+1 what the solve of pass k wrote into the
+ * workspace (with BASIS of its t).  Per pixel of the set: r, g = EPIPOLAR(R, t); a pixel with !(g > 0) adds nothing to this pass;
+ * sg = sqrt(g), rho = r / sg, d2 = (r r) / g, w = 1 / (1 + (d2 / (scale scale))) -- the Cauchy weight; J0 = ((a1 e2) - (a2 e1)) / sg,
+ * J1 = ((a2 e0) - (a0 e2)) / sg, J2 = ((a0 e1) - (a1 e0)) / sg (a x e: the derivative of r by a left rotation of R), J3 = (-(((c0
+ * b1_0) + (c1 b1_1)) + (c2 b1_2))) / sg, J4 likewise with b2 (by a step of t along b1, b2): the derivative of rho with g HELD FIXED.
+ * With wJ_i = w J_i the 22 sums are S[i (i + 1) / 2 + j] += wJ_i J_j (j <= i: the triangle of sum w J J^T, 15), S[15 + i] += wJ_i rho
+ * (5), S[20] += w, S[21] += w d2 (the cost: sum of d2 / (1 + d2 / scale^2), Geman-McClure's bounded function), plus the integer
+ * count of the set; lanes in "dominant motion"'s lane order, ONE tree round over all 22 (22 x 256 doubles and 256 ints of LDS), and
+ * one lane per image adds the parts in index order.
+ * SOLVE of pass k, that lane.  Pass 0: ok = 1 where the image is not OFF and samples >= 5; else every output but samples is 0 and the
+ * image is frozen.  best = theta_0: rotation, translation = the input's bits, best_pass = 0, weight_sum = S[20], cost[0] = S[21].
+ * Pass k > 0 of an image that is not frozen: a sum that is not finite freezes the image (cost[k] = 0); else cost[k] = S[21] and,
+ * where S[21] < cost[best_pass] -- strictly: ties stay with the earlier pass --, rotation, translation = theta_k, best_pass = k,
+ * weight_sum = S[20].  A pass that a frozen image skips has cost 0.  For k < iters the STEP: the 5 x 5 system (sum w J J^T) x = -(sum
+ * w J rho), tr = (((S[0] + S[2]) + S[5]) + S[9]) + S[14], motion_ldlt at size 5 with the right-hand side (-S[15], .., -S[19]) and the
+ * pivot rule d > 1e-9 tr (a NaN fails); x = (omega (3), beta1, beta2).  UPDATE: a = omega / 2 entry by entry, q = ((a0 a0) + (a1
+ * a1)) + (a2 a2), p = 1 - q, den = 1 + q; the Cayley map C = ((1 - q) I + 2 a a^T + 2 [a]x) / den as C_ii = (p + (2 (a_i a_i))) / den,
+ * C_01 = ((2 (a0 a1)) - (2 a2)) / den, C_02 = ((2 (a0 a2)) + (2 a1)) / den, C_10 = ((2 (a1 a0)) + (2 a2)) / den, C_12 = ((2 (a1 a2)) -
+ * (2 a0)) / den, C_20 = ((2 (a2 a0)) - (2 a1)) / den, C_21 = ((2 (a2 a1)) + (2 a0)) / den -- rational, orthogonal up to rounding, no
+ * sine or cosine; R <- C R, entry (r, c) = ((C_r0 R_0c) + (C_r1 R_1c)) + (C_r2 R_2c); u_i = (t_i + (beta1 b1_i)) + (beta2 b2_i) with
+ * BASIS(t), t <- u / sqrt(((u0 u0) + (u1 u1)) + (u2 u2)).  A sum of pass 0 that is not finite, a failed pivot, or an entry of the new
+ * R or t that is not finite FREEZES the image: it keeps its best pose so far and its later passes add nothing.
+ * By construction iters = 0 returns the input pose bit for bit with its cost, and cost[best_pass] <= cost[0] for any iters.
+ * rotation N x 9, translation N x 3 doubles; ok N bytes; samples, best_pass N int32; cost N x (iters + 1), weight_sum N doubles; every
+ * element is written.  2 (iters + 1) launches on `stream`: sums on the grid (parts, N), then solve; no atomic, no host
+ * synchronisation, no process-wide state; an image's result does not depend on its neighbours in the batch and two calls give the
+ * same bits.  workspace: pwc_pose_refine_workspace_bytes = 8 (N parts 22 + N 19) + 4 N parts rounded up to 8 (0 for sizes the call
+ * refuses), 8-byte aligned.  Checks, in pwc_camera_pose_f64's order: a null pointer but valid, N, H, W < 1, iters outside 0 ..
+ * PWC_MOTION_MAX_ITERS, scale not > 0 (a NaN fails), a negative or NaN threshold, flow_cs < 2 (PWC_EINVAL); H W > 2^31 - 65537 or N >
+ * 65535 (PWC_ERANGE); flows, samples or best_pass off a 4-byte, any double array or the workspace off an 8-byte boundary
+ * (PWC_EALIGN); a workspace that is too small (PWC_EINVAL).
+ *
+ * What this cannot do: what the closed form cannot -- a point that moves along its epipolar line, a camera that only rotates (OFF
+ * here); it refines one pair at a time and no structure: no bundle adjustment over a sequence; a bad start stays bad (the set is
+ * chosen by the input pose).  scale, threshold, iters, the pivot rule and the fixed-g Jacobian are choices nobody has tuned. */
+size_t pwc_pose_refine_workspace_bytes(int N, int H, int W);
+int pwc_pose_refine_f64(const float* flows, int flow_cs, const uint8_t* valid, const double* intrinsics, const double* rotation0,
+                        const double* translation0, int N, int H, int W, int iters, double scale, double threshold, void* workspace,
+                        size_t workspace_bytes, double* rotation, double* translation, uint8_t* ok, int32_t* samples,
+                        int32_t* best_pass, double* cost, double* weight_sum, pwc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,10 @@ point map, are refused; --intrinsics FX FY CX CY, the camera's calibration in pi
 float64, [R | t] of pwcnet_amd.camera_pose with X' = R X + t and |t| = 1, all zeros where <out>/pose_ok.npy (pairs,) bool is False,
 and with --depth, per pair, <fname>_depth.npy (float32, the depth in the first frame in baselines of THAT pair, 1e10 where unknown;
 pwcnet_amd.triangulate_depth on the inliers of pwcnet_amd.epipolar_residual) and <fname>_depth.png, 8-bit inverse depth scaled to
-the image's largest known inverse depth, 0 where unknown; --depth_min_parallax P switches pixels with less parallax off [0.25]);
+the image's largest known inverse depth, 0 where unknown; --depth_min_parallax P switches pixels with less parallax off [0.25]); --pose_refine K (needs --intrinsics) refines every pose with K
+passes of pwcnet_amd.refine_pose before anything uses it: pose.npy, the depth maps and the --trajectory chain are then the refined
+poses', <out>/pose_closed.npy (pairs, 3, 4) keeps the closed form and <out>/pose_refine.npy (pairs, 4) float64 holds the rows
+samples best_pass cost_first cost_best; a pair whose refinement is not ok keeps the closed form;
 --trajectory (needs --intrinsics and frames of one size) chains the pairs' baselines on the GPU (pwcnet_amd.camera_trajectory,
 across batch boundaries; the depth maps are computed for it whether or not --depth is given) and writes <out>/trajectory.npy
 (frames, 3, 4) float64, world-to-camera [A | c] with X_cam = A X_world + c, the world being the first camera of the frame's segment,
@@ -155,6 +158,11 @@ def build_parser():
                     help="--motion fundamental: the camera's focal lengths and principal point in pixels of the FRAMES (with --fit "
                          "resize the flow is refitted to the frames' own grid, so these need no scaling); also write pose.npy "
                          "(pairs, 3, 4), [R | t] with |t| = 1, and pose_ok.npy (pwcnet_amd.camera_pose) [off]")
+    ap.add_argument("--pose_refine", type=int, default=0, metavar="K",
+                    help="--intrinsics: refine every pose with K passes of pwcnet_amd.refine_pose (the --motion_scale weight, the 1 px "
+                         "inlier gate); pose.npy, the --depth files and the --trajectory chain then use the refined poses, "
+                         "pose_closed.npy (pairs, 3, 4) keeps camera_pose's and pose_refine.npy (pairs, 4) holds the rows samples "
+                         "best_pass cost_first cost_best [0: off]")
     ap.add_argument("--depth", action="store_true",
                     help="--intrinsics: also write <fname>_depth.npy (float32 depth in baselines of that pair, 1e10 where unknown) "
                          "and <fname>_depth.png (8-bit inverse depth, 0 where unknown) for every pair")
@@ -456,6 +464,10 @@ def main():
         ap.error("--intrinsics needs --motion fundamental: the pose comes from the fundamental matrix")
     if args.depth and args.intrinsics is None:
         ap.error("--depth needs --intrinsics FX FY CX CY")
+    if args.pose_refine and args.intrinsics is None:
+        ap.error("--pose_refine needs --intrinsics FX FY CX CY")
+    if not 0 <= args.pose_refine <= 64:
+        ap.error(f"--pose_refine must be in 0 .. 64, got {args.pose_refine}")
     if args.trajectory and (args.motion != "fundamental" or args.intrinsics is None):
         ap.error("--trajectory needs --motion fundamental --intrinsics FX FY CX CY")
     if not args.depth_min_parallax >= 0.0:
@@ -533,6 +545,7 @@ def main():
     epipolar = args.motion == "fundamental"
     epipoles = [None] * (len(frames) - 1) if epipolar else None
     poses, poses_ok = ([None] * (len(frames) - 1), [None] * (len(frames) - 1)) if args.intrinsics is not None else (None, None)
+    poses_closed, poses_refine = [None] * (len(frames) - 1), [None] * (len(frames) - 1)      # --pose_refine
     proj = {"projective": True} if args.motion == "homography" else {}       # the other models: the calls as they were
     if args.stabilize > 0 and any(f.shape != frames[0].shape for f in frames):
         raise ValueError("--stabilize needs frames of one size" + (" after cropping" if args.fit == "crop" else ""))
@@ -595,6 +608,16 @@ def main():
                     epipoles[i:j] = list(fit_info["epipole"].cpu().numpy())
                     if poses is not None:            # the pose, flags and (--depth) the depth maps cross to the host
                         rotation, translation, pose_ok, _ = pwcnet_amd.camera_pose(flow_final, matrices, args.intrinsics)
+                        if args.pose_refine:         # the closed form is kept beside the refined pose
+                            poses_closed[i:j] = list(torch.cat([rotation, translation[:, :, None]], dim=2).cpu().numpy())
+                            refined, moved, refine_ok, refine_info = pwcnet_amd.refine_pose(
+                                flow_final, rotation, translation, args.intrinsics, iters=args.pose_refine, scale=args.motion_scale)
+                            rotation = torch.where(refine_ok[:, None, None], refined, rotation)
+                            translation = torch.where(refine_ok[:, None], moved, translation)
+                            cost = refine_info["cost"]
+                            cost_best = cost.gather(1, refine_info["best_pass"].long()[:, None])[:, 0]
+                            poses_refine[i:j] = list(torch.stack([refine_info["samples"].double(), refine_info["best_pass"].double(),
+                                                                  cost[:, 0], cost_best], dim=1).cpu().numpy())
                         poses[i:j] = list(torch.cat([rotation, translation[:, :, None]], dim=2).cpu().numpy())
                         poses_ok[i:j] = list(pose_ok.cpu().numpy())
                         if args.depth or path_chainer is not None:
@@ -677,6 +700,9 @@ def main():
             np.save(os.path.join(args.out, "epipoles.npy"), np.stack(epipoles))
         if poses is not None:
             np.save(os.path.join(args.out, "pose.npy"), np.stack(poses))
+            if args.pose_refine:
+                np.save(os.path.join(args.out, "pose_closed.npy"), np.stack(poses_closed))
+                np.save(os.path.join(args.out, "pose_refine.npy"), np.stack(poses_refine))
             np.save(os.path.join(args.out, "pose_ok.npy"), np.asarray(poses_ok, bool))
     if args.stabilize > 0:                           # the second pass: the frames again, batch by batch
         steady = pwcnet_amd.smooth_path(np.stack(motions), args.stabilize, **proj)

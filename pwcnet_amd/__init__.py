@@ -27,6 +27,8 @@ from . import pose  # noqa: F401
 from .pose import camera_pose, flow_depth, triangulate_depth  # noqa: F401
 from . import trajectory  # noqa: F401
 from .trajectory import camera_trajectory, flow_trajectory  # noqa: F401
+from . import pose_refine  # noqa: F401
+from .pose_refine import refine_pose  # noqa: F401
 from . import region_tracks  # noqa: F401
 from .region_tracks import link_regions, region_identities, relabel_regions, track_regions  # noqa: F401
 from . import flow_filter  # noqa: F401
@@ -58,6 +60,7 @@ __all__ = ["PWCDCNet", "ForwardPipeline", "PWCDCNetModule", "FeaturePyramidExtra
            "fundamental", "fit_fundamental", "epipolar_residual", "epipolar_regions",
            "pose", "camera_pose", "triangulate_depth", "flow_depth",
            "trajectory", "camera_trajectory", "flow_trajectory",
+           "pose_refine", "refine_pose",
            "region_tracks", "link_regions", "region_identities", "relabel_regions", "track_regions",
            "flow_filter", "filter_tables", "filter_flow", "fill_flow",
            "temporal", "temporal_filter", "plan_windows",

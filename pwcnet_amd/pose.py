@@ -5,7 +5,7 @@ field and how far away every rigid pixel is (csrc/pwc_pose.hip).
     triangulate_depth(flows, rotation, translation, intrinsics, valid=None,
                       min_parallax=0.25, return_parallax=False)                  -> (depth (N,H,W) f32, known (N,H,W) bool[, parallax])
     flow_depth(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0,
-               min_parallax=0.25)                                                -> (depth, known, rotation, translation, ok, info)
+               min_parallax=0.25, refine=0)                                      -> (depth, known, rotation, translation, ok, info)
 
 fit_fundamental says which pixels belong to the rigid scene.  With the intrinsics fx fy cx cy of the camera, in pixels of the
 flow's grid and the same for both frames, its matrix becomes the essential matrix E = K^T F K = [t]x R, whose closed-form
@@ -140,7 +140,7 @@ def triangulate_depth(flows, rotation, translation, intrinsics, valid=None, min_
     return depth, known.view(torch.bool)
 
 
-def flow_depth(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0, min_parallax=0.25):
+def flow_depth(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0, min_parallax=0.25, refine=0):
     """(depth, known, rotation, translation, ok, info): depth from flow in one call -- fit_fundamental(flows, valid, iters, scale),
     epipolar_residual(flows, matrices, valid, threshold), camera_pose(flows, matrices, intrinsics, valid, threshold) and
     triangulate_depth(flows, rotation, translation, intrinsics, valid=inlier, min_parallax), nothing in between.
@@ -148,10 +148,26 @@ def flow_depth(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0,
     depth (N,H,W) float32 in BASELINES, 1e10 where known (N,H,W) torch.bool is False: each pair of a sequence has its own scale.
     ok is camera_pose's; info is camera_pose's with "matrices", "fit_ok", "distance" and "inlier" added.  A camera that only rotates
     gives fit_fundamental's ok False upstream, hence ok False and an all-unknown map.  iters, scale: fit_fundamental's; threshold,
-    min_parallax and the half-the-voters rule are choices nobody has tuned on real video.  No autograd."""
+    min_parallax and the half-the-voters rule are choices nobody has tuned on real video.  No autograd.
+
+    refine = K > 0 runs pwcnet_amd.refine_pose(flows, rotation, translation, intrinsics, valid, iters=K, scale, threshold) between
+    camera_pose and triangulate_depth: rotation, translation and the depth are then the refined pose's, an image whose refinement is
+    not ok keeps camera_pose's, and info gains "closed_rotation", "closed_translation" (camera_pose's) and "refine_ok", "samples",
+    "best_pass", "cost", "weight_sum" (refine_pose's).  refine = 0, the default, is the call as it was: the same launches, the same
+    bits."""
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+        raise ValueError(f"refine: expected a non-negative integer, the passes of refine_pose, got {refine!r}")
     matrices, fit_ok, _ = fit_fundamental(flows, valid=valid, iters=iters, scale=scale)
     distance, inlier = epipolar_residual(flows, matrices, valid=valid, threshold=threshold)
     rotation, translation, ok, info = camera_pose(flows, matrices, intrinsics, valid=valid, threshold=threshold)
+    if refine > 0:
+        from .pose_refine import refine_pose
+        closed_rotation, closed_translation = rotation, translation
+        refined, moved, refine_ok, refine_info = refine_pose(flows, rotation, translation, intrinsics, valid=valid, iters=refine,
+                                                             scale=scale, threshold=threshold)
+        rotation = torch.where(refine_ok[:, None, None], refined, closed_rotation)
+        translation = torch.where(refine_ok[:, None], moved, closed_translation)
+        info = dict(info, closed_rotation=closed_rotation, closed_translation=closed_translation, refine_ok=refine_ok, **refine_info)
     depth, known = triangulate_depth(flows, rotation, translation, intrinsics, valid=inlier, min_parallax=min_parallax)
     info = dict(info, matrices=matrices, fit_ok=fit_ok, distance=distance, inlier=inlier)
     return depth, known, rotation, translation, ok, info

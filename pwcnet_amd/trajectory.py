@@ -3,7 +3,7 @@ it (csrc/pwc_trajectory.hip).
 
     camera_trajectory(flows, rotation, translation, intrinsics, depth, known, min_samples=64, state=None)
         -> (trajectory (T+1,3,4) f64, scales (T,) f64, segment (T,) int32, info, state)
-    flow_trajectory(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0, min_parallax=0.25, min_samples=64, state=None)
+    flow_trajectory(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0, min_parallax=0.25, min_samples=64, state=None, refine=0)
         -> (depth, known, trajectory, scales, segment, info, state)
 
 flows are the T consecutive flows of ONE sequence, pair j being frames j -> j + 1.  pose.flow_depth gives every pair a pose with
@@ -141,7 +141,8 @@ def camera_trajectory(flows, rotation, translation, intrinsics, depth, known, mi
     return trajectory, scales, segment, {"ratio": ratio, "samples": samples, "linked": linked.view(torch.bool)}, state
 
 
-def flow_trajectory(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0, min_parallax=0.25, min_samples=64, state=None):
+def flow_trajectory(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold=1.0, min_parallax=0.25, min_samples=64, state=None,
+                    refine=0):
     """(depth, known, trajectory, scales, segment, info, state): from the consecutive flows of ONE sequence to its depth maps and the
     camera's path in one call -- flow_depth(flows, intrinsics, valid, iters, scale, threshold, min_parallax), then
     camera_trajectory(flows, rotation, translation, intrinsics, depth, known, min_samples, state), nothing in between.
@@ -149,9 +150,10 @@ def flow_trajectory(flows, intrinsics, valid=None, iters=4, scale=1.0, threshold
     depth (T,H,W) float32 stays in each pair's OWN baseline, 1e10 where known is False: depth[j] * scales[j] is the depth in the
     unit of pair j's segment.  info is camera_trajectory's with flow_depth's added ("rotation", "translation", "ok" and its info).
     The limits are camera_trajectory's and flow_depth's; every threshold here is a choice nobody has tuned on real video.  No
-    autograd."""
+    autograd.  refine = K > 0 is flow_depth's: the poses are refined by K passes of refine_pose before the depth maps and the chain;
+    0, the default, is the call as it was."""
     depth, known, rotation, translation, ok, depth_info = flow_depth(flows, intrinsics, valid=valid, iters=iters, scale=scale,
-                                                                     threshold=threshold, min_parallax=min_parallax)
+                                                                     threshold=threshold, min_parallax=min_parallax, refine=refine)
     trajectory, scales, segment, info, state = camera_trajectory(flows, rotation, translation, intrinsics, depth, known,
                                                                  min_samples=min_samples, state=state)
     info = dict(depth_info, rotation=rotation, translation=translation, ok=ok, **info)
