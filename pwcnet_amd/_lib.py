@@ -23,7 +23,7 @@ HARNESS_SIGNATURES_NAMES = ("pwc_debug_cost_volume_blk_rows", "pwc_debug_conv3x3
 SOURCES = ["conv3x3_mfma.hip", "conv3x3_wino.hip", "conv3x3_direct.hip", "cost_volume.hip", "pwc_ops.hip",
            "pwc_backward.hip", "conv3x3_wgrad.hip", "conv3x3_h2.hip", "conv3x3_c16pair.hip", "conv3x3_sk.hip", "conv3x3_s2.hip", "conv3x3_t32.hip", "conv3x3_w32.hip",
            "pwc_flow_loss.hip", "pwc_unsup.hip", "pwc_census.hip", "pwc_ssim.hip", "pwc_fbcheck.hip", "pwc_fit.hip", "pwc_augment.hip", "pwc_splat.hip", "pwc_pyramid.hip", "pwc_featnorm.hip", "pwc_distill.hip", "pwc_compose.hip", "pwc_flowvis.hip", "pwc_track.hip", "pwc_interp.hip", "pwc_motion.hip", "pwc_regions.hip", "pwc_region_links.hip", "pwc_flow_filter.hip", "pwc_temporal.hip", "pwc_plate.hip", "pwc_homography.hip", "pwc_fundamental.hip", "pwc_pose.hip", "pwc_trajectory.hip", "pwc_pose_refine.hip"]
-HEADERS = ["pwc_common.h", "conv_fp32_common.h", "cost_volume_common.h", "loss_common.h", "motion_ldlt.h", "motion_jacobi.h", "two_view.h", "projective.h", "cost_volume_roll.hip", "cost_volume_mfma.hip", "cost_volume_h2.hip", "cost_volume_blk.hip", "conv3x3_wino4.hip", os.path.join("..", "..", "include", "pwc_hip.h")]
+HEADERS = ["pwc_common.h", "conv_fp32_common.h", "cost_volume_common.h", "loss_common.h", "motion_ldlt.h", "motion_jacobi.h", "two_view.h", "projective.h", "flow_record.h", "robust_fit.h", "cost_volume_roll.hip", "cost_volume_mfma.hip", "cost_volume_h2.hip", "cost_volume_blk.hip", "conv3x3_wino4.hip", os.path.join("..", "..", "include", "pwc_hip.h")]
 
 _vp, _i, _f, _l, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long, ctypes.c_size_t, ctypes.c_double
 

@@ -33,11 +33,8 @@ static inline int pwc_loss_sums_check(int N, int H, int W, int words, size_t wor
     if (workspace_floats < pwc_loss_workspace_floats(N, H, W, words)) return PWC_EINVAL;
     return PWC_OK;
 }
-// Workgroups of a gradient kernel over npix = N * H * W pixels: 256 lanes each, at most 4096 (grid-stride beyond).
-static inline dim3 pwc_loss_grad_blocks(int N, int H, int W) {
-    long blocks = ((long)N * H * W + 255) / 256;
-    return dim3((unsigned)(blocks > 4096 ? 4096 : blocks));
-}
+// Workgroups of a gradient kernel over npix = N * H * W pixels: pwc_common.h's flat grid.
+static inline dim3 pwc_loss_grad_blocks(int N, int H, int W) { return pwc_flat_grid((long)N * H * W); }
 
 // ---------------------------------------------------------------- device: sums
 // Sum of M floats and K ints over the 256 threads of a workgroup: t += t + k for k = 128, 64 .. 1, every quantity on its own,

@@ -6,14 +6,14 @@
 // For a last row of exactly 0 0 1, D is exactly 1 and the quotients have the bits of the affine path's sums.  A tiny positive D
 // gives a huge or infinite position, which the callers' in-frame comparisons reject -- what keeps their corner reads inside.
 #pragma once
-#include "pwc_common.h"
+#include "flow_record.h"
 
 #pragma clang fp contract(off)
 
 __device__ __forceinline__ bool pwc_projective_finite(const double* m, double* e) {
     bool good = true;
 #pragma unroll
-    for (int j = 0; j < 9; ++j) { e[j] = m[j]; good = good && fabs(e[j]) <= 1.7976931348623157e308; }   // (false for a NaN)
+    for (int j = 0; j < 9; ++j) { e[j] = m[j]; good = good && pwc_finite(e[j]); }
     return good;
 }
 

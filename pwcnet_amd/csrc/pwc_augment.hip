@@ -134,8 +134,6 @@ __global__ __launch_bounds__(AUG_TILE * AUG_TILE) void augment_pairs_kernel(
     out_valid[op] = ok ? 1 : 0;
 }
 
-inline bool aug_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 }  // namespace
 
 extern "C" int pwc_augment_pairs_f32(const void* im0, const void* im1, int im_is_u8, const float* flow, const unsigned char* valid,
@@ -144,9 +142,9 @@ extern "C" int pwc_augment_pairs_f32(const void* im0, const void* im1, int im_is
     if (!im0 || !im1 || !params || !out0 || !out1) return PWC_EINVAL;
     if (flow && (!out_flow || !out_valid)) return PWC_EINVAL;
     if (N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return PWC_EINVAL;
-    if (!im_is_u8 && (aug_off(im0, 3u) || aug_off(im1, 3u))) return PWC_EALIGN;
-    if (aug_off(out0, 3u) || aug_off(out1, 3u) || aug_off(params, 7u)) return PWC_EALIGN;
-    if (flow && (aug_off(flow, 7u) || aug_off(out_flow, 7u))) return PWC_EALIGN;
+    if (!im_is_u8 && (pwc_off(im0, 3u) || pwc_off(im1, 3u))) return PWC_EALIGN;
+    if (pwc_off(out0, 3u) || pwc_off(out1, 3u) || pwc_off(params, 7u)) return PWC_EALIGN;
+    if (flow && (pwc_off(flow, 7u) || pwc_off(out_flow, 7u))) return PWC_EALIGN;
     if ((long long)N * H * W >= (1ll << 31) || (long long)N * OH * OW >= (1ll << 31) || N > 65535 ||
         (OH + AUG_TILE - 1) / AUG_TILE > 65535)
         return PWC_ERANGE;

@@ -65,15 +65,13 @@ __global__ __launch_bounds__(256) void census_prepare_kernel(const CensusArgs a)
         // (every comparison is false for a NaN; an Inf fails one of them.)  The test keeps the four corner reads inside image n.
         const bool in = sx >= 0.0 && sx <= (double)(a.W - 1) && sy >= 0.0 && sy <= (double)(a.H - 1);
         if (in) {
-            const double fx0 = floor(sx), fy0 = floor(sy);
-            const int x0 = (int)fx0, y0 = (int)fy0;
-            const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);
-            const double wx1 = sx - fx0, wy1 = sy - fy0, wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+            const PwcBilinearF64 bl = pwc_bilinear_f64(sx, sy, a.H, a.W);
+            const double wx0 = bl.wx0, wx1 = bl.wx1, wy0 = bl.wy0, wy1 = bl.wy1;
             const size_t img = (size_t)px.n * a.H * a.W;
-            const float* p00 = a.im1 + (img + (size_t)y0 * a.W + x0) * a.im1_cs;
-            const float* p01 = a.im1 + (img + (size_t)y0 * a.W + x1) * a.im1_cs;
-            const float* p10 = a.im1 + (img + (size_t)y1 * a.W + x0) * a.im1_cs;
-            const float* p11 = a.im1 + (img + (size_t)y1 * a.W + x1) * a.im1_cs;
+            const float* p00 = a.im1 + (img + bl.o00) * a.im1_cs;
+            const float* p01 = a.im1 + (img + bl.o01) * a.im1_cs;
+            const float* p10 = a.im1 + (img + bl.o10) * a.im1_cs;
+            const float* p11 = a.im1 + (img + bl.o11) * a.im1_cs;
             double sb = 0.0, dx = 0.0, dy = 0.0;
 #pragma unroll
             for (int c = 0; c < C; ++c) {

@@ -47,6 +47,14 @@ static inline int pwc_cu_count() {
     return cus[dev];
 }
 
+// The flat grid of the one-lane-per-item kernels: workgroups of 256 lanes over `items`, at most 4096 (grid-stride beyond).
+static inline dim3 pwc_flat_grid(long items) {
+    const long blocks = (items + 255) / 256;
+    return dim3((unsigned)(blocks > 4096 ? 4096 : blocks));
+}
+
+// Whether p is off the boundary of mask + 1 bytes.
+static inline bool pwc_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 static inline bool pwc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // The argument checks the conv entry points share (F16 and fp32 matrix pipe), in the order they report: null pointers and non-positive
@@ -120,6 +128,24 @@ __device__ __forceinline__ f32x4 pwc_blend_corners(f32x4 w, f32x4 x00, f32x4 x01
     v = __builtin_elementwise_fma(f32x4{w[2], w[2], w[2], w[2]}, x10, v);
     v = __builtin_elementwise_fma(f32x4{w[3], w[3], w[3], w[3]}, x11, v);
     return v;
+}
+
+// ---- the bilinear corner table in doubles (the flow consumers, the label-free losses) of a position (sx, sy) INSIDE an H x W
+// image -- the caller's own inside test is what keeps the four reads in the image: the corners (y0, x0), (y0, x1), (y1, x0),
+// (y1, x1) as pixel offsets within the image, x1 and y1 clipped to the last column and row, and the weights along x and y from the
+// floors.  The inside test and the blend stay with each site.
+struct PwcBilinearF64 {
+    size_t o00, o01, o10, o11;
+    double wx0, wx1, wy0, wy1;
+};
+__device__ __forceinline__ PwcBilinearF64 pwc_bilinear_f64(double sx, double sy, int H, int W) {
+    const double fx0 = floor(sx), fy0 = floor(sy);
+    const int x0 = (int)fx0, y0 = (int)fy0;
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    PwcBilinearF64 k;
+    k.wx1 = sx - fx0; k.wy1 = sy - fy0; k.wx0 = 1.0 - k.wx1; k.wy0 = 1.0 - k.wy1;
+    k.o00 = (size_t)y0 * W + x0; k.o01 = (size_t)y0 * W + x1; k.o10 = (size_t)y1 * W + x0; k.o11 = (size_t)y1 * W + x1;
+    return k;
 }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a fence over global memory as well, which

@@ -23,8 +23,11 @@
 // gradient times that power of two.
 // One lane per pixel.  Flows at any channel stride >= 2: where every flow pointer of a call is on an 8-byte boundary and every
 // channel stride is even a pixel's two components are one 8-byte access, else two 4-byte ones -- the values fetched, and so
-// every bit, are the same (pwc_distill.hip's arrangement).
+// every bit, are the same (flow_record.h).
 #include "loss_common.h"
+#include "flow_record.h"
+
+#pragma clang fp contract(fast)   // (flow_record.h turns contraction off behind it; this file's arithmetic is contracted)
 
 struct ComposeArgs {
     const float* ab;          // [N][H][W] records of ab_cs floats, 2 used
@@ -43,27 +46,6 @@ struct ComposeArgs {
     int accumulate;
 };
 
-template <bool VEC>
-__device__ __forceinline__ void compose_load2(const float* p, float& a, float& b) {
-    if (VEC) {
-        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
-        a = v[0]; b = v[1];
-    } else {
-        a = p[0]; b = p[1];
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void compose_store2(float* p, float a, float b) {
-    if (VEC) {
-        *reinterpret_cast<f32x2*>(p) = f32x2{a, b};
-    } else {
-        p[0] = a; p[1] = b;
-    }
-}
-
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool compose_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-
 // What a valid pixel holds: f, the flat indices of its four corners in flow_bc, the weights along x and y, the corner values.
 struct ComposeSample {
     double f[2];
@@ -78,25 +60,22 @@ template <bool VEC>
 __device__ __forceinline__ bool compose_pixel(const ComposeArgs& a, int n, int y, int x, size_t pix, ComposeSample& s) {
     if (a.vab && !a.vab[pix]) return false;
     float f0, f1;
-    compose_load2<VEC>(a.ab + pix * a.ab_cs, f0, f1);
-    if (!compose_known(f0, f1)) return false;
+    pwc_flow_load2<VEC>(a.ab + pix * a.ab_cs, f0, f1);
+    if (!pwc_flow_known(f0, f1)) return false;
     const double qx = (double)x + (double)f0, qy = (double)y + (double)f1;
     if (!(qx >= 0.0 && qx <= (double)(a.W - 1) && qy >= 0.0 && qy <= (double)(a.H - 1))) return false;
-    const double fx0 = floor(qx), fy0 = floor(qy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);
-    s.wx1 = qx - fx0; s.wy1 = qy - fy0; s.wx0 = 1.0 - s.wx1; s.wy0 = 1.0 - s.wy1;
+    const PwcBilinearF64 bl = pwc_bilinear_f64(qx, qy, a.H, a.W);
+    s.wx1 = bl.wx1; s.wy1 = bl.wy1; s.wx0 = bl.wx0; s.wy0 = bl.wy0;
     const size_t img = (size_t)n * a.H * a.W;
-    s.o00 = img + (size_t)y0 * a.W + x0; s.o01 = img + (size_t)y0 * a.W + x1;
-    s.o10 = img + (size_t)y1 * a.W + x0; s.o11 = img + (size_t)y1 * a.W + x1;
+    s.o00 = img + bl.o00; s.o01 = img + bl.o01; s.o10 = img + bl.o10; s.o11 = img + bl.o11;
     if (a.vbc && !(a.vbc[s.o00] && a.vbc[s.o01] && a.vbc[s.o10] && a.vbc[s.o11])) return false;
     float c00[2], c01[2], c10[2], c11[2];
-    compose_load2<VEC>(a.bc + s.o00 * a.bc_cs, c00[0], c00[1]);
-    compose_load2<VEC>(a.bc + s.o01 * a.bc_cs, c01[0], c01[1]);
-    compose_load2<VEC>(a.bc + s.o10 * a.bc_cs, c10[0], c10[1]);
-    compose_load2<VEC>(a.bc + s.o11 * a.bc_cs, c11[0], c11[1]);
-    if (!(compose_known(c00[0], c00[1]) && compose_known(c01[0], c01[1]) && compose_known(c10[0], c10[1]) &&
-          compose_known(c11[0], c11[1])))
+    pwc_flow_load2<VEC>(a.bc + s.o00 * a.bc_cs, c00[0], c00[1]);
+    pwc_flow_load2<VEC>(a.bc + s.o01 * a.bc_cs, c01[0], c01[1]);
+    pwc_flow_load2<VEC>(a.bc + s.o10 * a.bc_cs, c10[0], c10[1]);
+    pwc_flow_load2<VEC>(a.bc + s.o11 * a.bc_cs, c11[0], c11[1]);
+    if (!(pwc_flow_known(c00[0], c00[1]) && pwc_flow_known(c01[0], c01[1]) && pwc_flow_known(c10[0], c10[1]) &&
+          pwc_flow_known(c11[0], c11[1])))
         return false;
     s.f[0] = (double)f0; s.f[1] = (double)f1;
 #pragma unroll
@@ -114,14 +93,14 @@ __global__ __launch_bounds__(256) void flow_compose_kernel(const ComposeArgs a) 
         const PwcLossPixel px = pwc_loss_pixel(p, a.H, a.W);
         ComposeSample s;
         const bool ok = compose_pixel<VEC>(a, px.n, px.y, px.x, (size_t)p, s);
-        float o0 = 1e10f, o1 = 1e10f;
+        float o0 = PWC_FLOW_SENTINEL, o1 = PWC_FLOW_SENTINEL;
         if (ok) {
             const double t0 = s.wx0 * s.v00[0] + s.wx1 * s.v01[0], b0 = s.wx0 * s.v10[0] + s.wx1 * s.v11[0];
             const double t1 = s.wx0 * s.v00[1] + s.wx1 * s.v01[1], b1 = s.wx0 * s.v10[1] + s.wx1 * s.v11[1];
             o0 = (float)(s.f[0] + (s.wy0 * t0 + s.wy1 * b0));
             o1 = (float)(s.f[1] + (s.wy0 * t1 + s.wy1 * b1));
         }
-        compose_store2<VEC>(a.out + p * a.out_cs, o0, o1);
+        pwc_flow_store2<VEC>(a.out + p * a.out_cs, o0, o1);
         a.vout[p] = ok ? 1 : 0;
     }
 }
@@ -153,7 +132,7 @@ __global__ __launch_bounds__(256) void flow_compose_max_kernel(const ComposeArgs
         ComposeSample s;
         if (!compose_pixel<VEC>(a, n, y, x, pix, s)) continue;
         float g0, g1;
-        compose_load2<VEC>(a.g + pix * a.g_cs, g0, g1);
+        pwc_flow_load2<VEC>(a.g + pix * a.g_cs, g0, g1);
         m = max(m, max(__float_as_uint(fabsf(g0)), __float_as_uint(fabsf(g1))));
     }
     const int t = threadIdx.x;
@@ -182,7 +161,7 @@ __global__ __launch_bounds__(256) void flow_compose_scatter_kernel(const Compose
             continue;
         }
         float gf0, gf1;
-        compose_load2<VEC>(a.g + p * a.g_cs, gf0, gf1);
+        pwc_flow_load2<VEC>(a.g + p * a.g_cs, gf0, gf1);
         const double g[2] = {(double)gf0, (double)gf1};
         // d S_k / d qx, d S_k / d qy: 0 where the clamp made the two corners one pixel (the difference of a value with itself)
         double dx = 0.0, dy = 0.0;
@@ -234,8 +213,6 @@ __global__ __launch_bounds__(256) void flow_compose_finish_kernel(const ComposeA
 }
 
 // ---------------------------------------------------------------- host
-static inline bool compose_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 // per pixel and channel an accumulator, per image the word of its maximum (8 bytes each)
 static inline size_t compose_fix_words(int N, int H, int W) { return (size_t)N * H * W * 2 + (size_t)N; }
 
@@ -250,12 +227,11 @@ extern "C" int pwc_flow_compose_f32(const float* flow_ab, int ab_cs, const float
     if (!flow_ab || !flow_bc || !flow_ac || !valid_ac || N < 1 || H < 1 || W < 1 || ab_cs < 2 || bc_cs < 2 || ac_cs < 2)
         return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (compose_off(flow_ab, 3u) || compose_off(flow_bc, 3u) || compose_off(flow_ac, 3u)) return PWC_EALIGN;
+    if (pwc_off(flow_ab, 3u) || pwc_off(flow_bc, 3u) || pwc_off(flow_ac, 3u)) return PWC_EALIGN;
     ComposeArgs a = {};
     a.ab = flow_ab; a.bc = flow_bc; a.vab = valid_ab; a.vbc = valid_bc; a.out = flow_ac; a.vout = valid_ac;
     a.ab_cs = ab_cs; a.bc_cs = bc_cs; a.out_cs = ac_cs; a.N = N; a.H = H; a.W = W;
-    const bool vec = !((ab_cs | bc_cs | ac_cs) & 1) && !compose_off(flow_ab, 7u) && !compose_off(flow_bc, 7u) &&
-                     !compose_off(flow_ac, 7u);
+    const bool vec = pwc_flow_vec(ab_cs | bc_cs | ac_cs, {flow_ab, flow_bc, flow_ac});
     const dim3 grid = pwc_loss_grad_blocks(N, H, W);
     if (vec) hipLaunchKernelGGL(flow_compose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(flow_compose_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -270,11 +246,11 @@ extern "C" int pwc_flow_compose_grad_f32(const float* flow_ab, int ab_cs, const 
         dab_cs < 2 || dbc_cs < 2)
         return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (compose_off(flow_ab, 3u) || compose_off(flow_bc, 3u) || compose_off(g, 3u) || compose_off(dflow_ab, 3u) ||
-        compose_off(dflow_bc, 3u))
+    if (pwc_off(flow_ab, 3u) || pwc_off(flow_bc, 3u) || pwc_off(g, 3u) || pwc_off(dflow_ab, 3u) ||
+        pwc_off(dflow_bc, 3u))
         return PWC_EALIGN;
     if (!workspace) return PWC_EINVAL;
-    if (compose_off(workspace, 7u)) return PWC_EALIGN;
+    if (pwc_off(workspace, 7u)) return PWC_EALIGN;
     if (workspace_bytes < pwc_flow_compose_grad_workspace_bytes(N, H, W)) return PWC_EINVAL;
     ComposeArgs a = {};
     a.ab = flow_ab; a.bc = flow_bc; a.vab = valid_ab; a.vbc = valid_bc; a.g = g; a.dab = dflow_ab; a.dbc = dflow_bc;
@@ -286,7 +262,7 @@ extern "C" int pwc_flow_compose_grad_f32(const float* flow_ab, int ab_cs, const 
     const hipError_t me = hipMemsetAsync(workspace, 0, compose_fix_words(N, H, W) * sizeof(long long), s);
     if (me != hipSuccess) { (void)hipGetLastError(); return (int)me; }          // the memset's OWN error, never PWC_OK
     // (dflow_ab and dflow_bc are stored 4 bytes at a time through pwc_grad_store2: their parity does not matter)
-    const bool vec = !((ab_cs | bc_cs | g_cs) & 1) && !compose_off(flow_ab, 7u) && !compose_off(flow_bc, 7u) && !compose_off(g, 7u);
+    const bool vec = pwc_flow_vec(ab_cs | bc_cs | g_cs, {flow_ab, flow_bc, g});
     const dim3 parts((unsigned)pwc_loss_parts(H, W), (unsigned)N);
     const dim3 grid = pwc_loss_grad_blocks(N, H, W);
     if (vec) {

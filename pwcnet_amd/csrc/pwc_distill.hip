@@ -18,6 +18,9 @@
 // Flows at any channel stride >= 2.  Where every flow pointer is on an 8-byte boundary and every channel stride is even a
 // pixel's two components are one 8-byte access, else two 4-byte ones: the values fetched, and so every bit, are the same.
 #include "loss_common.h"
+#include "flow_record.h"
+
+#pragma clang fp contract(fast)   // (flow_record.h turns contraction off behind it; this file's arithmetic is contracted)
 
 struct DistillArgs {
     const float* student;     // [N][h][w] records of s_cs floats, 2 used
@@ -34,16 +37,6 @@ struct DistillArgs {
     int accumulate;
 };
 
-template <bool VEC>
-__device__ __forceinline__ void distill_load2(const float* p, float& a, float& b) {
-    if (VEC) {
-        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
-        a = v[0]; b = v[1];
-    } else {
-        a = p[0]; b = p[1];
-    }
-}
-
 // Student pixel (n, y, x): whether it contributes, and then d = student - teacher per component (exact up to one double rounding).
 // The window check of the host (0 <= y0, y0 + h <= H, likewise x) is what keeps P inside image n of the teacher.
 template <bool VEC>
@@ -53,9 +46,9 @@ __device__ __forceinline__ bool distill_pixel(const DistillArgs& a, int n, int y
     if (a.exclude && a.exclude[p]) return false;
     if (a.tvalid && !a.tvalid[P]) return false;
     float s0, s1, t0, t1;
-    distill_load2<VEC>(a.teacher + P * a.t_cs, t0, t1);
-    if (!(fabsf(t0) <= 1e9f && fabsf(t1) <= 1e9f)) return false;                         // (false for a NaN, an Inf, the sentinel)
-    distill_load2<VEC>(a.student + p * a.s_cs, s0, s1);
+    pwc_flow_load2<VEC>(a.teacher + P * a.t_cs, t0, t1);
+    if (!pwc_flow_known(t0, t1)) return false;
+    pwc_flow_load2<VEC>(a.student + p * a.s_cs, s0, s1);
     if (!(fabsf(s0) < __builtin_inff() && fabsf(s1) < __builtin_inff())) return false;   // (false for a NaN)
     d[0] = (double)s0 - (double)t0;
     d[1] = (double)s1 - (double)t1;
@@ -147,8 +140,6 @@ extern "C" size_t pwc_flow_distill_workspace_bytes(int N, int h, int w) {
     return (size_t)N * pwc_loss_parts(h, w) * (sizeof(double) + sizeof(int));
 }
 
-static inline bool distill_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 // The checks both entry points share behind their own null checks, in the order they report.
 static int distill_check(const float* student, int s_cs, const float* teacher, int t_cs, int N, int h, int w, int H, int W, int y0,
                          int x0, double eps, double q) {
@@ -156,7 +147,7 @@ static int distill_check(const float* student, int s_cs, const float* teacher, i
     if (y0 < 0 || x0 < 0 || (long)y0 + h > H || (long)x0 + w > W) return PWC_EINVAL;       // the window inside the teacher
     if (!(eps > 0.0) || !(q > 0.0 && q <= 1.0)) return PWC_EINVAL;                          // (a NaN fails both)
     if (!pwc_loss_in_range(N, h, w) || !pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (distill_off(student, 3u) || distill_off(teacher, 3u)) return PWC_EALIGN;
+    if (pwc_off(student, 3u) || pwc_off(teacher, 3u)) return PWC_EALIGN;
     return PWC_OK;
 }
 
@@ -174,14 +165,14 @@ extern "C" int pwc_flow_distill_sums_f32(const float* student, int s_cs, const f
     const int rc = distill_check(student, s_cs, teacher, t_cs, N, h, w, H, W, y0, x0, eps, q);
     if (rc != PWC_OK) return rc;
     if (!sums || !counts || !workspace) return PWC_EINVAL;
-    if (distill_off(workspace, 7u)) return PWC_EALIGN;
+    if (pwc_off(workspace, 7u)) return PWC_EALIGN;
     if (workspace_bytes < pwc_flow_distill_workspace_bytes(N, h, w)) return PWC_EINVAL;
     const int parts = (int)pwc_loss_parts(h, w);
     DistillArgs a = {};
     distill_args(a, student, s_cs, teacher, t_cs, N, h, w, H, W, y0, x0, teacher_valid, exclude, eps, q);
     a.part = reinterpret_cast<double*>(workspace);
     a.part_n = reinterpret_cast<int*>(a.part + (size_t)N * parts);
-    const bool vec = !((s_cs | t_cs) & 1) && !distill_off(student, 7u) && !distill_off(teacher, 7u);
+    const bool vec = pwc_flow_vec(s_cs | t_cs, {student, teacher});
     const dim3 grid((unsigned)parts, (unsigned)N);
     const hipStream_t s = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(flow_distill_parts_kernel<true>, grid, dim3(256), 0, s, a);
@@ -198,11 +189,11 @@ extern "C" int pwc_flow_distill_grad_f32(const float* student, int s_cs, const f
     const int rc = distill_check(student, s_cs, teacher, t_cs, N, h, w, H, W, y0, x0, eps, q);
     if (rc != PWC_OK) return rc;
     if (!dsums || !dstudent || ds_cs < 2) return PWC_EINVAL;
-    if (distill_off(dsums, 3u) || distill_off(dstudent, 3u)) return PWC_EALIGN;
+    if (pwc_off(dsums, 3u) || pwc_off(dstudent, 3u)) return PWC_EALIGN;
     DistillArgs a = {};
     distill_args(a, student, s_cs, teacher, t_cs, N, h, w, H, W, y0, x0, teacher_valid, exclude, eps, q);
     a.dsums = dsums; a.dstudent = dstudent; a.d_cs = ds_cs; a.accumulate = accumulate ? 1 : 0;
-    const bool vec = !((s_cs | t_cs) & 1) && !distill_off(student, 7u) && !distill_off(teacher, 7u);
+    const bool vec = pwc_flow_vec(s_cs | t_cs, {student, teacher});
     const dim3 grid = pwc_loss_grad_blocks(N, h, w);
     const hipStream_t s = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(flow_distill_grad_kernel<true>, grid, dim3(256), 0, s, a);

@@ -40,15 +40,13 @@ __device__ __forceinline__ bool fb_pixel(const float* own, int own_cs, const flo
     const double px = (double)x + f0, py = (double)y + f1;
     // (every comparison is false for a NaN; an Inf fails one of them)
     if (!(px >= 0.0 && px <= (double)(W - 1) && py >= 0.0 && py <= (double)(H - 1))) return false;
-    const double fx0 = floor(px), fy0 = floor(py);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    const double wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+    const PwcBilinearF64 bl = pwc_bilinear_f64(px, py, H, W);
+    const double wx0 = bl.wx0, wx1 = bl.wx1, wy0 = bl.wy0, wy1 = bl.wy1;
     const size_t img = (size_t)n * H * W;
-    const float* p00 = other + (img + (size_t)y0 * W + x0) * other_cs;
-    const float* p01 = other + (img + (size_t)y0 * W + x1) * other_cs;
-    const float* p10 = other + (img + (size_t)y1 * W + x0) * other_cs;
-    const float* p11 = other + (img + (size_t)y1 * W + x1) * other_cs;
+    const float* p00 = other + (img + bl.o00) * other_cs;
+    const float* p01 = other + (img + bl.o01) * other_cs;
+    const float* p10 = other + (img + bl.o10) * other_cs;
+    const float* p11 = other + (img + bl.o11) * other_cs;
     double g[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -173,13 +171,11 @@ __device__ __forceinline__ bool fbc_pixel(const float* own, int own_cs, const fl
     const double px = (double)x + f0, py = (double)y + f1;
     // (every comparison is false for a NaN; an Inf fails one of them)
     if (!(px >= 0.0 && px <= (double)(W - 1) && py >= 0.0 && py <= (double)(H - 1))) return false;
-    const double fx0 = floor(px), fy0 = floor(py);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    const double wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+    const PwcBilinearF64 bl = pwc_bilinear_f64(px, py, H, W);
+    const double wx0 = bl.wx0, wx1 = bl.wx1, wy0 = bl.wy0, wy1 = bl.wy1;
     const size_t img = (size_t)n * H * W;
-    s.o00 = img + (size_t)y0 * W + x0; s.o01 = img + (size_t)y0 * W + x1;
-    s.o10 = img + (size_t)y1 * W + x0; s.o11 = img + (size_t)y1 * W + x1;
+    s.o00 = img + bl.o00; s.o01 = img + bl.o01;
+    s.o10 = img + bl.o10; s.o11 = img + bl.o11;
     s.w00 = wy0 * wx0; s.w01 = wy0 * wx1; s.w10 = wy1 * wx0; s.w11 = wy1 * wx1;
     const float* p00 = other + s.o00 * other_cs;
     const float* p01 = other + s.o01 * other_cs;

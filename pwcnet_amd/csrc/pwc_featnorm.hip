@@ -297,16 +297,14 @@ extern "C" int pwc_feature_norm_parts(int H, int W, int C) {
     return featnorm_parts(H, W, C);
 }
 
-static inline bool featnorm_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 // The checks both entry points share behind their own null / stride checks, in the order they report.
 static int featnorm_check(int N, int H, int W, int C, const void* stats, const void* workspace, size_t workspace_bytes) {
     if ((long)H * W * C >= (1L << 31) || N > 65535) return PWC_ERANGE;
-    if (featnorm_off(stats, 7u)) return PWC_EALIGN;
+    if (pwc_off(stats, 7u)) return PWC_EALIGN;
     const size_t need = pwc_feature_norm_workspace_bytes(N, H, W, C);
     if (need) {
         if (!workspace) return PWC_EINVAL;
-        if (featnorm_off(workspace, 7u)) return PWC_EALIGN;
+        if (pwc_off(workspace, 7u)) return PWC_EALIGN;
         if (workspace_bytes < need) return PWC_EINVAL;
     }
     return PWC_OK;
@@ -331,7 +329,7 @@ extern "C" int pwc_feature_norm_f32(const float* f0, int f0_cs, const float* f1,
                                     double* stats, pwc_stream_t stream) {
     if (!f0 || !f1 || !y0 || !y1 || !stats || N <= 0 || H <= 0 || W <= 0 || C <= 0) return PWC_EINVAL;
     if (f0_cs < C || f1_cs < C || y0_cs < C || y1_cs < C || !(eps >= 0.0)) return PWC_EINVAL;
-    if (featnorm_off(f0, 3u) || featnorm_off(f1, 3u) || featnorm_off(y0, 3u) || featnorm_off(y1, 3u)) return PWC_EALIGN;
+    if (pwc_off(f0, 3u) || pwc_off(f1, 3u) || pwc_off(y0, 3u) || pwc_off(y1, 3u)) return PWC_EALIGN;
     const int rc = featnorm_check(N, H, W, C, stats, workspace, workspace_bytes);
     if (rc != PWC_OK) return rc;
     FeatNormArgs a = {};
@@ -363,8 +361,8 @@ extern "C" int pwc_feature_norm_grad_f32(const float* f0, int f0_cs, const float
                                          int accumulate, pwc_stream_t stream) {
     if (!f0 || !f1 || !g0 || !g1 || !d0 || !d1 || !stats || N <= 0 || H <= 0 || W <= 0 || C <= 0) return PWC_EINVAL;
     if (f0_cs < C || f1_cs < C || g0_cs < C || g1_cs < C || d0_cs < C || d1_cs < C) return PWC_EINVAL;
-    if (featnorm_off(f0, 3u) || featnorm_off(f1, 3u) || featnorm_off(g0, 3u) || featnorm_off(g1, 3u) || featnorm_off(d0, 3u) ||
-        featnorm_off(d1, 3u))
+    if (pwc_off(f0, 3u) || pwc_off(f1, 3u) || pwc_off(g0, 3u) || pwc_off(g1, 3u) || pwc_off(d0, 3u) ||
+        pwc_off(d1, 3u))
         return PWC_EALIGN;
     const int rc = featnorm_check(N, H, W, C, stats, workspace, workspace_bytes);
     if (rc != PWC_OK) return rc;

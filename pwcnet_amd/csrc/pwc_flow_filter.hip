@@ -23,7 +23,9 @@
 // Every lane runs the same trip counts; no loop waits for another lane.  All sums are exact integers: the order cannot matter.
 // The passes of iters > 1 alternate between the workspace and out so that the last one writes out; every pass reads the field and
 // the mask of the pass before.
-#include "pwc_common.h"
+#include "flow_record.h"
+
+#pragma clang fp contract(fast)   // (flow_record.h turns contraction off behind it; this file's arithmetic is contracted)
 
 constexpr int FILTER_TW = 32, FILTER_TH = 8;          // centres of a tile: one per lane of the 256
 constexpr int FILTER_MAX_TILES_X = 1024;              // workgroups per image, tile-stride beyond
@@ -48,7 +50,8 @@ struct FilterArgs {
 __device__ __forceinline__ unsigned filter_key(unsigned b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
 __device__ __forceinline__ unsigned filter_unkey(unsigned k) { return (k >> 31) ? (k ^ 0x80000000u) : ~k; }
 
-// A float guide value as a byte: rint(clamp(255 v, 0, 255)) in double, ties to even, 0 for a NaN.
+// A float guide value as a byte: rint(clamp(255 v, 0, 255)) in double, ties to even, 0 for a NaN.  Not pwc_round_byte: the clamp
+// comes before the rint.
 __device__ __forceinline__ unsigned filter_byte(float v) {
     const double t = (double)v * 255.0;
     const double c = t >= 255.0 ? 255.0 : (t >= 0.0 ? t : 0.0);           // (both comparisons are false for a NaN)
@@ -89,7 +92,7 @@ __device__ __forceinline__ void filter_stage(const FilterArgs& a, int n, int ty0
             const float* f = a.flow + p * a.flow_cs;
             const float fu = f[0], fv = f[1];
             // the .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel
-            const bool known = (!a.valid || a.valid[p]) && fabsf(fu) <= 1e9f && fabsf(fv) <= 1e9f;
+            const bool known = (!a.valid || a.valid[p]) && pwc_flow_known(fu, fv);
             u = filter_key(__float_as_uint(fu));
             v = filter_key(__float_as_uint(fv));
             g = filter_guide(a, p) | (known ? FILTER_KNOWN : 0u);
@@ -223,15 +226,13 @@ __global__ __launch_bounds__(256) void flow_filter_kernel(const FilterArgs a) {
         }
         const size_t p = ((size_t)n * a.H + y) * a.W + x;
         float* o = a.out + p * a.out_cs;
-        o[0] = ok ? __uint_as_float(filter_unkey(ou)) : 1e10f;
-        o[1] = ok ? __uint_as_float(filter_unkey(ov)) : 1e10f;
+        o[0] = ok ? __uint_as_float(filter_unkey(ou)) : PWC_FLOW_SENTINEL;
+        o[1] = ok ? __uint_as_float(filter_unkey(ov)) : PWC_FLOW_SENTINEL;
         a.out_valid[p] = ok ? 1 : 0;
     }
 }
 
 // ---------------------------------------------------------------- host
-static inline bool filter_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 // Whether [p, p + bytes_p) and [q, q + bytes_q) share a byte (sizes as 128-bit numbers: N H W cs 4 may pass 2^64).
 static inline bool filter_overlap(const void* p, unsigned __int128 bytes_p, const void* q, unsigned __int128 bytes_q) {
     const unsigned __int128 a0 = reinterpret_cast<uintptr_t>(p), b0 = reinterpret_cast<uintptr_t>(q);
@@ -270,8 +271,8 @@ extern "C" int pwc_flow_filter_f32(const float* flows, int flow_cs, const uint8_
     const size_t bytes = pwc_flow_filter_workspace_bytes(N, H, W, iters);
     if (bytes && (!workspace || workspace_bytes < bytes)) return PWC_EINVAL;
     if (!filter_in_range(N, H, W)) return PWC_ERANGE;
-    if (filter_off(flows, 3u) || filter_off(out, 3u) || filter_off(space_table, 3u) || (guide && filter_off(color_table, 3u)) ||
-        (guide && guide_dtype == PWC_FLOW_FILTER_F32 && filter_off(guide, 3u)) || (bytes && filter_off(workspace, 7u)))
+    if (pwc_off(flows, 3u) || pwc_off(out, 3u) || pwc_off(space_table, 3u) || (guide && pwc_off(color_table, 3u)) ||
+        (guide && guide_dtype == PWC_FLOW_FILTER_F32 && pwc_off(guide, 3u)) || (bytes && pwc_off(workspace, 7u)))
         return PWC_EALIGN;
     FilterArgs a = {};
     a.guide = guide; a.space = space_table; a.color = color_table;

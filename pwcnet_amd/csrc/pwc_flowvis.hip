@@ -21,6 +21,7 @@
 // off a 4-byte boundary, is written byte by byte.
 #include <float.h>
 
+#include "flow_record.h"
 #include "loss_common.h"
 
 #pragma clang fp contract(off)
@@ -54,17 +55,11 @@ struct VisArgs {
 
 __device__ __forceinline__ unsigned vis_pack(unsigned r, unsigned g, unsigned b) { return r | (g << 8) | (b << 16); }
 
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool vis_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-
 // The flow of a record times the scale: one float32 product per component (1.0f changes nothing).
 __device__ __forceinline__ void vis_load_flow(const float* p, float scale, float& u, float& v) {
     u = pwc_mul_rounded(p[0], scale);
     v = pwc_mul_rounded(p[1], scale);
 }
-
-// A double in [0, 255] (whatever else it is: 0 for a NaN) as a byte.
-__device__ __forceinline__ unsigned vis_byte(double t) { return t >= 255.0 ? 255u : (t >= 0.0 ? (unsigned)(int)t : 0u); }
 
 // flow_io.flow_to_color for one pixel whose unknown / masked flow has been replaced by (0, 0).
 __device__ __forceinline__ unsigned vis_flow_color(double u, double v, double max_rad) {
@@ -81,7 +76,7 @@ __device__ __forceinline__ unsigned vis_flow_color(double u, double v, double ma
     for (int j = 0; j < 3; ++j) {
         double col = (1.0 - f) * (double)vis_wheel[k0][j] / 255.0 + f * (double)vis_wheel[k1][j] / 255.0;
         col = rad <= 1.0 ? 1.0 - rad * (1.0 - col) : col * 0.75;
-        c[j] = vis_byte(floor(255.0 * col));
+        c[j] = pwc_clamp_byte(floor(255.0 * col));
     }
     return vis_pack(c[0], c[1], c[2]);
 }
@@ -89,7 +84,7 @@ __device__ __forceinline__ unsigned vis_flow_color(double u, double v, double ma
 // The error map's pixel: gt known (and valid), (pu, pv) the prediction.
 __device__ __forceinline__ unsigned vis_error_color(float pu, float pv, float gu, float gv) {
     int bin = 9;
-    if (vis_known(pu, pv)) {
+    if (pwc_flow_known(pu, pv)) {
         const double du = (double)pu - (double)gu, dv = (double)pv - (double)gv;
         const double d_err = sqrt(du * du + dv * dv);
         const double d_mag = sqrt((double)gu * (double)gu + (double)gv * (double)gv);
@@ -123,14 +118,14 @@ __device__ __forceinline__ unsigned vis_pixel(const VisArgs& a, long g) {
     }
     if (t.kind == PWC_VIS_FRAME_F32) {
         const float* p = reinterpret_cast<const float*>(t.src) + pix * 3;
-        return vis_pack(vis_byte(rint(255.0 * (double)p[0])), vis_byte(rint(255.0 * (double)p[1])),
-                        vis_byte(rint(255.0 * (double)p[2])));
+        return vis_pack(pwc_clamp_byte(rint(255.0 * (double)p[0])), pwc_clamp_byte(rint(255.0 * (double)p[1])),
+                        pwc_clamp_byte(rint(255.0 * (double)p[2])));
     }
     if (t.kind == PWC_VIS_ERROR) {
         if (t.valid && !t.valid[pix]) return 0u;
         const float* gp = t.gt + pix * t.gt_cs;
         const float gu = gp[0], gv = gp[1];
-        if (!vis_known(gu, gv)) return 0u;
+        if (!pwc_flow_known(gu, gv)) return 0u;
         const float* pp = reinterpret_cast<const float*>(t.src) + pix * t.src_cs;
         return vis_error_color(pp[0], pp[1], gu, gv);
     }
@@ -138,7 +133,7 @@ __device__ __forceinline__ unsigned vis_pixel(const VisArgs& a, long g) {
     if (!(t.valid && !t.valid[pix])) {
         float uf, vf;
         vis_load_flow(reinterpret_cast<const float*>(t.src) + pix * t.src_cs, t.flow_scale, uf, vf);
-        if (vis_known(uf, vf)) { u = (double)uf; v = (double)vf; }
+        if (pwc_flow_known(uf, vf)) { u = (double)uf; v = (double)vf; }
     }
     return vis_flow_color(u, v, t.max_rad[n]);
 }
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(256) void flow_max_radius_kernel(const float* __res
         if (valid && !valid[pix]) continue;
         float uf, vf;
         vis_load_flow(flow + pix * cs, scale, uf, vf);
-        if (!vis_known(uf, vf)) continue;
+        if (!pwc_flow_known(uf, vf)) continue;
         const double u = (double)uf, v = (double)vf;
         const unsigned long long b = (unsigned long long)__double_as_longlong(sqrt(u * u + v * v));
         m = b > m ? b : m;
@@ -193,8 +188,6 @@ __global__ __launch_bounds__(256) void flow_max_radius_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------- host
-static inline bool vis_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 extern "C" int pwc_flow_vis_wheel_u8(uint8_t* wheel) {
     if (!wheel) return PWC_EINVAL;
     for (int k = 0; k < VIS_WHEEL_N; ++k)
@@ -206,7 +199,7 @@ extern "C" int pwc_flow_max_radius_f64(const float* flow, int flow_cs, const uin
                                        double* max_rad, pwc_stream_t stream) {
     if (!flow || !max_rad || N < 1 || H < 1 || W < 1 || flow_cs < 2) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (vis_off(flow, 3u) || vis_off(max_rad, 7u)) return PWC_EALIGN;
+    if (pwc_off(flow, 3u) || pwc_off(max_rad, 7u)) return PWC_EALIGN;
     const hipStream_t s = (hipStream_t)stream;
     const hipError_t me = hipMemsetAsync(max_rad, 0, (size_t)N * sizeof(double), s);
     if (me != hipSuccess) { (void)hipGetLastError(); return (int)me; }          // the memset's OWN error, never PWC_OK
@@ -235,14 +228,14 @@ extern "C" int pwc_flow_vis_tiles_u8(const pwc_vis_tile* tiles, int ntiles, int 
         if (!pwc_loss_in_range(N, tiles[k].src_h, tiles[k].src_w)) return PWC_ERANGE;
     for (int k = 0; k < ntiles; ++k) {
         const pwc_vis_tile& t = tiles[k];
-        if (t.kind != PWC_VIS_FRAME_U8 && vis_off(t.src, 3u)) return PWC_EALIGN;
-        if (t.kind == PWC_VIS_ERROR && vis_off(t.gt, 3u)) return PWC_EALIGN;
-        if (t.kind == PWC_VIS_FLOW && vis_off(t.max_rad, 7u)) return PWC_EALIGN;
+        if (t.kind != PWC_VIS_FRAME_U8 && pwc_off(t.src, 3u)) return PWC_EALIGN;
+        if (t.kind == PWC_VIS_ERROR && pwc_off(t.gt, 3u)) return PWC_EALIGN;
+        if (t.kind == PWC_VIS_FLOW && pwc_off(t.max_rad, 7u)) return PWC_EALIGN;
     }
     VisArgs a = {};
     for (int k = 0; k < ntiles; ++k) a.t[k] = tiles[k];
     a.out = out; a.npix = (long)N * out_h * out_w; a.ntiles = ntiles; a.out_h = out_h; a.out_w = out_w;
-    a.dwords = vis_off(out, 3u) ? 0 : 1;
+    a.dwords = pwc_off(out, 3u) ? 0 : 1;
     const long blocks = ((a.npix + 3) / 4 + 255) / 256;
     hipLaunchKernelGGL(flow_vis_tiles_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, (hipStream_t)stream, a);
     return pwc_launch_status();

@@ -7,9 +7,9 @@
 //                                         epipole (N, 3) doubles
 //   pwc_epipolar_residual_f32             distance (N, H, W) floats and inlier (N, H, W) bytes
 //
-// The pass structure is pwc_homography_fit_f64's: iters + 1 passes of two launches each on the caller's stream, the device reading
+// The pass structure is robust_fit.h's: iters + 1 passes of two launches each on the caller's stream, the device reading
 // what the pass before wrote.
-//   sums    grid (parts, N), loss_common.h's partition.  A known pixel (pwc_motion.hip's rule) has xh, yh, x', y' as the homography
+//   sums    grid (parts, N), loss_common.h's partition.  A known pixel (flow_record.h's rule) has xh, yh, x', y' as the homography
 //           fit has them and contributes w a a^T, a = (x' xh, x' yh, x', y' xh, y' yh, y', xh, yh, 1).  The 45 entries of the lower
 //           triangle are 36 distinct monomials, {1, x', y', x'x', x'y', y'y'} x {1, xh, yh, xh xh, xh yh, yh yh}: 36 sums, ONE tree
 //           round of pwc_block_tree_sum_f64<36, 1> -- 36 x 256 doubles and 256 ints are 74,752 B of LDS (gfx950 has 160 KB a CU).
@@ -20,41 +20,17 @@
 // Every value is an IEEE double + - x / sqrt or a comparison in the order written here -- no fused multiply-add is formed anywhere
 // in this file (the pragma below), sqrt on doubles (correctly rounded, as pwc_flowvis.hip relies on) is the only library call -- so
 // tests/fundamental_ref.py restates it in numpy bit for bit.  No atomic, no host synchronisation, no process-wide state.  Flows at
-// any channel stride >= 2, loaded as pwc_motion.hip loads them.
-#include "loss_common.h"
+// any channel stride >= 2, loaded as flow_record.h loads them.  The Sampson terms r and g are two_view.h's, the one order both the
+// weights and the residual use.
 #include "motion_jacobi.h"
+#include "robust_fit.h"
+#include "two_view.h"
 
 #pragma clang fp contract(off)
 
 #define FUNDAMENTAL_EIGEN_FLOOR 1e-9
 #define FUNDAMENTAL_SUMS 36
 #define FUNDAMENTAL_MIN_COUNT 8
-#define FUNDAMENTAL_SENTINEL 1e10f
-#define FUNDAMENTAL_MAX_BLOCKS 4096
-
-template <bool VEC>
-__device__ __forceinline__ void fundamental_load2(const float* p, float& a, float& b) {
-    if (VEC) {
-        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
-        a = v[0]; b = v[1];
-    } else {
-        a = p[0]; b = p[1];
-    }
-}
-
-__device__ __forceinline__ bool fundamental_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-__device__ __forceinline__ bool fundamental_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // (false for a NaN)
-
-// r = p'^T F p and g = l0^2 + l1^2 + l'0^2 + l'1^2 with l = F p, l' = F^T p': the one order both the weights and the residual use.
-__device__ __forceinline__ void fundamental_sampson(const double* f, double x, double y, double xp, double yp, double& r, double& g) {
-    const double l0 = ((f[0] * x) + (f[1] * y)) + f[2];
-    const double l1 = ((f[3] * x) + (f[4] * y)) + f[5];
-    const double l2 = ((f[6] * x) + (f[7] * y)) + f[8];
-    r = ((xp * l0) + (yp * l1)) + l2;
-    const double m0 = ((f[0] * xp) + (f[3] * yp)) + f[6];
-    const double m1 = ((f[1] * xp) + (f[4] * yp)) + f[7];
-    g = (((l0 * l0) + (l1 * l1)) + (m0 * m0)) + (m1 * m1);
-}
 
 struct FundamentalFitArgs {
     const float* flow;        // [N][H][W] records of cs floats, 2 used
@@ -77,8 +53,8 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void fundamental_sums_kernel(const FundamentalFitArgs a) {
     const int n = blockIdx.y, hw = a.H * a.W;
     const size_t img = (size_t)n * hw;
-    const double cx = (double)(a.W - 1) / 2.0, cy = (double)(a.H - 1) / 2.0, s = (double)max(a.H, a.W) / 2.0;
-    const double c2 = a.scale * a.scale, s2 = s * s;
+    const PwcFitNorm t = pwc_fit_norm(a.H, a.W);
+    const double s = t.s, c2 = a.scale * a.scale, s2 = s * s;
     double f[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) f[j] = a.first ? 0.0 : a.param[(size_t)n * 9 + j];
@@ -89,15 +65,16 @@ __global__ __launch_bounds__(256) void fundamental_sums_kernel(const Fundamental
     for (int i = blockIdx.x * 256 + threadIdx.x; i < hw; i += (int)gridDim.x * 256) {
         if (a.valid && !a.valid[img + i]) continue;
         float fu, fv;
-        fundamental_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
-        if (!fundamental_known(fu, fv)) continue;
+        pwc_flow_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
+        if (!pwc_flow_known(fu, fv)) continue;
         cnt += 1;                                                          // (a known pixel, in the pass or left out of it)
-        const double xh = ((double)(i % a.W) - cx) / s, yh = ((double)(i / a.W) - cy) / s;
+        double xh, yh;
+        pwc_fit_normalise(t, i, a.W, xh, yh);
         const double xp = xh + ((double)fu / s), yp = yh + ((double)fv / s);
         double w = 1.0;
         if (!a.first) {
             double r, g;
-            fundamental_sampson(f, xh, yh, xp, yp, r, g);
+            two_view_sampson(f, xh, yh, xp, yp, r, g);
             if (!(g > 0.0)) continue;                                      // no gradient under the F^ of the pass before: left out
             const double d2 = ((r * r) / g) * s2;
             w = (1.0 / (1.0 + (d2 / c2))) / g;
@@ -114,13 +91,7 @@ __global__ __launch_bounds__(256) void fundamental_sums_kernel(const Fundamental
             for (int j = 0; j < 6; ++j) sum[6 * (m + 1) + j] = sum[6 * (m + 1) + j] + (b[j] * pa[m]);
         }
     }
-    pwc_block_tree_sum_f64<FUNDAMENTAL_SUMS, 1>(sum, &cnt);
-    if (threadIdx.x == 0) {
-        const size_t o = (size_t)n * gridDim.x + blockIdx.x;
-#pragma unroll
-        for (int j = 0; j < FUNDAMENTAL_SUMS; ++j) a.part[o * FUNDAMENTAL_SUMS + j] = sum[j];
-        a.part_n[o] = cnt;
-    }
+    pwc_fit_write_part<FUNDAMENTAL_SUMS>(sum, cnt, n, a.part, a.part_n);
 }
 
 // a_k = P[pk] Q[qk] with P = (1, x', y'), Q = (1, xh, yh); the monomial of a pair of P's (or of Q's) among (1, x, y, x x, x y, y y)
@@ -135,15 +106,8 @@ __global__ __launch_bounds__(64) void fundamental_solve_kernel(const Fundamental
     const int n = blockIdx.x * 64 + threadIdx.x;
     if (n >= a.N) return;
     double S[FUNDAMENTAL_SUMS];
-#pragma unroll
-    for (int j = 0; j < FUNDAMENTAL_SUMS; ++j) S[j] = 0.0;
-    int cnt = 0;
-    for (int i = 0; i < a.parts; ++i) {
-        const size_t o = (size_t)n * a.parts + i;
-#pragma unroll
-        for (int j = 0; j < FUNDAMENTAL_SUMS; ++j) S[j] = S[j] + a.part[o * FUNDAMENTAL_SUMS + j];
-        cnt += a.part_n[o];
-    }
+    int cnt;
+    pwc_fit_gather<FUNDAMENTAL_SUMS>(a.part, a.part_n, n, a.parts, S, cnt);
     const bool before = a.first || a.ok[n] != 0;                           // not degenerate in an earlier pass
     bool good = before && cnt >= FUNDAMENTAL_MIN_COUNT;
     double F[9], v[3] = {0.0, 0.0, 0.0}, eig[2] = {0.0, 0.0};
@@ -184,25 +148,20 @@ __global__ __launch_bounds__(64) void fundamental_solve_kernel(const Fundamental
             for (int j = 0; j < 3; ++j) F[3 * i + j] = F[3 * i + j] - (ui * v[j]);
         }
 #pragma unroll
-        for (int j = 0; j < 9; ++j) good = good && fundamental_finite(F[j]);
-        good = good && fundamental_finite(v[0]) && fundamental_finite(v[1]) && fundamental_finite(v[2]) && fundamental_finite(eig[0]) &&
-               fundamental_finite(eig[1]);
+        for (int j = 0; j < 9; ++j) good = good && pwc_finite(F[j]);
+        good = good && pwc_finite(v[0]) && pwc_finite(v[1]) && pwc_finite(v[2]) && pwc_finite(eig[0]) &&
+               pwc_finite(eig[1]);
     }
     const bool fit = good;                                                 // what the later passes see
     if (a.last) {
-        const double cx = (double)(a.W - 1) / 2.0, cy = (double)(a.H - 1) / 2.0, s = (double)max(a.H, a.W) / 2.0;
-        // F^ T, row by row: (h0 / s, h1 / s, h2 - ((h0 cx) + (h1 cy)) / s); then T^T (F^ T) the same way down the columns
+        const PwcFitNorm t = pwc_fit_norm(a.H, a.W);
+        const double cx = t.cx, cy = t.cy, s = t.s;
+        // F^ T, row by row; then T^T (F^ T) the same way down the columns
         double r[3][3], m[9];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            r[i][0] = F[3 * i] / s; r[i][1] = F[3 * i + 1] / s;
-            r[i][2] = F[3 * i + 2] - (((F[3 * i] * cx) + (F[3 * i + 1] * cy)) / s);
-        }
+        for (int i = 0; i < 3; ++i) pwc_fit_row_times_t(t, F[3 * i], F[3 * i + 1], F[3 * i + 2], r[i][0], r[i][1], r[i][2]);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            m[j] = r[0][j] / s; m[3 + j] = r[1][j] / s;
-            m[6 + j] = r[2][j] - (((r[0][j] * cx) + (r[1][j] * cy)) / s);
-        }
+        for (int j = 0; j < 3; ++j) pwc_fit_row_times_t(t, r[0][j], r[1][j], r[2][j], m[j], m[3 + j], m[6 + j]);
         double q = m[0] * m[0];
 #pragma unroll
         for (int j = 1; j < 9; ++j) q = q + (m[j] * m[j]);
@@ -216,8 +175,8 @@ __global__ __launch_bounds__(64) void fundamental_solve_kernel(const Fundamental
         const bool flip = sign < 0.0;
         const double e[3] = {(s * v[0]) + (cx * v[2]), (s * v[1]) + (cy * v[2]), v[2]};
 #pragma unroll
-        for (int j = 0; j < 9; ++j) { m[j] = flip ? -m[j] : m[j]; good = good && fundamental_finite(m[j]); }
-        good = good && fundamental_finite(e[0]) && fundamental_finite(e[1]) && fundamental_finite(e[2]);
+        for (int j = 0; j < 9; ++j) { m[j] = flip ? -m[j] : m[j]; good = good && pwc_finite(m[j]); }
+        good = good && pwc_finite(e[0]) && pwc_finite(e[1]) && pwc_finite(e[2]);
 #pragma unroll
         for (int j = 0; j < 9; ++j) a.matrices[(size_t)n * 9 + j] = good ? m[j] : 0.0;
 #pragma unroll
@@ -255,15 +214,15 @@ __global__ __launch_bounds__(256) void epipolar_residual_kernel(const EpipolarRe
         bool zero = true;
 #pragma unroll
         for (int j = 0; j < 9; ++j) { f[j] = a.matrices[(size_t)q.n * 9 + j]; zero = zero && f[j] == 0.0; }
-        float d = FUNDAMENTAL_SENTINEL;
+        float d = PWC_FLOW_SENTINEL;
         uint8_t in = 0;
         if (!zero && !(a.valid && !a.valid[p])) {
             float fu, fv;
-            fundamental_load2<VEC>(a.flow + (size_t)p * a.cs, fu, fv);
-            if (fundamental_known(fu, fv)) {
+            pwc_flow_load2<VEC>(a.flow + (size_t)p * a.cs, fu, fv);
+            if (pwc_flow_known(fu, fv)) {
                 const double x = (double)q.x, y = (double)q.y;
                 double r, g;
-                fundamental_sampson(f, x, y, x + (double)fu, y + (double)fv, r, g);
+                two_view_sampson(f, x, y, x + (double)fu, y + (double)fv, r, g);
                 if (g > 0.0) {
                     const double dd = fabs(r) / sqrt(g);
                     d = (float)dd;
@@ -277,42 +236,27 @@ __global__ __launch_bounds__(256) void epipolar_residual_kernel(const EpipolarRe
 }
 
 // ---------------------------------------------------------------- host
-static inline bool fundamental_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 extern "C" size_t pwc_fundamental_fit_workspace_bytes(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0 || !pwc_loss_in_range(N, H, W)) return 0;
-    const size_t cells = (size_t)N * pwc_loss_parts(H, W);
-    return 8 * (cells * FUNDAMENTAL_SUMS + (size_t)N * 9) + ((4 * cells + 7) & ~(size_t)7);
+    return pwc_fit_workspace_bytes(N, H, W, FUNDAMENTAL_SUMS, 9);
 }
 
 extern "C" int pwc_fundamental_fit_f64(const float* flows, int flow_cs, const uint8_t* valid, int N, int H, int W, int iters,
                                        double scale, void* workspace, size_t workspace_bytes, double* matrices, uint8_t* ok,
                                        int32_t* count, double* weight_sum, double* eigen, double* epipole, pwc_stream_t stream) {
-    if (!flows || !workspace || !matrices || !ok || !count || !weight_sum || !eigen || !epipole) return PWC_EINVAL;
-    if (N < 1 || H < 1 || W < 1 || iters < 0 || iters > PWC_MOTION_MAX_ITERS || !(scale > 0.0) || flow_cs < 2) return PWC_EINVAL;
-    if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (fundamental_off(flows, 3u) || fundamental_off(workspace, 7u) || fundamental_off(matrices, 7u) || fundamental_off(weight_sum, 7u) ||
-        fundamental_off(eigen, 7u) || fundamental_off(epipole, 7u) || fundamental_off(count, 3u))
-        return PWC_EALIGN;
-    if (workspace_bytes < pwc_fundamental_fit_workspace_bytes(N, H, W)) return PWC_EINVAL;
+    if (!matrices || !ok || !count || !weight_sum || !eigen || !epipole) return PWC_EINVAL;
+    const int rc = pwc_fit_check(flows, flow_cs, N, H, W, iters, scale, workspace, workspace_bytes,
+                                 pwc_fundamental_fit_workspace_bytes(N, H, W),
+                                 pwc_off(matrices, 7u) || pwc_off(weight_sum, 7u) || pwc_off(eigen, 7u) || pwc_off(epipole, 7u) ||
+                                     pwc_off(count, 3u));
+    if (rc != PWC_OK) return rc;
     const int parts = (int)pwc_loss_parts(H, W);
-    const size_t cells = (size_t)N * parts;
     FundamentalFitArgs a = {};
     a.flow = flows; a.valid = valid;
-    a.part = reinterpret_cast<double*>(workspace);
-    a.param = a.part + cells * FUNDAMENTAL_SUMS;
-    a.part_n = reinterpret_cast<int*>(a.param + (size_t)N * 9);
+    pwc_fit_carve(workspace, N, parts, FUNDAMENTAL_SUMS, 9, a.part, a.param, a.part_n);
     a.matrices = matrices; a.ok = ok; a.count = count; a.weight_sum = weight_sum; a.eigen = eigen; a.epipole = epipole;
     a.scale = scale; a.cs = flow_cs; a.N = N; a.H = H; a.W = W; a.parts = parts;
-    const bool vec = !(flow_cs & 1) && !fundamental_off(flows, 7u);
-    const hipStream_t s = (hipStream_t)stream;
-    for (int pass = 0; pass <= iters; ++pass) {
-        a.first = pass == 0 ? 1 : 0;
-        a.last = pass == iters ? 1 : 0;
-        if (vec) hipLaunchKernelGGL(fundamental_sums_kernel<true>, dim3(parts, N), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(fundamental_sums_kernel<false>, dim3(parts, N), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(fundamental_solve_kernel, dim3((N + 63) / 64), dim3(64), 0, s, a);
-    }
+    pwc_fit_passes<fundamental_sums_kernel<true>, fundamental_sums_kernel<false>, fundamental_solve_kernel>(
+        a, iters, pwc_flow_vec(flow_cs, {flows}), (hipStream_t)stream);
     return pwc_launch_status();
 }
 
@@ -321,13 +265,12 @@ extern "C" int pwc_epipolar_residual_f32(const float* flows, int flow_cs, const 
     if (!flows || !matrices || !distance || !inlier) return PWC_EINVAL;
     if (N < 1 || H < 1 || W < 1 || flow_cs < 2 || !(threshold >= 0.0)) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (fundamental_off(flows, 3u) || fundamental_off(distance, 3u) || fundamental_off(matrices, 7u)) return PWC_EALIGN;
+    if (pwc_off(flows, 3u) || pwc_off(distance, 3u) || pwc_off(matrices, 7u)) return PWC_EALIGN;
     EpipolarResidualArgs a = {};
     a.flow = flows; a.valid = valid; a.matrices = matrices; a.distance = distance; a.inlier = inlier;
     a.threshold = threshold; a.cs = flow_cs; a.N = N; a.H = H; a.W = W;
-    const bool vec = !(flow_cs & 1) && !fundamental_off(flows, 7u);
-    const long blocks = ((long)N * H * W + 255) / 256;
-    const dim3 grid((unsigned)(blocks > FUNDAMENTAL_MAX_BLOCKS ? FUNDAMENTAL_MAX_BLOCKS : blocks));
+    const bool vec = pwc_flow_vec(flow_cs, {flows});
+    const dim3 grid = pwc_loss_grad_blocks(N, H, W);
     const hipStream_t s = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(epipolar_residual_kernel<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(epipolar_residual_kernel<false>, grid, dim3(256), 0, s, a);

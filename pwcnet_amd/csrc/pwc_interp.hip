@@ -23,6 +23,7 @@
 // no other image's: a call cut along N or M gives the whole call's bits.
 // Grids: scatter (min(ceil(N H W / 256), 4096), 2), resolve min(ceil(N M H W / 1024), 4096) workgroups of 256 lanes, grid-stride
 // beyond.  No LDS, no host synchronisation, no process-wide state; 64-bit indices into the workspace.
+#include "flow_record.h"
 #include "loss_common.h"
 
 #pragma clang fp contract(off)
@@ -46,9 +47,6 @@ struct InterpArgs {
     float alpha, min_range;
     int out_vec, source_vec;  // out on a 4-byte (bytes) / 16-byte (floats) boundary, source on a 4-byte one
 };
-
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool interp_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
 
 // The three channels of pixel `pix` of a frame as doubles: a byte v is v / 255, a float is widened.
 template <bool U8>
@@ -77,18 +75,16 @@ __device__ __forceinline__ double interp_match_weight(const InterpArgs& a, int k
                                                       const double* own) {
     const double qx = (double)x + f0, qy = (double)y + f1;
     if (!(qx >= 0.0 && qx <= (double)(a.W - 1) && qy >= 0.0 && qy <= (double)(a.H - 1))) return exp(-INTERP_CLAMP);
-    const double fx0 = floor(qx), fy0 = floor(qy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);
-    const double wx1 = qx - fx0, wy1 = qy - fy0, wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+    const PwcBilinearF64 bl = pwc_bilinear_f64(qx, qy, a.H, a.W);
+    const double wx0 = bl.wx0, wx1 = bl.wx1, wy0 = bl.wy0, wy1 = bl.wy1;
     const size_t img = (size_t)n * a.H * a.W;
     const void* other = a.frame[1 - k];
     const int cs = a.frame_cs[1 - k];
     double c00[3], c01[3], c10[3], c11[3];
-    interp_load<U8>(other, cs, img + (size_t)y0 * a.W + x0, c00);
-    interp_load<U8>(other, cs, img + (size_t)y0 * a.W + x1, c01);
-    interp_load<U8>(other, cs, img + (size_t)y1 * a.W + x0, c10);
-    interp_load<U8>(other, cs, img + (size_t)y1 * a.W + x1, c11);
+    interp_load<U8>(other, cs, img + bl.o00, c00);
+    interp_load<U8>(other, cs, img + bl.o01, c01);
+    interp_load<U8>(other, cs, img + bl.o10, c10);
+    interp_load<U8>(other, cs, img + bl.o11, c11);
     double e = 0.0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -114,7 +110,7 @@ __global__ __launch_bounds__(256) void interp_scatter_kernel(const InterpArgs a)
     for (long p = blockIdx.x * 256L + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
         if (valid && !valid[p]) continue;
         const float fu = flow[p * fcs], fv = flow[p * fcs + 1];
-        if (!interp_known(fu, fv)) continue;
+        if (!pwc_flow_known(fu, fv)) continue;
         const PwcLossPixel q = pwc_loss_pixel(p, a.H, a.W);
         const double f0 = (double)fu, f1 = (double)fv;
         double col[3];
@@ -133,6 +129,7 @@ __global__ __launch_bounds__(256) void interp_scatter_kernel(const InterpArgs a)
             const double px = (double)q.x + s * f0, py = (double)q.y + s * f1;
             // (every comparison is false for a NaN; an Inf fails one of them)
             if (!(px > -1.0 && px < (double)a.W && py > -1.0 && py < (double)a.H)) continue;
+            // (not pwc_bilinear_f64: a splat -- the position may lie up to a pixel outside, corners outside are dropped, not clipped)
             const double fx0 = floor(px), fy0 = floor(py);
             const int x0 = (int)fx0, y0 = (int)fy0;
             const double wx = px - fx0, wy = py - fy0;
@@ -158,10 +155,9 @@ __global__ __launch_bounds__(256) void interp_scatter_kernel(const InterpArgs a)
 
 __device__ __forceinline__ bool interp_wild(long long v) { return v >= (1LL << 61) || v <= -(1LL << 61); }
 
-// A double as a byte: rint(255 v), ties to even, clamped to [0, 255]; 0 for a NaN.
+// A double as a byte: rint(255 v), ties to even, clamped to [0, 255]; 0 for a NaN.  Not pwc_round_byte: the value is scaled first.
 __device__ __forceinline__ unsigned interp_byte(double v) {
-    const double t = rint(255.0 * v);
-    return t >= 255.0 ? 255u : (t >= 0.0 ? (unsigned)(int)t : 0u);
+    return pwc_clamp_byte(rint(255.0 * v));
 }
 
 // Output pixel g of the flat (N, M, H, W) index: its three channels and its source code; false where the pixel is dead (the
@@ -259,10 +255,6 @@ __global__ __launch_bounds__(256) void interp_resolve_kernel(const InterpArgs a)
 }
 
 // ---------------------------------------------------------------- host
-#define INTERP_MAX_BLOCKS 4096
-
-static inline bool interp_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 // Whether 8 (N M H W 10 + 1) bytes can be counted in a size_t at all.
 static inline bool interp_countable(int N, int M, int H, int W) {
     const size_t per_image = (size_t)H * W * 10;                           // H W < 2^31
@@ -289,9 +281,9 @@ extern "C" int pwc_interp_frames(const void* frames_0, int dtype_0, int cs_0, co
     const bool u8 = dtype_0 == PWC_INTERP_U8;
     if (fw_cs < 2 || bw_cs < 2 || (u8 ? (cs_0 != 3 || cs_1 != 3) : (cs_0 < 3 || cs_1 < 3))) return PWC_EINVAL;
     if ((long)H * W >= (1L << 31) || !interp_countable(N, M, H, W)) return PWC_ERANGE;
-    if (interp_off(flows_fw, 3u) || interp_off(flows_bw, 3u) || (weights_fw && interp_off(weights_fw, 3u)) ||
-        (weights_bw && interp_off(weights_bw, 3u)) || interp_off(workspace, 7u) ||
-        (!u8 && (interp_off(frames_0, 3u) || interp_off(frames_1, 3u) || interp_off(frames_t, 3u))))
+    if (pwc_off(flows_fw, 3u) || pwc_off(flows_bw, 3u) || (weights_fw && pwc_off(weights_fw, 3u)) ||
+        (weights_bw && pwc_off(weights_bw, 3u)) || pwc_off(workspace, 7u) ||
+        (!u8 && (pwc_off(frames_0, 3u) || pwc_off(frames_1, 3u) || pwc_off(frames_t, 3u))))
         return PWC_EALIGN;
     const size_t bytes = pwc_interp_workspace_bytes(N, M, H, W);
     if (workspace_bytes < bytes) return PWC_EINVAL;
@@ -302,15 +294,13 @@ extern "C" int pwc_interp_frames(const void* frames_0, int dtype_0, int cs_0, co
     for (int m = 0; m < M; ++m) a.times[m] = times[m];
     a.frame_cs[0] = cs_0; a.frame_cs[1] = cs_1; a.flow_cs[0] = fw_cs; a.flow_cs[1] = bw_cs;
     a.N = N; a.M = M; a.H = H; a.W = W; a.alpha = alpha; a.min_range = min_range;
-    a.out_vec = interp_off(frames_t, u8 ? 3u : 15u) ? 0 : 1;
-    a.source_vec = interp_off(source, 3u) ? 0 : 1;
+    a.out_vec = pwc_off(frames_t, u8 ? 3u : 15u) ? 0 : 1;
+    a.source_vec = pwc_off(source, 3u) ? 0 : 1;
     const hipStream_t s = (hipStream_t)stream;
     const hipError_t me = hipMemsetAsync(workspace, 0, bytes, s);
     if (me != hipSuccess) { (void)hipGetLastError(); return (int)me; }          // the memset's OWN error, never PWC_OK
-    const long sblocks = ((long)N * H * W + 255) / 256;
-    const long rblocks = (((long)N * M * H * W + 3) / 4 + 255) / 256;
-    const dim3 sgrid((unsigned)(sblocks > INTERP_MAX_BLOCKS ? INTERP_MAX_BLOCKS : sblocks), 2u);
-    const dim3 rgrid((unsigned)(rblocks > INTERP_MAX_BLOCKS ? INTERP_MAX_BLOCKS : rblocks));
+    const dim3 sgrid(pwc_loss_grad_blocks(N, H, W).x, 2u);
+    const dim3 rgrid = pwc_flat_grid(((long)N * M * H * W + 3) / 4);
     if (u8) {
         hipLaunchKernelGGL(interp_scatter_kernel<true>, sgrid, dim3(256), 0, s, a);
         hipLaunchKernelGGL(interp_resolve_kernel<true>, rgrid, dim3(256), 0, s, a);

@@ -26,30 +26,15 @@
 // formed anywhere in this file (the pragma below), no library function is called -- so tests/motion_ref.py restates it in numpy
 // bit for bit.  No atomic, no host synchronisation, no process-wide state.
 // Flows at any channel stride >= 2: where the pointers of a call are on an 8-byte boundary and the stride is even a record's two
-// floats are one 8-byte access, else two 4-byte ones -- the values, and so every bit, are the same (pwc_track.hip's arrangement).
-#include "loss_common.h"
+// floats are one 8-byte access, else two 4-byte ones -- the values, and so every bit, are the same (flow_record.h).  The pass
+// structure, the parts and the workspace are robust_fit.h's.
 #include "motion_ldlt.h"
 #include "projective.h"
+#include "robust_fit.h"
 
 #pragma clang fp contract(off)
 
-#define MOTION_SENTINEL 1e10f
 #define MOTION_PIVOT 1e-9
-#define MOTION_MAX_BLOCKS 4096
-
-template <bool VEC>
-__device__ __forceinline__ void motion_load2(const float* p, float& a, float& b) {
-    if (VEC) {
-        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
-        a = v[0]; b = v[1];
-    } else {
-        a = p[0]; b = p[1];
-    }
-}
-
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool motion_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-__device__ __forceinline__ bool motion_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // (false for a NaN)
 
 // ---------------------------------------------------------------- the fit
 struct MotionFitArgs {
@@ -71,7 +56,7 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void motion_sums_kernel(const MotionFitArgs a) {
     const int n = blockIdx.y, hw = a.H * a.W;
     const size_t img = (size_t)n * hw;
-    const double cx = (double)(a.W - 1) / 2.0, cy = (double)(a.H - 1) / 2.0, s = (double)max(a.H, a.W) / 2.0;
+    const PwcFitNorm t = pwc_fit_norm(a.H, a.W);
     const double c2 = a.scale * a.scale;
     double p[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (!a.first) {
@@ -85,10 +70,11 @@ __global__ __launch_bounds__(256) void motion_sums_kernel(const MotionFitArgs a)
     for (int i = blockIdx.x * 256 + threadIdx.x; i < hw; i += (int)gridDim.x * 256) {
         if (a.valid && !a.valid[img + i]) continue;
         float fu, fv;
-        motion_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
-        if (!motion_known(fu, fv)) continue;
+        pwc_flow_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
+        if (!pwc_flow_known(fu, fv)) continue;
         const double u = (double)fu, v = (double)fv;
-        const double xh = ((double)(i % a.W) - cx) / s, yh = ((double)(i / a.W) - cy) / s;
+        double xh, yh;
+        pwc_fit_normalise(t, i, a.W, xh, yh);
         double w = 1.0;
         if (!a.first) {
             const double ru = u - ((p[0] + (p[1] * xh)) + (p[2] * yh)), rv = v - ((p[3] + (p[4] * xh)) + (p[5] * yh));
@@ -101,13 +87,7 @@ __global__ __launch_bounds__(256) void motion_sums_kernel(const MotionFitArgs a)
         sum[9] = sum[9] + (w * v);   sum[10] = sum[10] + (wx * v); sum[11] = sum[11] + (wy * v);
         cnt += 1;
     }
-    pwc_block_tree_sum_f64<12, 1>(sum, &cnt);
-    if (threadIdx.x == 0) {
-        const size_t o = (size_t)n * gridDim.x + blockIdx.x;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) a.part[o * 12 + j] = sum[j];
-        a.part_n[o] = cnt;
-    }
+    pwc_fit_write_part<12>(sum, cnt, n, a.part, a.part_n);
 }
 
 // (motion_ldlt: motion_ldlt.h, shared with pwc_homography.hip.)
@@ -116,15 +96,8 @@ __global__ __launch_bounds__(64) void motion_solve_kernel(const MotionFitArgs a)
     const int n = blockIdx.x * 64 + threadIdx.x;
     if (n >= a.N) return;
     double S[12];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) S[j] = 0.0;
-    int cnt = 0;
-    for (int i = 0; i < a.parts; ++i) {
-        const size_t o = (size_t)n * a.parts + i;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) S[j] = S[j] + a.part[o * 12 + j];
-        cnt += a.part_n[o];
-    }
+    int cnt;
+    pwc_fit_gather<12>(a.part, a.part_n, n, a.parts, S, cnt);
     const double tol = MOTION_PIVOT * S[0];
     double p[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     bool good = a.first || a.ok[n] != 0;
@@ -155,10 +128,13 @@ __global__ __launch_bounds__(64) void motion_solve_kernel(const MotionFitArgs a)
     a.count[n] = cnt;
     a.weight_sum[n] = S[0];
     if (a.last) {
-        const double cx = (double)(a.W - 1) / 2.0, cy = (double)(a.H - 1) / 2.0, s = (double)max(a.H, a.W) / 2.0;
+        // the identity plus (A T) row by row, A = [[p1 p2 p0] [p4 p5 p3]]
         double* m = a.matrices + (size_t)n * 9;
-        m[0] = 1.0 + (p[1] / s); m[1] = p[2] / s;         m[2] = p[0] - (((p[1] * cx) + (p[2] * cy)) / s);
-        m[3] = p[4] / s;         m[4] = 1.0 + (p[5] / s); m[5] = p[3] - (((p[4] * cx) + (p[5] * cy)) / s);
+        double r[2][3];
+        pwc_fit_row_times_t(pwc_fit_norm(a.H, a.W), p[1], p[2], p[0], r[0][0], r[0][1], r[0][2]);
+        pwc_fit_row_times_t(pwc_fit_norm(a.H, a.W), p[4], p[5], p[3], r[1][0], r[1][1], r[1][2]);
+        m[0] = 1.0 + r[0][0]; m[1] = r[0][1];       m[2] = r[0][2];
+        m[3] = r[1][0];       m[4] = 1.0 + r[1][1]; m[5] = r[1][2];
         m[6] = 0.0; m[7] = 0.0; m[8] = 1.0;
     }
 }
@@ -178,7 +154,7 @@ struct MotionResidualArgs {
 __device__ __forceinline__ bool motion_affine(const double* m, double* e) {
     bool good = m[6] == 0.0 && m[7] == 0.0 && m[8] == 1.0;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) { e[j] = m[j]; good = good && motion_finite(e[j]); }
+    for (int j = 0; j < 6; ++j) { e[j] = m[j]; good = good && pwc_finite(e[j]); }
     return good;
 }
 
@@ -189,14 +165,14 @@ __global__ __launch_bounds__(256) void motion_residual_kernel(const MotionResidu
     const long npix = (long)a.N * a.H * a.W;
     for (long g = blockIdx.x * 256L + threadIdx.x; g < npix; g += (long)gridDim.x * 256) {
         const PwcLossPixel q = pwc_loss_pixel(g, a.H, a.W);
-        float r0 = MOTION_SENTINEL, r1 = MOTION_SENTINEL;
+        float r0 = PWC_FLOW_SENTINEL, r1 = PWC_FLOW_SENTINEL;
         uint8_t in = 0;
         double m[PROJ ? 9 : 6];
         const bool good = PROJ ? pwc_projective_finite(a.matrices + (size_t)q.n * 9, m) : motion_affine(a.matrices + (size_t)q.n * 9, m);
         if (good && !(a.valid && !a.valid[g])) {
             float fu, fv;
-            motion_load2<VEC>(a.flow + (size_t)g * a.cs, fu, fv);
-            if (motion_known(fu, fv)) {
+            pwc_flow_load2<VEC>(a.flow + (size_t)g * a.cs, fu, fv);
+            if (pwc_flow_known(fu, fv)) {
                 const double x = (double)q.x, y = (double)q.y;
                 double sx, sy;
                 bool there = true;
@@ -213,11 +189,7 @@ __global__ __launch_bounds__(256) void motion_residual_kernel(const MotionResidu
                 }
             }
         }
-        if (VEC) {
-            *reinterpret_cast<f32x2*>(a.residual + 2 * g) = f32x2{r0, r1};
-        } else {
-            a.residual[2 * g] = r0; a.residual[2 * g + 1] = r1;
-        }
+        pwc_flow_store2<VEC>(a.residual + 2 * g, r0, r1);
         a.inlier[g] = in;
     }
 }
@@ -231,12 +203,6 @@ struct MotionWarpArgs {
     int N, H, W;
     int out_vec, covered_vec; // out on a 4-byte (bytes) / 16-byte (floats) boundary, covered on a 4-byte one
 };
-
-// A double as a byte: rint, ties to even, clamped to [0, 255]; 0 for a NaN.
-__device__ __forceinline__ unsigned motion_byte(double v) {
-    const double t = rint(v);
-    return t >= 255.0 ? 255u : (t >= 0.0 ? (unsigned)(int)t : 0u);
-}
 
 // Output pixel g: its C channels as doubles (pwc_fb_valid_u8's sample of the source position); false where it is not covered.
 // PROJ: projective.h's rule in place of the affine one.
@@ -254,13 +220,11 @@ __device__ __forceinline__ bool motion_warp_pixel(const MotionWarpArgs& a, long 
     }
     // (every comparison is false for a NaN; an Inf fails one of them) -- what keeps the four corner reads inside image n
     if (!(sx >= 0.0 && sx <= (double)(a.W - 1) && sy >= 0.0 && sy <= (double)(a.H - 1))) return false;
-    const double fx0 = floor(sx), fy0 = floor(sy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);
-    const double wx1 = sx - fx0, wy1 = sy - fy0, wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+    const PwcBilinearF64 bl = pwc_bilinear_f64(sx, sy, a.H, a.W);
+    const double wx0 = bl.wx0, wx1 = bl.wx1, wy0 = bl.wy0, wy1 = bl.wy1;
     const size_t img = (size_t)q.n * a.H * a.W;
-    const size_t o00 = (img + (size_t)y0 * a.W + x0) * C, o01 = (img + (size_t)y0 * a.W + x1) * C;
-    const size_t o10 = (img + (size_t)y1 * a.W + x0) * C, o11 = (img + (size_t)y1 * a.W + x1) * C;
+    const size_t o00 = (img + bl.o00) * C, o01 = (img + bl.o01) * C;
+    const size_t o10 = (img + bl.o10) * C, o11 = (img + bl.o11) * C;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         double c00, c01, c10, c11;
@@ -294,7 +258,7 @@ __global__ __launch_bounds__(256) void motion_warp_kernel(const MotionWarpArgs a
             cov |= (ok ? 1u : 0u) << (8 * i);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                if (U8) b[C * i + c] = ok ? motion_byte(v[c]) : 0u;
+                if (U8) b[C * i + c] = ok ? pwc_round_byte(v[c]) : 0u;
                 else f[C * i + c] = ok ? (float)v[c] : 0.f;
             }
         }
@@ -330,43 +294,24 @@ __global__ __launch_bounds__(256) void motion_warp_kernel(const MotionWarpArgs a
 }
 
 // ---------------------------------------------------------------- host
-static inline bool motion_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
-extern "C" size_t pwc_motion_fit_workspace_bytes(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0 || !pwc_loss_in_range(N, H, W)) return 0;
-    const size_t cells = (size_t)N * pwc_loss_parts(H, W);
-    return 8 * (cells * 12 + (size_t)N * 6) + ((4 * cells + 7) & ~(size_t)7);
-}
+extern "C" size_t pwc_motion_fit_workspace_bytes(int N, int H, int W) { return pwc_fit_workspace_bytes(N, H, W, 12, 6); }
 
 extern "C" int pwc_motion_fit_f64(const float* flows, int flow_cs, const uint8_t* valid, int N, int H, int W, int model, int iters,
                                   double scale, void* workspace, size_t workspace_bytes, double* matrices, uint8_t* ok,
                                   int32_t* count, double* weight_sum, pwc_stream_t stream) {
-    if (!flows || !workspace || !matrices || !ok || !count || !weight_sum) return PWC_EINVAL;
-    if (N < 1 || H < 1 || W < 1 || iters < 0 || iters > PWC_MOTION_MAX_ITERS || !(scale > 0.0) || flow_cs < 2) return PWC_EINVAL;
+    if (!matrices || !ok || !count || !weight_sum) return PWC_EINVAL;
     if (model != PWC_MOTION_TRANSLATION && model != PWC_MOTION_SIMILARITY && model != PWC_MOTION_AFFINE) return PWC_EINVAL;
-    if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (motion_off(flows, 3u) || motion_off(workspace, 7u) || motion_off(matrices, 7u) || motion_off(weight_sum, 7u) ||
-        motion_off(count, 3u))
-        return PWC_EALIGN;
-    if (workspace_bytes < pwc_motion_fit_workspace_bytes(N, H, W)) return PWC_EINVAL;
+    const int rc = pwc_fit_check(flows, flow_cs, N, H, W, iters, scale, workspace, workspace_bytes, pwc_motion_fit_workspace_bytes(N, H, W),
+                                 pwc_off(matrices, 7u) || pwc_off(weight_sum, 7u) || pwc_off(count, 3u));
+    if (rc != PWC_OK) return rc;
     const int parts = (int)pwc_loss_parts(H, W);
-    const size_t cells = (size_t)N * parts;
     MotionFitArgs a = {};
     a.flow = flows; a.valid = valid;
-    a.part = reinterpret_cast<double*>(workspace);
-    a.param = a.part + cells * 12;
-    a.part_n = reinterpret_cast<int*>(a.param + (size_t)N * 6);
+    pwc_fit_carve(workspace, N, parts, 12, 6, a.part, a.param, a.part_n);
     a.matrices = matrices; a.ok = ok; a.count = count; a.weight_sum = weight_sum;
     a.scale = scale; a.cs = flow_cs; a.N = N; a.H = H; a.W = W; a.parts = parts; a.model = model;
-    const bool vec = !(flow_cs & 1) && !motion_off(flows, 7u);
-    const hipStream_t s = (hipStream_t)stream;
-    for (int pass = 0; pass <= iters; ++pass) {
-        a.first = pass == 0 ? 1 : 0;
-        a.last = pass == iters ? 1 : 0;
-        if (vec) hipLaunchKernelGGL(motion_sums_kernel<true>, dim3(parts, N), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(motion_sums_kernel<false>, dim3(parts, N), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(motion_solve_kernel, dim3((N + 63) / 64), dim3(64), 0, s, a);
-    }
+    pwc_fit_passes<motion_sums_kernel<true>, motion_sums_kernel<false>, motion_solve_kernel>(a, iters, pwc_flow_vec(flow_cs, {flows}),
+                                                                                            (hipStream_t)stream);
     return pwc_launch_status();
 }
 
@@ -375,13 +320,12 @@ static int motion_residual_call(const float* flows, int flow_cs, const uint8_t* 
     if (!flows || !matrices || !residual || !inlier) return PWC_EINVAL;
     if (N < 1 || H < 1 || W < 1 || flow_cs < 2 || !(threshold >= 0.0)) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (motion_off(flows, 3u) || motion_off(residual, 3u) || motion_off(matrices, 7u)) return PWC_EALIGN;
+    if (pwc_off(flows, 3u) || pwc_off(residual, 3u) || pwc_off(matrices, 7u)) return PWC_EALIGN;
     MotionResidualArgs a = {};
     a.flow = flows; a.valid = valid; a.matrices = matrices; a.residual = residual; a.inlier = inlier;
     a.thr2 = threshold * threshold; a.cs = flow_cs; a.N = N; a.H = H; a.W = W;
-    const bool vec = !(flow_cs & 1) && !motion_off(flows, 7u) && !motion_off(residual, 7u);
-    const long blocks = ((long)N * H * W + 255) / 256;
-    const dim3 grid((unsigned)(blocks > MOTION_MAX_BLOCKS ? MOTION_MAX_BLOCKS : blocks));
+    const bool vec = pwc_flow_vec(flow_cs, {flows, residual});
+    const dim3 grid = pwc_loss_grad_blocks(N, H, W);
     const hipStream_t s = (hipStream_t)stream;
     if (projective) {
         if (vec) hipLaunchKernelGGL((motion_residual_kernel<true, true>), grid, dim3(256), 0, s, a);
@@ -418,13 +362,12 @@ static int motion_warp_call(const void* frames, int dtype, int C, const double* 
     if (N < 1 || H < 1 || W < 1 || C < 1 || C > 4 || (dtype != PWC_MOTION_U8 && dtype != PWC_MOTION_F32)) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
     const bool u8 = dtype == PWC_MOTION_U8;
-    if (motion_off(matrices, 7u) || (!u8 && (motion_off(frames, 3u) || motion_off(out, 3u)))) return PWC_EALIGN;
+    if (pwc_off(matrices, 7u) || (!u8 && (pwc_off(frames, 3u) || pwc_off(out, 3u)))) return PWC_EALIGN;
     MotionWarpArgs a = {};
     a.frames = frames; a.matrices = matrices; a.out = out; a.covered = covered; a.N = N; a.H = H; a.W = W;
-    a.out_vec = motion_off(out, u8 ? 3u : 15u) ? 0 : 1;
-    a.covered_vec = motion_off(covered, 3u) ? 0 : 1;
-    const long blocks = (((long)N * H * W + 3) / 4 + 255) / 256;
-    const dim3 grid((unsigned)(blocks > MOTION_MAX_BLOCKS ? MOTION_MAX_BLOCKS : blocks));
+    a.out_vec = pwc_off(out, u8 ? 3u : 15u) ? 0 : 1;
+    a.covered_vec = pwc_off(covered, 3u) ? 0 : 1;
+    const dim3 grid = pwc_flat_grid(((long)N * H * W + 3) / 4);
     if (projective) {
         if (u8) motion_warp_launch<true, true>(C, grid, (hipStream_t)stream, a);
         else motion_warp_launch<false, true>(C, grid, (hipStream_t)stream, a);

@@ -19,7 +19,7 @@
 // Every value is an IEEE double + - x /, a floor, a rint or a comparison in the order of the header -- no fused multiply-add is
 // formed anywhere in this file (the pragma below) -- so tests/plate_ref.py restates it in numpy bit for bit.  No atomics, no
 // workspace, no scratch, no host synchronisation, no process-wide state; frame offsets are 64-bit.
-#include "pwc_common.h"
+#include "flow_record.h"
 #include "projective.h"
 
 #pragma clang fp contract(off)
@@ -27,11 +27,7 @@
 #define PLATE_TILE_W 32
 #define PLATE_TILE_H 8
 #define PLATE_MAX_TILES 65536
-#define PLATE_MAX_BLOCKS 4096
 #define PLATE_MAX_PIXELS (2147483647L - 65536L)
-
-__device__ __forceinline__ bool plate_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // (false for a NaN)
-__device__ __forceinline__ bool plate_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
 
 // WARP's rule (pwc_motion.hip's motion_affine): last row exactly 0 0 1, first two rows finite; e: the matrix (the last row is
 // read by the projective branch only).  projective (uniform in the workgroup): projective.h's rule, all nine entries finite.
@@ -39,15 +35,9 @@ __device__ __forceinline__ bool plate_affine(const double* m, double* e, int pro
     if (projective) return pwc_projective_finite(m, e);
     bool good = m[6] == 0.0 && m[7] == 0.0 && m[8] == 1.0;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) { e[j] = m[j]; good = good && plate_finite(e[j]); }
+    for (int j = 0; j < 6; ++j) { e[j] = m[j]; good = good && pwc_finite(e[j]); }
     e[6] = 0.0; e[7] = 0.0; e[8] = 1.0;
     return good;
-}
-
-// A double as a byte: rint, ties to even, clamped to [0, 255]; 0 for a NaN (pwc_motion.hip's).
-__device__ __forceinline__ unsigned plate_byte(double v) {
-    const double t = rint(v);
-    return t >= 255.0 ? 255u : (t >= 0.0 ? (unsigned)(int)t : 0u);
 }
 
 // pwc_flow_filter.hip's total order: negative floats reversed below the positive ones, -0 < +0.
@@ -57,10 +47,7 @@ __device__ __forceinline__ unsigned plate_unkey(unsigned k) { return (k >> 31) ?
 // Where pixel (x, y) lands in an H x W image under the affine rows m, as the four clamped corners (pixel offsets inside the
 // image) and their weights; false where the position is outside [0, W - 1] x [0, H - 1] (every comparison is false for a NaN) --
 // which is what keeps the corner reads inside the image.
-struct PlateCorners {
-    size_t o00, o01, o10, o11;
-    double wx0, wx1, wy0, wy1;
-};
+typedef PwcBilinearF64 PlateCorners;
 __device__ __forceinline__ bool plate_corners(const double* m, int px, int py, int H, int W, PlateCorners& k, int projective) {
     const double x = (double)px, y = (double)py;
     double sx, sy;
@@ -70,11 +57,7 @@ __device__ __forceinline__ bool plate_corners(const double* m, int px, int py, i
         sx = ((m[0] * x) + (m[1] * y)) + m[2]; sy = ((m[3] * x) + (m[4] * y)) + m[5];
     }
     if (!(sx >= 0.0 && sx <= (double)(W - 1) && sy >= 0.0 && sy <= (double)(H - 1))) return false;
-    const double fx0 = floor(sx), fy0 = floor(sy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    k.wx1 = sx - fx0; k.wy1 = sy - fy0; k.wx0 = 1.0 - k.wx1; k.wy0 = 1.0 - k.wy1;
-    k.o00 = (size_t)y0 * W + x0; k.o01 = (size_t)y0 * W + x1; k.o10 = (size_t)y1 * W + x0; k.o11 = (size_t)y1 * W + x1;
+    k = pwc_bilinear_f64(sx, sy, H, W);
     return true;
 }
 
@@ -90,7 +73,7 @@ __device__ __forceinline__ double plate_blend(const void* base, size_t img, int 
         const float* f = reinterpret_cast<const float*>(base);
         const float f00 = f[(img + k.o00) * C + c], f01 = f[(img + k.o01) * C + c];
         const float f10 = f[(img + k.o10) * C + c], f11 = f[(img + k.o11) * C + c];
-        *fin = *fin && plate_finite(f00) && plate_finite(f01) && plate_finite(f10) && plate_finite(f11);
+        *fin = *fin && pwc_finite(f00) && pwc_finite(f01) && pwc_finite(f10) && pwc_finite(f11);
         c00 = (double)f00; c01 = (double)f01; c10 = (double)f10; c11 = (double)f11;
     }
     const double top = (k.wx0 * c00) + (k.wx1 * c01), bot = (k.wx0 * c10) + (k.wx1 * c11);
@@ -111,7 +94,7 @@ struct PlateBuildArgs {
 
 template <bool U8, int C>
 __device__ __forceinline__ void plate_store(const PlateBuildArgs& a, size_t o, int c, double v, bool keep) {
-    if (U8) reinterpret_cast<uint8_t*>(a.plate)[o * C + c] = keep ? (uint8_t)plate_byte(v) : (uint8_t)0;
+    if (U8) reinterpret_cast<uint8_t*>(a.plate)[o * C + c] = keep ? (uint8_t)pwc_round_byte(v) : (uint8_t)0;
     else reinterpret_cast<float*>(a.plate)[o * C + c] = keep ? (float)v : 0.f;
 }
 
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(256) void plate_build_kernel(const PlateBuildArgs a
             } else if (U8) {
                 unsigned w = 0u;
 #pragma unroll
-                for (int c = 0; c < C; ++c) w |= plate_byte(v[c]) << (8 * c);
+                for (int c = 0; c < C; ++c) w |= pwc_round_byte(v[c]) << (8 * c);
                 mine[256 * n] = w;
             } else {
                 present |= 1ull << t;
@@ -259,7 +242,7 @@ __global__ __launch_bounds__(256) void plate_difference_kernel(const PlateDiffAr
                     f = (double)reinterpret_cast<const uint8_t*>(a.frames)[(size_t)g * C + c];
                 } else {
                     const float fv = reinterpret_cast<const float*>(a.frames)[(size_t)g * C + c];
-                    fin = fin && plate_finite(fv);
+                    fin = fin && pwc_finite(fv);
                     f = (double)fv;
                 }
                 const double s = plate_blend<U8>(a.plate, 0, C, c, k, &fin);
@@ -275,8 +258,6 @@ __global__ __launch_bounds__(256) void plate_difference_kernel(const PlateDiffAr
 }
 
 // ---------------------------------------------------------------- host
-static inline bool plate_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 template <bool U8, int C>
 static void plate_build_launch(int mean, dim3 grid, size_t lds, hipStream_t s, const PlateBuildArgs& a) {
     if (mean) hipLaunchKernelGGL((plate_build_kernel<U8, C, true>), grid, dim3(256), 0, s, a);
@@ -300,7 +281,7 @@ static int plate_build_call(const void* frames, int dtype, int C, const double* 
         return PWC_EINVAL;
     if ((long)H * W > PLATE_MAX_PIXELS || (long)Hc * Wc > PLATE_MAX_PIXELS) return PWC_ERANGE;
     const bool u8 = dtype == PWC_MOTION_U8;
-    if (plate_off(matrices, 7u) || (!u8 && (plate_off(frames, 3u) || plate_off(plate, 3u)))) return PWC_EALIGN;
+    if (pwc_off(matrices, 7u) || (!u8 && (pwc_off(frames, 3u) || pwc_off(plate, 3u)))) return PWC_EALIGN;
     PlateBuildArgs a = {};
     a.frames = frames; a.matrices = matrices; a.use = use; a.masks = masks; a.plate = plate; a.count = count;
     a.T = T; a.H = H; a.W = W; a.Hc = Hc; a.Wc = Wc; a.min_count = min_count; a.projective = projective;
@@ -340,14 +321,13 @@ static int plate_difference_call(const void* frames, int dtype, int C, const voi
     if ((dtype != PWC_MOTION_U8 && dtype != PWC_MOTION_F32) || min_count < 1 || !(threshold >= 0.0)) return PWC_EINVAL;
     if ((long)H * W > PLATE_MAX_PIXELS || (long)Hc * Wc > PLATE_MAX_PIXELS || T > 65535) return PWC_ERANGE;
     const bool u8 = dtype == PWC_MOTION_U8;
-    if (plate_off(matrices, 7u) || plate_off(difference, 3u) || (!u8 && (plate_off(frames, 3u) || plate_off(plate, 3u))))
+    if (pwc_off(matrices, 7u) || pwc_off(difference, 3u) || (!u8 && (pwc_off(frames, 3u) || pwc_off(plate, 3u))))
         return PWC_EALIGN;
     PlateDiffArgs a = {};
     a.frames = frames; a.plate = plate; a.count = count; a.matrices = matrices; a.difference = difference;
     a.foreground = foreground; a.known = known; a.threshold = threshold;
     a.T = T; a.H = H; a.W = W; a.Hc = Hc; a.Wc = Wc; a.min_count = min_count; a.projective = projective;
-    const long blocks = ((long)T * H * W + 255) / 256;
-    const dim3 grid((unsigned)(blocks > PLATE_MAX_BLOCKS ? PLATE_MAX_BLOCKS : blocks));
+    const dim3 grid = pwc_flat_grid((long)T * H * W);
     if (u8) plate_difference_launch<true>(C, grid, (hipStream_t)stream, a);
     else plate_difference_launch<false>(C, grid, (hipStream_t)stream, a);
     return pwc_launch_status();

@@ -26,8 +26,6 @@
 
 #pragma clang fp contract(off)
 
-#define POSE_SENTINEL 1e10f
-#define POSE_MAX_BLOCKS 4096
 #define POSE_WS 22            // doubles per image: R_a (9), R_b (9), t (3), good (1.0 or 0.0)
 
 struct PoseArgs {
@@ -125,10 +123,10 @@ __global__ __launch_bounds__(64) void pose_decompose_kernel(const PoseArgs a) {
             }
         }
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { t[i] = u3[i]; good = good && two_view_finite(t[i]); }
+        for (int i = 0; i < 3; ++i) { t[i] = u3[i]; good = good && pwc_finite(t[i]); }
 #pragma unroll
-        for (int j = 0; j < 9; ++j) good = good && two_view_finite(Ra[j]) && two_view_finite(Rb[j]) && two_view_finite(E[j]);
-        good = good && two_view_finite(sing[0]) && two_view_finite(sing[1]);
+        for (int j = 0; j < 9; ++j) good = good && pwc_finite(Ra[j]) && pwc_finite(Rb[j]) && pwc_finite(E[j]);
+        good = good && pwc_finite(sing[0]) && pwc_finite(sing[1]);
     }
     double* w = a.ws + (size_t)n * POSE_WS;
 #pragma unroll
@@ -165,8 +163,8 @@ __global__ __launch_bounds__(256) void pose_vote_kernel(const PoseArgs a) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < hw; i += (int)gridDim.x * 256) {
         if (a.valid && !a.valid[img + i]) continue;
         float fu, fv;
-        two_view_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
-        if (!two_view_known(fu, fv)) continue;
+        pwc_flow_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
+        if (!pwc_flow_known(fu, fv)) continue;
         const double x = (double)(i % a.W), y = (double)(i / a.W);
         const double xp = x + (double)fu, yp = y + (double)fv;
         double r, g;
@@ -249,12 +247,12 @@ __global__ __launch_bounds__(256) void pose_depth_kernel(const DepthArgs a) {
         for (int j = 0; j < 3; ++j) t[j] = a.translation[(size_t)q.n * 3 + j];
 #pragma unroll
         for (int j = 0; j < 4; ++j) k[j] = a.intrinsics[(size_t)q.n * 4 + j];
-        float d = POSE_SENTINEL, par = 0.f;
+        float d = PWC_FLOW_SENTINEL, par = 0.f;
         uint8_t kn = 0;
         if (!zero && two_view_intrinsics_fine(k) && !(a.valid && !a.valid[p])) {
             float fu, fv;
-            two_view_load2<VEC>(a.flow + (size_t)p * a.cs, fu, fv);
-            if (two_view_known(fu, fv)) {
+            pwc_flow_load2<VEC>(a.flow + (size_t)p * a.cs, fu, fv);
+            if (pwc_flow_known(fu, fv)) {
                 const double x = (double)q.x, y = (double)q.y;
                 const double xp = x + (double)fu, yp = y + (double)fv;
                 const double d0x = (x - k[2]) / k[0], d0y = (y - k[3]) / k[1], d1x = (xp - k[2]) / k[0], d1y = (yp - k[3]) / k[1];
@@ -278,8 +276,6 @@ __global__ __launch_bounds__(256) void pose_depth_kernel(const DepthArgs a) {
 }
 
 // ---------------------------------------------------------------- host
-static inline bool pose_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 extern "C" size_t pwc_camera_pose_workspace_bytes(int N) {
     if (N <= 0 || N > 65535) return 0;
     return 8 * (size_t)N * POSE_WS;
@@ -293,8 +289,8 @@ extern "C" int pwc_camera_pose_f64(const float* flows, int flow_cs, const uint8_
         return PWC_EINVAL;
     if (N < 1 || H < 1 || W < 1 || flow_cs < 2 || !(threshold >= 0.0)) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (pose_off(flows, 3u) || pose_off(matrices, 7u) || pose_off(intrinsics, 7u) || pose_off(workspace, 7u) || pose_off(rotation, 7u) ||
-        pose_off(translation, 7u) || pose_off(votes, 3u) || pose_off(voters, 3u) || pose_off(singular, 7u) || pose_off(essential, 7u))
+    if (pwc_off(flows, 3u) || pwc_off(matrices, 7u) || pwc_off(intrinsics, 7u) || pwc_off(workspace, 7u) || pwc_off(rotation, 7u) ||
+        pwc_off(translation, 7u) || pwc_off(votes, 3u) || pwc_off(voters, 3u) || pwc_off(singular, 7u) || pwc_off(essential, 7u))
         return PWC_EALIGN;
     if (workspace_bytes < pwc_camera_pose_workspace_bytes(N)) return PWC_EINVAL;
     PoseArgs a = {};
@@ -304,7 +300,7 @@ extern "C" int pwc_camera_pose_f64(const float* flows, int flow_cs, const uint8_
     a.singular = singular; a.essential = essential;
     a.threshold = threshold; a.cs = flow_cs; a.N = N; a.H = H; a.W = W;
     const int parts = (int)pwc_loss_parts(H, W);
-    const bool vec = !(flow_cs & 1) && !pose_off(flows, 7u);
+    const bool vec = pwc_flow_vec(flow_cs, {flows});
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(pose_decompose_kernel, dim3((N + 63) / 64), dim3(64), 0, s, a);
     if (vec) hipLaunchKernelGGL(pose_vote_kernel<true>, dim3(parts, N), dim3(256), 0, s, a);
@@ -319,16 +315,15 @@ extern "C" int pwc_triangulate_depth_f32(const float* flows, int flow_cs, const 
     if (!flows || !rotation || !translation || !intrinsics || !depth || !known) return PWC_EINVAL;
     if (N < 1 || H < 1 || W < 1 || flow_cs < 2 || !(min_parallax >= 0.0)) return PWC_EINVAL;
     if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (pose_off(flows, 3u) || pose_off(depth, 3u) || pose_off(parallax, 3u) || pose_off(rotation, 7u) || pose_off(translation, 7u) ||
-        pose_off(intrinsics, 7u))
+    if (pwc_off(flows, 3u) || pwc_off(depth, 3u) || pwc_off(parallax, 3u) || pwc_off(rotation, 7u) || pwc_off(translation, 7u) ||
+        pwc_off(intrinsics, 7u))
         return PWC_EALIGN;
     DepthArgs a = {};
     a.flow = flows; a.valid = valid; a.rotation = rotation; a.translation = translation; a.intrinsics = intrinsics;
     a.depth = depth; a.known = known; a.parallax = parallax;
     a.min_parallax = min_parallax; a.cs = flow_cs; a.N = N; a.H = H; a.W = W;
-    const bool vec = !(flow_cs & 1) && !pose_off(flows, 7u);
-    const long blocks = ((long)N * H * W + 255) / 256;
-    const dim3 grid((unsigned)(blocks > POSE_MAX_BLOCKS ? POSE_MAX_BLOCKS : blocks));
+    const bool vec = pwc_flow_vec(flow_cs, {flows});
+    const dim3 grid = pwc_loss_grad_blocks(N, H, W);
     const hipStream_t s = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(pose_depth_kernel<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(pose_depth_kernel<false>, grid, dim3(256), 0, s, a);

@@ -6,7 +6,7 @@
 //   pwc_pose_refine_f64               rotation (N, 3, 3), translation (N, 3) doubles, ok (N) bytes, samples and best_pass (N) int32,
 //                                     cost (N, iters + 1) and weight_sum (N) doubles
 //
-// The pass structure is pwc_fundamental_fit_f64's: iters + 1 passes of two launches each on the caller's stream, the device reading
+// The pass structure is robust_fit.h's: iters + 1 passes of two launches each on the caller's stream, the device reading
 // what the pass before wrote.
 //   sums    grid (parts, N), loss_common.h's partition.  The pixel set is decided against the INPUT pose in every pass (the same
 //           pixels each time); a pixel of the set adds the 15 entries of the triangle of w J J^T, the 5 of w J rho, w and w d^2 under
@@ -17,8 +17,8 @@
 // Every value is an IEEE double + - x / sqrt or a comparison in the order written here -- no fused multiply-add is formed anywhere
 // in this file (the pragma below), sqrt on doubles (correctly rounded) is the only library call -- so tests/pose_refine_ref.py
 // restates it in numpy bit for bit.  No atomic, no host synchronisation, no process-wide state.
-#include "loss_common.h"
 #include "motion_ldlt.h"
+#include "robust_fit.h"
 #include "two_view.h"
 
 #pragma clang fp contract(off)
@@ -93,8 +93,8 @@ __global__ __launch_bounds__(256) void pose_refine_sums_kernel(const RefineArgs 
     for (int i = blockIdx.x * 256 + threadIdx.x; i < hw; i += (int)gridDim.x * 256) {
         if (a.valid && !a.valid[img + i]) continue;
         float fu, fv;
-        two_view_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
-        if (!two_view_known(fu, fv)) continue;
+        pwc_flow_load2<VEC>(a.flow + (img + i) * a.cs, fu, fv);
+        if (!pwc_flow_known(fu, fv)) continue;
         const double x = (double)(i % a.W), y = (double)(i / a.W);
         const double xp = x + (double)fu, yp = y + (double)fv;
         const double d0x = (x - cx) / fx, d0y = (y - cy) / fy, d1x = (xp - cx) / fx, d1y = (yp - cy) / fy;
@@ -126,13 +126,7 @@ __global__ __launch_bounds__(256) void pose_refine_sums_kernel(const RefineArgs 
         sum[20] = sum[20] + w;
         sum[21] = sum[21] + (w * d2);
     }
-    pwc_block_tree_sum_f64<REFINE_SUMS, 1>(sum, &cnt);
-    if (threadIdx.x == 0) {
-        const size_t o = (size_t)n * gridDim.x + blockIdx.x;
-#pragma unroll
-        for (int j = 0; j < REFINE_SUMS; ++j) a.part[o * REFINE_SUMS + j] = sum[j];
-        a.part_n[o] = cnt;
-    }
+    pwc_fit_write_part<REFINE_SUMS>(sum, cnt, n, a.part, a.part_n);
 }
 
 // One lane per image.
@@ -159,14 +153,7 @@ __global__ __launch_bounds__(64) void pose_refine_solve_kernel(const RefineArgs 
 #pragma unroll
     for (int j = 0; j < REFINE_SUMS; ++j) S[j] = 0.0;
     int cnt = 0;
-    if (!off) {
-        for (int i = 0; i < a.parts; ++i) {
-            const size_t o = (size_t)n * a.parts + i;
-#pragma unroll
-            for (int j = 0; j < REFINE_SUMS; ++j) S[j] = S[j] + a.part[o * REFINE_SUMS + j];
-            cnt += a.part_n[o];
-        }
-    }
+    if (!off) pwc_fit_gather<REFINE_SUMS>(a.part, a.part_n, n, a.parts, S, cnt);   // (an OFF image's workgroups wrote no part)
     if (first) {
         const bool good = !off && cnt >= REFINE_MIN_SAMPLES;
 #pragma unroll
@@ -190,7 +177,7 @@ __global__ __launch_bounds__(64) void pose_refine_solve_kernel(const RefineArgs 
     }
     bool fin = true;
 #pragma unroll
-    for (int j = 0; j < REFINE_SUMS; ++j) fin = fin && two_view_finite(S[j]);
+    for (int j = 0; j < REFINE_SUMS; ++j) fin = fin && pwc_finite(S[j]);
     if (!first) {
         if (!fin) {
             cost[a.pass] = 0.0;
@@ -239,9 +226,9 @@ __global__ __launch_bounds__(64) void pose_refine_solve_kernel(const RefineArgs 
             for (int i = 0; i < 3; ++i) u[i] = (t[i] + (r[0][3] * b1[i])) + (r[0][4] * b2[i]);
             const double nrm = sqrt(((u[0] * u[0]) + (u[1] * u[1])) + (u[2] * u[2]));
 #pragma unroll
-            for (int i = 0; i < 3; ++i) { tn[i] = u[i] / nrm; live = live && two_view_finite(tn[i]); }
+            for (int i = 0; i < 3; ++i) { tn[i] = u[i] / nrm; live = live && pwc_finite(tn[i]); }
 #pragma unroll
-            for (int j = 0; j < 9; ++j) live = live && two_view_finite(Rn[j]);
+            for (int j = 0; j < 9; ++j) live = live && pwc_finite(Rn[j]);
         }
     }
     if (live) {
@@ -258,12 +245,8 @@ __global__ __launch_bounds__(64) void pose_refine_solve_kernel(const RefineArgs 
 }
 
 // ---------------------------------------------------------------- host
-static inline bool refine_misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 extern "C" size_t pwc_pose_refine_workspace_bytes(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0 || !pwc_loss_in_range(N, H, W)) return 0;
-    const size_t cells = (size_t)N * pwc_loss_parts(H, W);
-    return 8 * (cells * REFINE_SUMS + (size_t)N * REFINE_STATE) + ((4 * cells + 7) & ~(size_t)7);
+    return pwc_fit_workspace_bytes(N, H, W, REFINE_SUMS, REFINE_STATE);
 }
 
 extern "C" int pwc_pose_refine_f64(const float* flows, int flow_cs, const uint8_t* valid, const double* intrinsics,
@@ -271,29 +254,22 @@ extern "C" int pwc_pose_refine_f64(const float* flows, int flow_cs, const uint8_
                                    double threshold, void* workspace, size_t workspace_bytes, double* rotation, double* translation,
                                    uint8_t* ok, int32_t* samples, int32_t* best_pass, double* cost, double* weight_sum,
                                    pwc_stream_t stream) {
-    if (!flows || !intrinsics || !rotation0 || !translation0 || !workspace || !rotation || !translation || !ok || !samples || !best_pass ||
-        !cost || !weight_sum)
+    if (!intrinsics || !rotation0 || !translation0 || !rotation || !translation || !ok || !samples || !best_pass || !cost || !weight_sum)
         return PWC_EINVAL;
-    if (N < 1 || H < 1 || W < 1 || iters < 0 || iters > PWC_MOTION_MAX_ITERS || !(scale > 0.0) || !(threshold >= 0.0) || flow_cs < 2)
-        return PWC_EINVAL;
-    if (!pwc_loss_in_range(N, H, W)) return PWC_ERANGE;
-    if (refine_misaligned(flows, 3u) || refine_misaligned(intrinsics, 7u) || refine_misaligned(rotation0, 7u) ||
-        refine_misaligned(translation0, 7u) || refine_misaligned(workspace, 7u) || refine_misaligned(rotation, 7u) ||
-        refine_misaligned(translation, 7u) || refine_misaligned(samples, 3u) || refine_misaligned(best_pass, 3u) ||
-        refine_misaligned(cost, 7u) || refine_misaligned(weight_sum, 7u))
-        return PWC_EALIGN;
-    if (workspace_bytes < pwc_pose_refine_workspace_bytes(N, H, W)) return PWC_EINVAL;
+    if (!(threshold >= 0.0)) return PWC_EINVAL;
+    const int rc = pwc_fit_check(flows, flow_cs, N, H, W, iters, scale, workspace, workspace_bytes, pwc_pose_refine_workspace_bytes(N, H, W),
+                                 pwc_off(intrinsics, 7u) || pwc_off(rotation0, 7u) || pwc_off(translation0, 7u) ||
+                                     pwc_off(rotation, 7u) || pwc_off(translation, 7u) || pwc_off(samples, 3u) ||
+                                     pwc_off(best_pass, 3u) || pwc_off(cost, 7u) || pwc_off(weight_sum, 7u));
+    if (rc != PWC_OK) return rc;
     const int parts = (int)pwc_loss_parts(H, W);
-    const size_t cells = (size_t)N * parts;
     RefineArgs a = {};
     a.flow = flows; a.valid = valid; a.intrinsics = intrinsics; a.rotation0 = rotation0; a.translation0 = translation0;
-    a.part = reinterpret_cast<double*>(workspace);
-    a.state = a.part + cells * REFINE_SUMS;
-    a.part_n = reinterpret_cast<int*>(a.state + (size_t)N * REFINE_STATE);
+    pwc_fit_carve(workspace, N, parts, REFINE_SUMS, REFINE_STATE, a.part, a.state, a.part_n);
     a.rotation = rotation; a.translation = translation; a.ok = ok; a.samples = samples; a.best_pass = best_pass;
     a.cost = cost; a.weight_sum = weight_sum;
     a.scale = scale; a.threshold = threshold; a.cs = flow_cs; a.N = N; a.H = H; a.W = W; a.parts = parts; a.iters = iters;
-    const bool vec = !(flow_cs & 1) && !refine_misaligned(flows, 7u);
+    const bool vec = pwc_flow_vec(flow_cs, {flows});
     const hipStream_t s = (hipStream_t)stream;
     const dim3 grid(parts, N);
     for (int pass = 0; pass <= iters; ++pass) {

@@ -26,7 +26,7 @@
 // pwc_relabel_regions one launch with a lane per pixel.
 // No host synchronisation, no process-wide state, no floating-point atomic, and no loop that waits for another lane or
 // workgroup: every loop's bound is stated next to it.  Between launches the stream's order is the hand-off.
-#include "pwc_common.h"
+#include "flow_record.h"
 
 #pragma clang fp contract(off)
 
@@ -60,9 +60,6 @@ __global__ __launch_bounds__(256) void links_clear_kernel(const LinksArgs a) {
 }
 
 // ---------------------------------------------------------------- vote
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool links_known(float u, float v) { return fabsf(u) <= 1e9f && fabsf(v) <= 1e9f; }
-
 __global__ __launch_bounds__(256) void links_vote_kernel(const LinksArgs a) {
     const int hw = a.H * a.W, lane = threadIdx.x & 63;
     const long i = blockIdx.x * 256L + threadIdx.x;
@@ -73,7 +70,7 @@ __global__ __launch_bounds__(256) void links_vote_kernel(const LinksArgs a) {
         if (la >= 1 && la <= a.R && (!a.valid || a.valid[img + i] != 0)) {
             const float* f = a.flow + (img + i) * a.cs;
             const float u = f[0], v = f[1];
-            if (links_known(u, v)) {
+            if (pwc_flow_known(u, v)) {
                 const int x = (int)(i % a.W), y = (int)(i / a.W);
                 const double qx = rint((double)x + (double)u), qy = rint((double)y + (double)v);
                 int c = a.R + 1;                     // the column of left[a]
@@ -239,7 +236,6 @@ __global__ __launch_bounds__(256) void links_relabel_kernel(const int* __restric
 }
 
 // ---------------------------------------------------------------- host
-static inline bool links_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 static inline bool links_in_range(int N, int H, int W) { return (long)H * W <= LINKS_MAX_PIXELS && N <= LINKS_MAX_IMAGES; }
 
 extern "C" size_t pwc_region_links_workspace_bytes(int N, int max_regions) {
@@ -256,9 +252,9 @@ extern "C" int pwc_link_regions(const int32_t* labels_a, const int32_t* labels_b
     if (N < 1 || H < 1 || W < 1 || max_regions < 1 || min_overlap < 1 || !(min_fraction >= 0.0 && min_fraction <= 1.0) || flow_cs < 2)
         return PWC_EINVAL;
     if (!links_in_range(N, H, W) || max_regions > LINKS_MAX_REGIONS) return PWC_ERANGE;
-    if (links_off(labels_a, 3u) || links_off(labels_b, 3u) || links_off(area_a, 3u) || links_off(area_b, 3u) || links_off(flows_ab, 3u) ||
-        links_off(workspace, 7u) || links_off(succ, 3u) || links_off(pred, 3u) || links_off(best_succ, 3u) || links_off(best_pred, 3u) ||
-        links_off(votes, 3u))
+    if (pwc_off(labels_a, 3u) || pwc_off(labels_b, 3u) || pwc_off(area_a, 3u) || pwc_off(area_b, 3u) || pwc_off(flows_ab, 3u) ||
+        pwc_off(workspace, 7u) || pwc_off(succ, 3u) || pwc_off(pred, 3u) || pwc_off(best_succ, 3u) || pwc_off(best_pred, 3u) ||
+        pwc_off(votes, 3u))
         return PWC_EALIGN;
     if (workspace_bytes < pwc_region_links_workspace_bytes(N, max_regions)) return PWC_EINVAL;
     LinksArgs a = {};
@@ -285,8 +281,8 @@ extern "C" int pwc_region_identities(const int32_t* pred, const int32_t* count, 
     if ((ids_prev != nullptr) != (age_prev != nullptr) || (ids_prev != nullptr) != (pred_prev != nullptr)) return PWC_EINVAL;
     if (S < 1 || max_regions < 1 || next_id < 1) return PWC_EINVAL;
     if (max_regions > LINKS_MAX_REGIONS || (long)next_id + (long)S * max_regions >= (1L << 31)) return PWC_ERANGE;
-    if (links_off(pred, 3u) || links_off(count, 3u) || links_off(ids_prev, 3u) || links_off(age_prev, 3u) || links_off(pred_prev, 3u) ||
-        links_off(next_id_in, 3u) || links_off(ids, 3u) || links_off(age, 3u) || links_off(next_id_out, 3u))
+    if (pwc_off(pred, 3u) || pwc_off(count, 3u) || pwc_off(ids_prev, 3u) || pwc_off(age_prev, 3u) || pwc_off(pred_prev, 3u) ||
+        pwc_off(next_id_in, 3u) || pwc_off(ids, 3u) || pwc_off(age, 3u) || pwc_off(next_id_out, 3u))
         return PWC_EALIGN;
     IdentArgs a = {};
     a.pred = pred; a.count = count; a.ids_prev = ids_prev; a.age_prev = age_prev; a.pred_prev = pred_prev; a.next_id_in = next_id_in;
@@ -301,7 +297,7 @@ extern "C" int pwc_relabel_regions(const int32_t* labels, const int32_t* ids, in
     if (!labels || !ids || !out) return PWC_EINVAL;
     if (S < 1 || H < 1 || W < 1 || max_regions < 1) return PWC_EINVAL;
     if (!links_in_range(S, H, W) || max_regions > LINKS_MAX_REGIONS) return PWC_ERANGE;
-    if (links_off(labels, 3u) || links_off(ids, 3u) || links_off(out, 3u)) return PWC_EALIGN;
+    if (pwc_off(labels, 3u) || pwc_off(ids, 3u) || pwc_off(out, 3u)) return PWC_EALIGN;
     hipLaunchKernelGGL(links_relabel_kernel, dim3((unsigned)(((long)H * W + 255) / 256), (unsigned)S), dim3(256), 0,
                        (hipStream_t)stream, labels, ids, H * W, max_regions, out);
     return pwc_launch_status();

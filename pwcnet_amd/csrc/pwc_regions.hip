@@ -44,7 +44,7 @@
 // Termination: no loop waits for another lane or workgroup.  A find follows parents to STRICTLY smaller indices and stops at
 // the first that is not; a union retries with the value its atomicMin returned, which is strictly smaller than the index it
 // was applied to.  Both are bounded by the index they start from.
-#include "pwc_common.h"
+#include "flow_record.h"
 
 #pragma clang fp contract(off)
 
@@ -71,15 +71,12 @@ struct RegionsArgs {
     int invert, cs, N, H, W, conn8, min_area, R, parts, chunk, tiles_x, tiles_y;
 };
 
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool regions_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-
 // FOREGROUND: the mask byte (inverted: its absence), and a known flow where one is given; a flow the mask excludes is not loaded.
 __device__ __forceinline__ bool regions_foreground(const RegionsArgs& a, size_t g) {
     if ((a.mask[g] != 0) == (a.invert != 0)) return false;
     if (!a.flow) return true;
     const float* f = a.flow + g * a.cs;
-    return regions_known(f[0], f[1]);
+    return pwc_flow_known(f[0], f[1]);
 }
 
 // ---------------------------------------------------------------- clear
@@ -397,7 +394,6 @@ __global__ __launch_bounds__(256) void regions_mean_kernel(const RegionsArgs a) 
 }
 
 // ---------------------------------------------------------------- host
-static inline bool regions_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 static inline bool regions_in_range(int N, int H, int W) { return (long)H * W <= REGIONS_MAX_PIXELS && N <= 65535; }
 static inline int regions_parts(int H, int W) {
     const long parts = ((long)H * W + 255) / 256;
@@ -422,8 +418,8 @@ extern "C" int pwc_label_regions(const uint8_t* mask, int invert, const float* f
         max_regions > REGIONS_MAX_REGIONS || (flows && flow_cs < 2))
         return PWC_EINVAL;
     if (!regions_in_range(N, H, W)) return PWC_ERANGE;
-    if (regions_off(flows, 3u) || regions_off(workspace, 7u) || regions_off(labels, 3u) || regions_off(count, 3u) ||
-        regions_off(area, 3u) || regions_off(box, 3u) || regions_off(sums, 7u) || regions_off(mean, 7u))
+    if (pwc_off(flows, 3u) || pwc_off(workspace, 7u) || pwc_off(labels, 3u) || pwc_off(count, 3u) ||
+        pwc_off(area, 3u) || pwc_off(box, 3u) || pwc_off(sums, 7u) || pwc_off(mean, 7u))
         return PWC_EALIGN;
     if (workspace_bytes < pwc_regions_workspace_bytes(N, H, W)) return PWC_EINVAL;
     const size_t npix = (size_t)N * H * W;

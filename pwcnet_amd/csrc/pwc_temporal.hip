@@ -19,7 +19,7 @@
 // Every value is an IEEE double + - x /, a floor, a rint or a comparison in the order written here -- no fused multiply-add is
 // formed anywhere in this file (the pragma below) -- so tests/temporal_ref.py restates it in numpy bit for bit.  No atomics, no
 // workspace, no host synchronisation, no process-wide state; frame and flow offsets are 64-bit.
-#include "pwc_common.h"
+#include "flow_record.h"
 
 #pragma clang fp contract(off)
 
@@ -42,9 +42,6 @@ struct TemporalArgs {
     float alpha1, alpha2;
 };
 
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool temporal_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-
 __device__ __forceinline__ bool temporal_inside(double qx, double qy, int H, int W) {
     return qx >= 0.0 && qx <= (double)(W - 1) && qy >= 0.0 && qy <= (double)(H - 1);
 }
@@ -53,16 +50,14 @@ __device__ __forceinline__ bool temporal_inside(double qx, double qy, int H, int
 // where a corner is masked out or unknown.
 __device__ __forceinline__ bool temporal_sample(const float* f, int cs, const uint8_t* m, int H, int W, double qx, double qy,
                                                 double& s0, double& s1) {
-    const double fx0 = floor(qx), fy0 = floor(qy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    const double wx = qx - fx0, wy = qy - fy0;
-    const size_t o00 = (size_t)y0 * W + x0, o01 = (size_t)y0 * W + x1, o10 = (size_t)y1 * W + x0, o11 = (size_t)y1 * W + x1;
+    const PwcBilinearF64 bl = pwc_bilinear_f64(qx, qy, H, W);
+    const double wx = bl.wx1, wy = bl.wy1;
+    const size_t o00 = bl.o00, o01 = bl.o01, o10 = bl.o10, o11 = bl.o11;
     if (m && !(m[o00] && m[o01] && m[o10] && m[o11])) return false;
     const float* p00 = f + o00 * cs; const float* p01 = f + o01 * cs; const float* p10 = f + o10 * cs; const float* p11 = f + o11 * cs;
     const float a00 = p00[0], b00 = p00[1], a01 = p01[0], b01 = p01[1], a10 = p10[0], b10 = p10[1], a11 = p11[0], b11 = p11[1];
-    if (!(temporal_known(a00, b00) && temporal_known(a01, b01) && temporal_known(a10, b10) && temporal_known(a11, b11))) return false;
-    const double ux = 1.0 - wx, uy = 1.0 - wy;
+    if (!(pwc_flow_known(a00, b00) && pwc_flow_known(a01, b01) && pwc_flow_known(a10, b10) && pwc_flow_known(a11, b11))) return false;
+    const double ux = bl.wx0, uy = bl.wy0;
     s0 = (uy * ((ux * (double)a00) + (wx * (double)a01))) + (wy * ((ux * (double)a10) + (wx * (double)a11)));
     s1 = (uy * ((ux * (double)b00) + (wx * (double)b01))) + (wy * ((ux * (double)b10) + (wx * (double)b11)));
     return true;
@@ -96,12 +91,6 @@ __device__ __forceinline__ double temporal_grey(const void* frames, size_t o) {
     if (U8) return (double)reinterpret_cast<const uint8_t*>(frames)[o];
     const double v = (double)reinterpret_cast<const float*>(frames)[o];
     return v == v ? 255.0 * v : 0.0;
-}
-
-// A double as a byte: rint, ties to even, clamped to [0, 255]; 0 for a NaN (pwc_motion.hip's).
-__device__ __forceinline__ unsigned temporal_byte(double v) {
-    const double t = rint(v);
-    return t >= 255.0 ? 255u : (t >= 0.0 ? (unsigned)(int)t : 0u);
 }
 
 template <bool U8, int C, int P>
@@ -159,6 +148,7 @@ __global__ __launch_bounds__(256) void temporal_filter_kernel(const TemporalArgs
             if (!alive) continue;
             // the samples of frame f around q = (x, y), which is inside the frame
             const double qx = (double)x, qy = (double)y;
+            // (not pwc_bilinear_f64: the footprint of a patch, S + 1 rows and columns each clamped on both sides)
             const double fx0 = floor(qx), fy0 = floor(qy);
             const int x0 = (int)fx0, y0 = (int)fy0;
             const double wx = qx - fx0, wy = qy - fy0, ux = 1.0 - wx, uy = 1.0 - wy;
@@ -215,14 +205,12 @@ __global__ __launch_bounds__(256) void temporal_filter_kernel(const TemporalArgs
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const double v = acc[c] / wsum;
-        if (U8) reinterpret_cast<uint8_t*>(a.out)[o * C + c] = (uint8_t)temporal_byte(v);
+        if (U8) reinterpret_cast<uint8_t*>(a.out)[o * C + c] = (uint8_t)pwc_round_byte(v);
         else reinterpret_cast<float*>(a.out)[o * C + c] = (float)(v / 255.0);
     }
 }
 
 // ---------------------------------------------------------------- host
-static inline bool temporal_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 template <bool U8, int C>
 static void temporal_launch(int P, dim3 grid, hipStream_t s, const TemporalArgs& a) {
     if (P == 0) hipLaunchKernelGGL((temporal_filter_kernel<U8, C, 0>), grid, dim3(256), 0, s, a);
@@ -239,7 +227,7 @@ extern "C" int pwc_temporal_filter(const void* frames, int dtype, int C, const f
     if ((dtype != PWC_TEMPORAL_U8 && dtype != PWC_TEMPORAL_F32) || (C != 1 && C != 3)) return PWC_EINVAL;
     if (radius < 1 || radius > PWC_TEMPORAL_MAX_RADIUS || patch < 0 || patch > PWC_TEMPORAL_MAX_PATCH) return PWC_EINVAL;
     // (a NaN fails; sigma sigma must be a positive finite double too)
-    if (!(sigma > 0.0) || !(sigma * sigma > 0.0) || !(sigma * sigma <= 1.7976931348623157e308) || max_distance != max_distance)
+    if (!(sigma > 0.0) || !(sigma * sigma > 0.0) || !pwc_finite(sigma * sigma) || max_distance != max_distance)
         return PWC_EINVAL;
     if (fb_check && (!(alpha1 >= 0.f) || !(alpha2 >= 0.f))) return PWC_EINVAL;
     if (i0 < 0 || i1 > T || i0 >= i1) return PWC_EINVAL;
@@ -247,7 +235,7 @@ extern "C" int pwc_temporal_filter(const void* frames, int dtype, int C, const f
     if (H > (1 << 24) || W > (1 << 24) || (long)H * W >= (1L << 31) || T > 65535 || (H + TEMPORAL_TILE_H - 1) / TEMPORAL_TILE_H > 65535)
         return PWC_ERANGE;
     const bool u8 = dtype == PWC_TEMPORAL_U8;
-    if ((T > 1 && (temporal_off(flows_fw, 3u) || temporal_off(flows_bw, 3u))) || (!u8 && (temporal_off(frames, 3u) || temporal_off(filtered, 3u))))
+    if ((T > 1 && (pwc_off(flows_fw, 3u) || pwc_off(flows_bw, 3u))) || (!u8 && (pwc_off(frames, 3u) || pwc_off(filtered, 3u))))
         return PWC_EALIGN;
     TemporalArgs a = {};
     a.frames = frames; a.fw = flows_fw; a.bw = flows_bw; a.vfw = T > 1 ? valids_fw : nullptr; a.vbw = T > 1 ? valids_bw : nullptr;

@@ -25,8 +25,8 @@
 // lanes of a wave store neighbouring records of one slice.  No LDS, no atomics, no workspace; 64-bit indices into (T + 1) P.
 // Flows at any channel stride >= 2: where every float pointer of a call is on an 8-byte boundary and every channel stride is
 // even a record's two floats are one 8-byte access, else two 4-byte ones -- the values, and so every bit, are the same
-// (pwc_compose.hip's arrangement).
-#include "pwc_common.h"
+// (flow_record.h).
+#include "flow_record.h"
 
 #pragma clang fp contract(off)
 
@@ -46,27 +46,6 @@ struct TrackArgs {
     float alpha1, alpha2;
 };
 
-template <bool VEC>
-__device__ __forceinline__ void track_load2(const float* p, float& a, float& b) {
-    if (VEC) {
-        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
-        a = v[0]; b = v[1];
-    } else {
-        a = p[0]; b = p[1];
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void track_store2(float* p, float a, float b) {
-    if (VEC) {
-        *reinterpret_cast<f32x2*>(p) = f32x2{a, b};
-    } else {
-        p[0] = a; p[1] = b;
-    }
-}
-
-// The .flo sentinel rule (flow_io.flow_valid): false for a NaN, an Inf, the sentinel.
-__device__ __forceinline__ bool track_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-
 __device__ __forceinline__ bool track_inside(double qx, double qy, int H, int W) {
     return qx >= 0.0 && qx <= (double)(W - 1) && qy >= 0.0 && qy <= (double)(H - 1);
 }
@@ -76,21 +55,19 @@ __device__ __forceinline__ bool track_inside(double qx, double qy, int H, int W)
 template <bool VEC>
 __device__ __forceinline__ bool track_sample(const float* f, int cs, const uint8_t* m, int H, int W, double qx, double qy,
                                              double& s0, double& s1) {
-    const double fx0 = floor(qx), fy0 = floor(qy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    const double wx = qx - fx0, wy = qy - fy0;
-    const size_t o00 = (size_t)y0 * W + x0, o01 = (size_t)y0 * W + x1, o10 = (size_t)y1 * W + x0, o11 = (size_t)y1 * W + x1;
+    const PwcBilinearF64 bl = pwc_bilinear_f64(qx, qy, H, W);
+    const double wx = bl.wx1, wy = bl.wy1;
+    const size_t o00 = bl.o00, o01 = bl.o01, o10 = bl.o10, o11 = bl.o11;
     if (m && !(m[o00] && m[o01] && m[o10] && m[o11])) return false;
     float c00[2], c01[2], c10[2], c11[2];
-    track_load2<VEC>(f + o00 * cs, c00[0], c00[1]);
-    track_load2<VEC>(f + o01 * cs, c01[0], c01[1]);
-    track_load2<VEC>(f + o10 * cs, c10[0], c10[1]);
-    track_load2<VEC>(f + o11 * cs, c11[0], c11[1]);
-    if (!(track_known(c00[0], c00[1]) && track_known(c01[0], c01[1]) && track_known(c10[0], c10[1]) &&
-          track_known(c11[0], c11[1])))
+    pwc_flow_load2<VEC>(f + o00 * cs, c00[0], c00[1]);
+    pwc_flow_load2<VEC>(f + o01 * cs, c01[0], c01[1]);
+    pwc_flow_load2<VEC>(f + o10 * cs, c10[0], c10[1]);
+    pwc_flow_load2<VEC>(f + o11 * cs, c11[0], c11[1]);
+    if (!(pwc_flow_known(c00[0], c00[1]) && pwc_flow_known(c01[0], c01[1]) && pwc_flow_known(c10[0], c10[1]) &&
+          pwc_flow_known(c11[0], c11[1])))
         return false;
-    const double ux = 1.0 - wx, uy = 1.0 - wy;
+    const double ux = bl.wx0, uy = bl.wy0;
     s0 = (uy * ((ux * (double)c00[0]) + (wx * (double)c01[0]))) + (wy * ((ux * (double)c10[0]) + (wx * (double)c11[0])));
     s1 = (uy * ((ux * (double)c00[1]) + (wx * (double)c01[1]))) + (wy * ((ux * (double)c10[1]) + (wx * (double)c11[1])));
     return true;
@@ -128,28 +105,28 @@ __global__ __launch_bounds__(256) void track_points_kernel(const TrackArgs a) {
     const long P = a.P;
     for (long p = blockIdx.x * 256L + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
         float px, py;
-        track_load2<VEC>(a.points + 2 * p, px, py);
+        pwc_flow_load2<VEC>(a.points + 2 * p, px, py);
         int s0 = a.start ? a.start[p] : 0;
         int st = a.status_in ? (int)a.status_in[p] : PWC_TRACK_UNSEEN;
         if (st != PWC_TRACK_UNSEEN) {
             s0 = 0;                                                        // the streaming form: the state of slice 0 is given
         } else if (s0 < 0 || s0 > a.T) {                                   // not in this call
             for (long t = 0; t <= a.T; ++t) {
-                track_store2<VEC>(a.tracks + 2 * (t * P + p), px, py);
+                pwc_flow_store2<VEC>(a.tracks + 2 * (t * P + p), px, py);
                 a.status[t * P + p] = PWC_TRACK_UNSEEN;
             }
             continue;
         } else {
             st = track_inside((double)px, (double)py, a.H, a.W) ? PWC_TRACK_VISIBLE : PWC_TRACK_LEFT;
         }
-        track_store2<VEC>(a.tracks + 2 * ((long)s0 * P + p), px, py);
+        pwc_flow_store2<VEC>(a.tracks + 2 * ((long)s0 * P + p), px, py);
         a.status[(long)s0 * P + p] = (uint8_t)st;
         float x = px, y = py;
         int s = st;
         for (long t = s0; t < a.T; ++t) {
             track_step<VEC>(a, a.fw + t * frame * a.fw_cs, a.fw_cs, a.vfw ? a.vfw + t * frame : nullptr,
                             a.bw ? a.bw + t * frame * a.bw_cs : nullptr, a.bw_cs, a.vbw ? a.vbw + t * frame : nullptr, x, y, s);
-            track_store2<VEC>(a.tracks + 2 * ((t + 1) * P + p), x, y);
+            pwc_flow_store2<VEC>(a.tracks + 2 * ((t + 1) * P + p), x, y);
             a.status[(t + 1) * P + p] = (uint8_t)s;
         }
         x = px; y = py; s = st;
@@ -160,15 +137,13 @@ __global__ __launch_bounds__(256) void track_points_kernel(const TrackArgs a) {
             } else {
                 s = PWC_TRACK_UNSEEN;
             }
-            track_store2<VEC>(a.tracks + 2 * ((t - 1) * P + p), x, y);
+            pwc_flow_store2<VEC>(a.tracks + 2 * ((t - 1) * P + p), x, y);
             a.status[(t - 1) * P + p] = (uint8_t)s;
         }
     }
 }
 
 // ---------------------------------------------------------------- host
-static inline bool track_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 extern "C" int pwc_track_points_f32(const float* flows_fw, int fw_cs, const float* flows_bw, int bw_cs, const uint8_t* valids_fw,
                                     const uint8_t* valids_bw, int T, int H, int W, const float* points, const int32_t* start,
                                     const uint8_t* status_in, int P, int direction, float alpha1, float alpha2,
@@ -180,8 +155,8 @@ extern "C" int pwc_track_points_f32(const float* flows_fw, int fw_cs, const floa
     if (flows_bw && (!(alpha1 >= 0.f) || !(alpha2 >= 0.f))) return PWC_EINVAL;     // (a NaN fails both)
     // (float)rx with rx <= W - 1 stays inside the frame only while W - 1 is a float32: W <= 2^24
     if (H > (1 << 24) || W > (1 << 24) || (long)H * W >= (1L << 31) || T > 65535) return PWC_ERANGE;
-    if (track_off(flows_fw, 3u) || (flows_bw && track_off(flows_bw, 3u)) || track_off(points, 3u) || track_off(tracks, 3u) ||
-        (start && track_off(start, 3u)))
+    if (pwc_off(flows_fw, 3u) || (flows_bw && pwc_off(flows_bw, 3u)) || pwc_off(points, 3u) || pwc_off(tracks, 3u) ||
+        (start && pwc_off(start, 3u)))
         return PWC_EALIGN;
     TrackArgs a = {};
     a.fw = flows_fw; a.bw = flows_bw; a.vfw = valids_fw; a.vbw = flows_bw ? valids_bw : nullptr;
@@ -190,10 +165,8 @@ extern "C" int pwc_track_points_f32(const float* flows_fw, int fw_cs, const floa
     a.both = direction == PWC_TRACK_BOTH ? 1 : 0;
     a.stop = stop_on_occlusion ? 1 : 0;
     a.alpha1 = alpha1; a.alpha2 = alpha2;
-    const bool vec = !((a.fw_cs | a.bw_cs) & 1) && !track_off(flows_fw, 7u) && !(flows_bw && track_off(flows_bw, 7u)) &&
-                     !track_off(points, 7u) && !track_off(tracks, 7u);
-    const long blocks = ((long)P + 255) / 256;
-    const dim3 grid((unsigned)(blocks > 4096 ? 4096 : blocks));
+    const bool vec = pwc_flow_vec(a.fw_cs | a.bw_cs, {flows_fw, flows_bw, points, tracks});
+    const dim3 grid = pwc_flat_grid(P);
     if (vec) hipLaunchKernelGGL(track_points_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(track_points_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return pwc_launch_status();

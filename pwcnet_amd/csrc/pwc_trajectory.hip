@@ -121,18 +121,16 @@ __global__ __launch_bounds__(256) void trj_keys_kernel(const LinkArgs a) {
         unsigned key = 0u;
         if (i < hw && !dead && known[i]) {
             float fu, fv;
-            two_view_load2<VEC>(flow + (size_t)i * cs, fu, fv);
-            if (two_view_known(fu, fv)) {
+            pwc_flow_load2<VEC>(flow + (size_t)i * cs, fu, fv);
+            if (pwc_flow_known(fu, fv)) {
                 const double x = (double)(i % a.W), y = (double)(i / a.W);
                 const double qx = x + (double)fu, qy = y + (double)fv;
                 // compose_flows' rule: q in frame (which keeps the four corner reads inside the image) and ALL FOUR corners known
                 if (qx >= 0.0 && qx <= (double)(a.W - 1) && qy >= 0.0 && qy <= (double)(a.H - 1)) {
-                    const double fx0 = floor(qx), fy0 = floor(qy);
-                    const int x0 = (int)fx0, y0 = (int)fy0;
-                    const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);
-                    const int o00 = y0 * a.W + x0, o01 = y0 * a.W + x1, o10 = y1 * a.W + x0, o11 = y1 * a.W + x1;
+                    const PwcBilinearF64 bl = pwc_bilinear_f64(qx, qy, a.H, a.W);
+                    const size_t o00 = bl.o00, o01 = bl.o01, o10 = bl.o10, o11 = bl.o11;
                     if (known_b[o00] && known_b[o01] && known_b[o10] && known_b[o11]) {
-                        const double wx1 = qx - fx0, wy1 = qy - fy0, wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+                        const double wx0 = bl.wx0, wx1 = bl.wx1, wy0 = bl.wy0, wy1 = bl.wy1;
                         const double top = (wx0 * (double)depth[o00]) + (wx1 * (double)depth[o01]);
                         const double bot = (wx0 * (double)depth[o10]) + (wx1 * (double)depth[o11]);
                         const double d = (wy0 * top) + (wy1 * bot);
@@ -319,8 +317,6 @@ __global__ __launch_bounds__(64) void trj_chain_kernel(const TrajectoryArgs a) {
 }
 
 // ---------------------------------------------------------------- host
-static inline bool trj_off(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 static inline bool trj_in_range(int T, int H, int W) { return (long)H * W <= TRJ_MAX_PIXELS && T <= 65535; }
 
 // per seam: the selection record and the three tables (one memset clears them), then the keys
@@ -342,9 +338,9 @@ extern "C" int pwc_scale_links_f32(const float* flows, int flow_cs, const double
     const bool has_prev = prev_flow != nullptr;
     if (has_prev && (!prev_rotation || !prev_translation || !prev_intrinsics || !prev_known || prev_cs < 2)) return PWC_EINVAL;
     if (!trj_in_range(T, H, W)) return PWC_ERANGE;
-    if (trj_off(flows, 3u) || trj_off(prev_flow, 3u) || trj_off(depth, 3u) || trj_off(ratio, 3u) || trj_off(samples, 3u) ||
-        trj_off(rotation, 7u) || trj_off(translation, 7u) || trj_off(intrinsics, 7u) || trj_off(prev_rotation, 7u) ||
-        trj_off(prev_translation, 7u) || trj_off(prev_intrinsics, 7u) || trj_off(workspace, 7u))
+    if (pwc_off(flows, 3u) || pwc_off(prev_flow, 3u) || pwc_off(depth, 3u) || pwc_off(ratio, 3u) || pwc_off(samples, 3u) ||
+        pwc_off(rotation, 7u) || pwc_off(translation, 7u) || pwc_off(intrinsics, 7u) || pwc_off(prev_rotation, 7u) ||
+        pwc_off(prev_translation, 7u) || pwc_off(prev_intrinsics, 7u) || pwc_off(workspace, 7u))
         return PWC_EALIGN;
     if (workspace_bytes < pwc_scale_links_workspace_bytes(T, H, W, has_prev ? 1 : 0)) return PWC_EINVAL;
     const int seams = T - 1 + (has_prev ? 1 : 0);
@@ -363,7 +359,7 @@ extern "C" int pwc_scale_links_f32(const float* flows, int flow_cs, const double
     if (me == hipSuccess && seams > 0) me = hipMemsetAsync(workspace, 0, 4 * trj_table_words(seams), s);
     if (me != hipSuccess) { (void)hipGetLastError(); return (int)me; }      // the memset's OWN error, never PWC_OK
     if (seams == 0) return pwc_launch_status();
-    const bool vec = !((flow_cs | a.pcs) & 1) && !trj_off(flows, 7u) && !trj_off(prev_flow, 7u);
+    const bool vec = pwc_flow_vec(flow_cs | a.pcs, {flows, prev_flow});
     const dim3 parts((unsigned)pwc_loss_parts(H, W), (unsigned)seams), one((unsigned)seams);
     if (vec) hipLaunchKernelGGL(trj_keys_kernel<true>, parts, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(trj_keys_kernel<false>, parts, dim3(256), 0, s, a);
@@ -384,9 +380,9 @@ extern "C" int pwc_camera_trajectory_f64(const double* rotation, const double* t
     if (T < 1 || min_samples < 1) return PWC_EINVAL;
     if (prev_rotation && (!prev_row || !prev_scale || !prev_segment)) return PWC_EINVAL;
     if (T > 65535) return PWC_ERANGE;
-    if (trj_off(rotation, 7u) || trj_off(translation, 7u) || trj_off(prev_rotation, 7u) || trj_off(prev_row, 7u) ||
-        trj_off(prev_scale, 7u) || trj_off(trajectory, 7u) || trj_off(scales, 7u) || trj_off(ratio, 3u) || trj_off(samples, 3u) ||
-        trj_off(prev_segment, 3u) || trj_off(segment, 3u) || trj_off(segment_state, 3u))
+    if (pwc_off(rotation, 7u) || pwc_off(translation, 7u) || pwc_off(prev_rotation, 7u) || pwc_off(prev_row, 7u) ||
+        pwc_off(prev_scale, 7u) || pwc_off(trajectory, 7u) || pwc_off(scales, 7u) || pwc_off(ratio, 3u) || pwc_off(samples, 3u) ||
+        pwc_off(prev_segment, 3u) || pwc_off(segment, 3u) || pwc_off(segment_state, 3u))
         return PWC_EALIGN;
     TrajectoryArgs a = {};
     a.rotation = rotation; a.translation = translation; a.ratio = ratio; a.samples = samples;

@@ -46,6 +46,7 @@ __device__ __forceinline__ bool photo_pixel(const PhotoArgs& a, int n, int y, in
     const double px = (double)x + (double)fp[0] * (double)a.flow_scale, py = (double)y + (double)fp[1] * (double)a.flow_scale;
     // (every comparison is false for a NaN; an Inf fails one of them)
     if (!(px >= 0.0 && px <= (double)(a.W - 1) && py >= 0.0 && py <= (double)(a.H - 1))) return false;
+    // (pwc_bilinear_f64's table, written out: with the struct photometric_grad_kernel<3> needs 68 VGPRs and loses a wave per SIMD)
     const double fx0 = floor(px), fy0 = floor(py);
     const int x0 = (int)fx0, y0 = (int)fy0;
     const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);

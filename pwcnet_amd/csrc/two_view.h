@@ -1,25 +1,12 @@
 // two_view.h -- the per-pixel core that the cheirality vote and the depth kernel of pwc_pose.hip, pwc_trajectory.hip and the sums of
 // pwc_pose_refine.hip share, so that its order of operations is written once (include/pwc_hip.h, "relative pose and depth" and
-// "pose refinement"; tests/pose_ref.py and tests/pose_refine_ref.py restate it in numpy): the flow loads and the known-pixel rule of
-// pwc_fundamental.hip, SAMPSON as that file has it, the ray of a pixel, the triangulation of a pixel pair under a candidate pose, the
+// "pose refinement"; tests/pose_ref.py and tests/pose_refine_ref.py restate it in numpy): SAMPSON, which pwc_fundamental.hip's
+// weights and residual use too, the ray of a pixel, the triangulation of a pixel pair under a candidate pose, the
 // epipolar residual on the rays and the tangent basis of a translation.
 #pragma once
-#include "pwc_common.h"
+#include "flow_record.h"
 
 #pragma clang fp contract(off)
-
-template <bool VEC>
-__device__ __forceinline__ void two_view_load2(const float* p, float& a, float& b) {
-    if (VEC) {
-        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
-        a = v[0]; b = v[1];
-    } else {
-        a = p[0]; b = p[1];
-    }
-}
-
-__device__ __forceinline__ bool two_view_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }
-__device__ __forceinline__ bool two_view_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // (false for a NaN)
 
 // SAMPSON of "epipolar motion": r = p'^T F p and g = l0^2 + l1^2 + l'0^2 + l'1^2 with l = F p, l' = F^T p'.
 __device__ __forceinline__ void two_view_sampson(const double* f, double x, double y, double xp, double yp, double& r, double& g) {
@@ -34,7 +21,7 @@ __device__ __forceinline__ void two_view_sampson(const double* f, double x, doub
 
 // fx, fy, cx, cy usable: all finite, both focal lengths positive.
 __device__ __forceinline__ bool two_view_intrinsics_fine(const double* k) {
-    return two_view_finite(k[0]) && two_view_finite(k[1]) && two_view_finite(k[2]) && two_view_finite(k[3]) && k[0] > 0.0 && k[1] > 0.0;
+    return pwc_finite(k[0]) && pwc_finite(k[1]) && pwc_finite(k[2]) && pwc_finite(k[3]) && k[0] > 0.0 && k[1] > 0.0;
 }
 
 // What a pixel pair says under the pose (R, t), X' = R X + t.  d0 = K^-1 p = (d0x, d0y, 1) and d1 = K^-1 p' = (d1x, d1y, 1) are

@@ -140,7 +140,12 @@ def test_the_surface_header_signatures_sources_and_all():
     assert "pwc_fundamental.hip" in _lib.SOURCES and "pwc_homography.hip" in _lib.SOURCES and "motion_jacobi.h" in _lib.HEADERS
     for f in ("pwc_fundamental.hip", "motion_jacobi.h"):
         assert os.path.exists(os.path.join(_lib.CSRC, f))
-    source = open(os.path.join(_lib.CSRC, "pwc_fundamental.hip")).read() + open(os.path.join(_lib.CSRC, "motion_jacobi.h")).read()
+    source = ""
+    for f in ("pwc_fundamental.hip", "motion_jacobi.h", "two_view.h", "robust_fit.h", "flow_record.h"):   # the file and the project
+        text = open(os.path.join(_lib.CSRC, f)).read()                                                   # headers its numerics come from
+        assert ("#pragma clang fp contract(off)" in text or f == "motion_jacobi.h") and "fma" not in text.replace("fmax", ""), f
+        source += text
+    assert "two_view_sampson(" in source and "pwc_fit_gather<FUNDAMENTAL_SUMS>" in source and "pwc_flow_known(" in source
     assert "#pragma clang fp contract(off)" in source and "MOTION_JACOBI_SWEEPS 10" in source and "fma" not in source.replace("fmax", "")
     for name in ("fit_fundamental", "epipolar_residual", "epipolar_regions"):
         assert name in pwcnet_amd.__all__ and getattr(pwcnet_amd, name) is getattr(fundamental, name)

@@ -279,3 +279,16 @@ def test_c_abi_surface():
     args = ap.parse_args(["-i", "a", "b", "--motion", "similarity", "--motion_iters", "2", "--motion_scale", "0.5", "--stabilize", "3",
                           "--motion_residual"])
     assert (args.motion, args.motion_iters, args.motion_scale, args.stabilize, args.motion_residual) == ("similarity", 2, 0.5, 3, True)
+
+
+def test_shared_rules_are_written_once():
+    """The known-flow rule and the finite test stand in flow_record.h alone, the host's misalignment test in pwc_common.h alone,
+    the Sampson terms in two_view.h alone."""
+    from pwcnet_amd import _lib
+    texts = {f: open(os.path.join(_lib.CSRC, f), errors="replace").read() for f in _lib.SOURCES + _lib.HEADERS}
+    for literal, home in (("<= 1e9f", "flow_record.h"), ("1.7976931348623157e308", "flow_record.h"),
+                          ("reinterpret_cast<uintptr_t>(p) & mask", "pwc_common.h")):
+        assert [f for f, t in texts.items() if literal in t] == [home], literal
+    assert not [f for f, t in texts.items() if "1e9f" in t and f != "flow_record.h"]
+    assert not [f for f, t in texts.items() if "fundamental_sampson" in t]
+    assert [f for f, t in texts.items() if "void two_view_sampson(" in t] == ["two_view.h"]

@@ -195,8 +195,11 @@ def test_the_surface_header_signatures_sources_and_all():
     assert len(decl.split(",")) == len(_lib.SIGNATURES["pwc_triangulate_depth_f32"][1]) == 14
     assert "pwc_pose.hip" in _lib.SOURCES and "two_view.h" in _lib.HEADERS
     source = ""
-    for f in ("pwc_pose.hip", "two_view.h"):
-        source += open(os.path.join(_lib.CSRC, f)).read()
+    for f in ("pwc_pose.hip", "two_view.h", "flow_record.h"):
+        text = open(os.path.join(_lib.CSRC, f)).read()
+        assert "#pragma clang fp contract(off)" in text and "fma" not in text.replace("fmax", ""), f
+        source += text
+    assert "pwc_flow_known(" in source.split("// two_view.h")[0] and "pwc_flow_load2<VEC>" in source.split("// two_view.h")[0]
     assert "#pragma clang fp contract(off)" in source and "motion_jacobi<3>" in source and "fma" not in source.replace("fmax", "")
     L = _lib.lib()
     assert L.pwc_camera_pose_workspace_bytes(3) == 8 * 22 * 3 and L.pwc_camera_pose_workspace_bytes(0) == 0

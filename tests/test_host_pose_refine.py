@@ -255,6 +255,10 @@ def test_the_surface_header_signatures_sources_and_all():
     assert '#include "two_view.h"' in source and "#pragma clang fp contract(off)" in source and "motion_ldlt<5, 1>" in source
     assert "fma" not in source and "atomic" not in source.replace("No atomic", "")
     shared = open(os.path.join(_lib.CSRC, "two_view.h")).read()
+    for f in ("two_view.h", "robust_fit.h", "flow_record.h"):              # the project headers its numerics come from
+        text = open(os.path.join(_lib.CSRC, f)).read()
+        assert f in _lib.HEADERS and "#pragma clang fp contract(off)" in text and "fma" not in text and "atomic" not in text
+    assert '#include "robust_fit.h"' in source and "pwc_fit_write_part<REFINE_SUMS>" in source and "pwc_fit_gather<REFINE_SUMS>" in source
     assert "two_view_epipolar" in shared and "two_view_tangent_basis" in shared and "two_view_epipolar" in source
     L = _lib.lib()
     assert L.pwc_pose_refine_workspace_bytes(3, 48, 64) == 8 * (3 * 12 * 22 + 3 * 19) + 4 * 3 * 12

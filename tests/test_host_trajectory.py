@@ -154,6 +154,10 @@ def test_the_surface_header_signatures_sources_and_all():
     assert "pwc_trajectory.hip" in _lib.SOURCES
     source = open(os.path.join(_lib.CSRC, "pwc_trajectory.hip")).read()
     assert "#pragma clang fp contract(off)" in source and "two_view_triangulate" in source and "fma" not in source
+    for f in ("two_view.h", "flow_record.h"):                              # the project headers its numerics come from
+        text = open(os.path.join(_lib.CSRC, f)).read()
+        assert "#pragma clang fp contract(off)" in text and "fma" not in text
+    assert "pwc_flow_load2<VEC>" in source and "pwc_flow_known(" in source
     L = _lib.lib()
     assert L.pwc_scale_links_workspace_bytes(3, 8, 8, 0) == 4 * (2 * 5124 + 2 * 64) + 16
     assert L.pwc_scale_links_workspace_bytes(3, 8, 8, 1) == 4 * (3 * 5124 + 3 * 64) + 16
